@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — headline benchmark of the `equi_pers` hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One process per GPU.  A "step" is one full forward of the single-pass spherical_fusion model
@@ -9,6 +9,13 @@ One process per GPU.  A "step" is one full forward of the single-pass spherical_
 per-GPU batch of synthetic panoramas already resident in HBM.  Panoramas shard by image (no
 data-path collective), so scaling is weak: every rank processes `--batch` panoramas
 per step and `value` = all panoramas of all ranks / max-over-ranks time.
+
+A plain run does only what `value` needs: set-up, warm-up, the K timed steps, the result line.
+`--full` adds every other figure of the result line (a longer timed region, one-at-a-time and stage
+times, resample rooflines and other shapes, host- and PNG-fed rates, one panorama per forward,
+BASELINE cfg 3, the CPU baseline) and the bit-for-bit cross-checks between execution modes.
+`--dump-outputs DIR` writes what the last timed step returned, DIR/depth.npy (float32, every rank's
+panoramas in rank order; a fixed sample of it above 64 MB); the inputs depend only on the arguments.
 
 Workload notes (DESIGN.md "Measurement"):
   * the reference network only exists at patch size 128 (SURVEY.md finding 0.1: its token width is
@@ -39,6 +46,7 @@ MFMA_F32_PEAK_TFLOPS = 157.3   # v_mfma_f32_32x32x2_f32 dense peak (= the fp32 v
 MFMA_F16_PEAK_TFLOPS = 2500.0  # v_mfma_f32_32x32x16_f16 dense peak (MI355X_MICROARCH.md); the f16x3 mode issues 3 of them per product
 ERP_H, ERP_W, NROWS, NPATCH, FOV = 512, 1024, 4, 18, (80.0, 80.0)
 NET_GFLOP_PER_PANO = 71.3      # 2 x 35.66 GMAC at P=128, N=18 (probed with forward hooks)
+DUMP_MAX_BYTES = 60 * 10**6    # --dump-outputs payload: under 64 MB in all, with room for the .npy headers
 
 
 def parse():
@@ -48,8 +56,13 @@ def parse():
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--batch", type=int, default=8, help="panoramas per GPU per step (8 = BASELINE cfg 4 shard)")
     ap.add_argument("--depth", type=int, default=3, help="forwards in flight per GPU (spherical_fusion.pipelined); 1 = one at a time")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _omp_threads(n):
@@ -315,46 +328,32 @@ def pmc_traffic(B, name="resample_traffic.json"):
     return d["traffic_bytes"], d.get("note", "")
 
 
-def main():
-    args = parse()
-    from omnifusion_amd import dist
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # started as a plain process: become N ranks, one per GPU (the driver's own launch form:
-        # python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
-        sys.exit(dist.respawn_under_launcher(os.path.abspath(__file__), sys.argv[1:], args.gpus))
-    assert torch.cuda.is_available(), "bench.py needs an MI355X (no CPU fallback exists)"
-    # one rank per GPU over RCCL.  (OMNI_BENCH_DIST_BACKEND=gloo lets the multi-rank path be exercised with several ranks
-    # sharing one GPU on a single-GPU box; the real launch is nccl = RCCL with LOCAL_RANK == device index.)
-    backend = os.environ.get("OMNI_BENCH_DIST_BACKEND", "nccl")
-    if dist.env_rank()[2] != args.gpus:
-        raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started WORLD_SIZE={dist.env_rank()[2]} ranks")
-    rank, local, world, dev = dist.init(backend)
-    local = dev.index
+def write_outputs(outdir, arrays):
+    """--dump-outputs: DIR/<name>.npy in float32 for every array the timed path returned.  Above DUMP_MAX_BYTES in all, each array is
+    replaced by a fixed sample of its flattened elements: one element per stratum of equal width, the offset inside each stratum drawn from
+    numpy's PCG64 with seed 0, so that runs with the same arguments sample the same positions."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_MAX_BYTES:
+            stride = -(-total // DUMP_MAX_BYTES)
+            base = np.arange(0, a.size - stride + 1, stride)
+            a = a.reshape(-1)[base + np.random.default_rng(0).integers(0, stride, base.size)]
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
+
+def resample_legs(dev, rank, B, rgb, g, steps):
+    """--full: the resample pair at the metric's patch size (18 x 256^2), same run, HIP events on the launch stream — measured BEFORE the
+    matrix-bound steps, in its own steady state (after 2500 panoramas/s of MFMA load the chip sits at its power-capped clock and the
+    same two kernels measure 5 % slower: round 2, 45.2 % in here vs 48 % in tools/kbench.py)"""
     from omnifusion_amd import _lib
     from omnifusion_amd.equi_pers.equi2pers_v3 import equi2pers_patches
     from omnifusion_amd.equi_pers.pers2equi_v3 import pers2equi
-    from omnifusion_amd.model.spherical_model import spherical_fusion
-    from omnifusion_amd.weights import make_state_dict
-    _lib.load()
-    if world > 1:                                              # sharded runs reproduce single-GPU results bit for bit whatever the
-        from omnifusion_amd.model._engine import Engine       # per-rank batch (SURVEY 8d parity gate): one split-K plan for all sizes
-        Engine.latency_plan = False
-
-    B = args.batch
-    g = torch.Generator(device="cpu").manual_seed(1234 + rank)
-    rgb = torch.rand((B, 3, ERP_H, ERP_W), generator=g).to(dev)               # synthetic RGB panoramas (BGR/255-like range)
-    net = spherical_fusion(NROWS, NPATCH, (128, 128), FOV).cuda(local)
-    net.load_state_dict(make_state_dict(42, NPATCH, False))                   # random-init weights of the reference architecture
-    eng = net._eng
     LAY = _lib.LAYOUT_BNCHW
-
-    # ---- the resample pair at the metric's patch size (18 x 256^2), same run, HIP events on the launch stream — measured BEFORE the
-    # matrix-bound steps, in its own steady state (after 2500 panoramas/s of MFMA load the chip sits at its power-capped clock and the
-    # same two kernels measure 5 % slower: round 2, 45.2 % in here vs 48 % in tools/kbench.py)
     P = 256
     depth_patches = torch.rand((B, NPATCH, 1, P, P), generator=g).to(dev)
-    K = max(args.steps, 20)
+    K = max(steps, 20)
     f_e2p = lambda: equi2pers_patches(rgb, FOV, NROWS, (P, P), layout=LAY)
     f_p2e = lambda: pers2equi(depth_patches, FOV, NROWS, (P, P), (ERP_H, ERP_W), None, layout=LAY)
     t_heat = time.perf_counter()
@@ -396,21 +395,17 @@ def main():
                            "fp32": resample_pair(dev, 1, 2048, 4096, 6, 512, torch.float32),
                            "fp16_b4": resample_pair(dev, 4, 2048, 4096, 6, 512, torch.float16, reps=8)}
         torch.cuda.empty_cache()
+    return {"r_e2p": r_e2p, "r_p2e": r_p2e, "rr_e2p": rr_e2p, "rr_p2e": rr_p2e, "t_pair": t_pair, "bytes_e2p": bytes_e2p,
+            "bytes_p2e": bytes_p2e, "gbs_pair": gbs_pair, "configs": configs}
 
-    dominant = dominant_kernel(dev, B) if (rank == 0 and eng.precision == "f16x3") else None
-    if dominant is not None:
-        pm, why = profile_json("conv_pmc.json")                        # tools/pmc_conv.sh: mfma_busy of the same kernel form, hash-matched
-        dominant["mfma_busy_from_profile"] = (pm or {}).get("mfma_busy", {}).get("conv_sh_kernel<128,128,4,2,3,4,PP>")
-        dominant["mfma_busy_note"] = why or (pm or {}).get("note", "")
-    shares, shares_note = profile_json("bench_kernel_shares.json")     # tools/prof_bench.sh: per-kernel-family shares of the timed region's GPU time
-    # Bring the GPU out of its idle power state before anything is counted (sclk idles at ~366 MHz and takes tens of
-    # milliseconds of load to ramp: a 5-step warm-up measured 1600-2200 panoramas/s on a box that then holds 2650).
-    t_heat = time.perf_counter()
-    while time.perf_counter() - t_heat < 0.3:
-        net(rgb, confidence=True)
-        torch.cuda.synchronize()
-    # ---- stage breakdown: a few forwards one at a time, stage by stage, HIP events on the launch stream (not the timed region)
-    nbr = max(5, min(args.steps, 20))
+
+def stage_breakdown(net, rgb, B, steps):
+    """--full: a few forwards one at a time, stage by stage, HIP events on the launch stream (not the timed region).  Returns the
+    one-at-a-time seconds per forward, its output (compared bit for bit with the pipelined one) and the seconds of each stage."""
+    from omnifusion_amd import _lib
+    from omnifusion_amd.equi_pers.equi2pers_v3 import equi2pers_patches
+    eng, LAY = net._eng, _lib.LAYOUT_BNCHW
+    nbr = max(5, min(steps, 20))
     ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(nbr)]
     state = {"depth": None}
 
@@ -432,29 +427,20 @@ def main():
         staged(k)
     torch.cuda.synchronize()
     t_un = (time.perf_counter() - t_un) / nbr
-    depth_seq = state["depth"].clone()
     sec = lambda i: float(np.mean([ev[k][i].elapsed_time(ev[k][i + 1]) for k in range(nbr)])) * 1e-3
-    t_e2p, t_net, t_p2e = sec(0), sec(1), sec(2)
+    return {"t_un": t_un, "depth_seq": state["depth"].clone(), "t_e2p": sec(0), "t_net": sec(1), "t_p2e": sec(2)}
 
-    # ---- the timed region: W untimed steps, barrier + synchronize, EXACTLY K steps, barrier + synchronize, MAX over ranks
-    # (omnifusion_amd/dist.py).  A step submits one complete forward of the batch; with --depth D > 1 up to D forwards are in
-    # flight on D streams (spherical_fusion.pipelined: consecutive batches overlap, every kernel works on the whole batch) and a
-    # step retires the forward submitted D steps earlier; the closing synchronize waits for all K.
-    depth = max(1, args.depth)
-    run = net.pipelined(depth)
-    pending = collections.deque()
 
-    def step():
-        pending.append(run(rgb, confidence=True))
-        if len(pending) > depth:
-            state["depth"] = pending.popleft().get()
-
-    dt = dist.timed_steps(step, args.steps, args.warmup, dev)
-    while pending:
-        state["depth"] = pending.popleft().get()
-    torch.cuda.synchronize()
-    # ... and a second region of at least 0.5 s (20 steps are 44 ms — too short to separate +-3 % of box noise); the contract's
-    # K-step region above stays `value`, this one is reported beside it as `value_long`
+def full_legs(args, dev, rank, world, B, g, net, rgb, run, step, pending, state, dt, rs, stages, dominant, shares, shares_note):
+    """--full: everything the result line reports beyond the timed region — a longer timed region, the pipelined vs one-at-a-time
+    bit-for-bit check, host- and PNG-fed rates, the PCIe link, one panorama per forward (eager, graph, request stream), BASELINE cfg 3,
+    and the MFMA / HBM rooflines.  Returns the result line's extra keys."""
+    from omnifusion_amd import dist
+    from omnifusion_amd.model.spherical_model import spherical_fusion
+    from omnifusion_amd.weights import make_state_dict
+    eng, depth, configs = net._eng, run.depth, rs["configs"]
+    # a second region of at least 0.5 s (VERDICT r3 #7: 20 steps are 44 ms — too short to separate +-3 % of box noise); the contract's
+    # K-step region stays `value`, this one is reported beside it as `value_long`
     steps_long = max(args.steps, int(np.ceil(0.5 / (dt / args.steps))))
     dt_long = dist.timed_steps(step, steps_long, 0, dev)
     while pending:
@@ -462,9 +448,12 @@ def main():
     torch.cuda.synchronize()
     depth_map = state["depth"]
     assert depth_map.shape == (B, 1, ERP_H, ERP_W) and bool(torch.isfinite(depth_map).all())
-    assert torch.equal(depth_map, depth_seq), "pipelined and one-at-a-time forwards must agree bit for bit"
+    assert torch.equal(depth_map, stages["depth_seq"]), "pipelined and one-at-a-time forwards must agree bit for bit"
     tflops = NET_GFLOP_PER_PANO * B * args.steps / dt / 1e3            # whole-GPU rate over the timed region (resample launches included)
     f16x3 = eng.precision == "f16x3"
+    t_un, t_e2p, t_net, t_p2e = stages["t_un"], stages["t_e2p"], stages["t_net"], stages["t_p2e"]
+    r_e2p, r_p2e, rr_e2p, rr_p2e, t_pair = rs["r_e2p"], rs["r_p2e"], rs["rr_e2p"], rs["rr_p2e"], rs["t_pair"]
+    bytes_e2p, bytes_p2e, gbs_pair = rs["bytes_e2p"], rs["bytes_p2e"], rs["gbs_pair"]
 
     traffic, traffic_note = pmc_traffic(B)
     net_traffic, net_traffic_note = pmc_traffic(B, "network_traffic.json")
@@ -560,7 +549,7 @@ def main():
     cfg3_ms = None
     if rank == 0:
         from omnifusion_amd.model.spherical_model_iterative import spherical_fusion as spherical_fusion_iterative
-        net3 = spherical_fusion_iterative(6, 46, (128, 128), FOV).cuda(local)
+        net3 = spherical_fusion_iterative(6, 46, (128, 128), FOV).cuda(dev.index)
         net3.load_state_dict(make_state_dict(42, 46, True))
         x3 = torch.rand((1, 3, 1024, 2048), generator=g).to(dev)
         for _ in range(3):
@@ -576,20 +565,8 @@ def main():
         configs["cfg3"]["note"] = "2-iteration iterative model at patch size 128 (SURVEY 0.1), one 1024x2048 panorama per forward; resample pair at 46 x 256^2, B = 1"
         del net3, x3, o3
 
-    out = {
-        "metric": "panoramas/sec at 512x1024 ERP, N=18 256^2 patches; equi2pers+pers2equi GB/s vs HBM peak",
-        "value": world * B * args.steps / dt, "unit": "panoramas/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+    return {
         "value_long": world * B * steps_long / dt_long, "steps_long": steps_long, "ms_per_step_long": dt_long / steps_long * 1e3,
-        "vs_baseline": None, "dtype": "f16x3 (fp16 hi/lo pairs, fp32 accumulate: fp32-class)" if f16x3 else "f32", "data": "synthetic",
-        "config": {"workload": f"cfg2/cfg4 shard: {B} panoramas/GPU/step, 512x1024 ERP, fov 80, nrows 4 (18 patches); full "
-                               "single-pass spherical_fusion forward (confidence=True) at patch size 128 — the only size the "
-                               "reference network exists at (SURVEY 0.1); random-init weights (seed 42); inputs resident in HBM; "
-                               "resample pair at 18x256^2 reported in roofline_resample",
-                   "per_gpu_batch": B, "global_batch": B * world, "parallelism": f"image-sharded x{world}",
-                   "execution": (f"{depth} forwards in flight per GPU on {depth} streams (spherical_fusion.pipelined)" if depth > 1 else
-                                 "one forward at a time" + (f", two half-batch lanes" if B >= 2 * net.LANES else ""))},
         "pipelining": {"depth": depth, "value_one_at_a_time": world * B / t_un, "ms_per_forward_one_at_a_time": t_un * 1e3,
                        "note": "value_one_at_a_time: the same forwards issued one after the other (two half-batch lanes inside each), "
                                "this rank's rate x ranks; outputs of the two modes are compared bit for bit in this run"},
@@ -651,8 +628,101 @@ def main():
                               "method": "one HIP event pair around 20+ back-to-back launches of the kernel, queued behind device-side spinning (agrees with rocprofv3 --kernel-trace: profiles/r03b_event_method.txt); mean of 3 such runs; measured before the matrix-bound steps"},
         "configs": configs,
     }
+
+
+def main():
+    args = parse()
+    from omnifusion_amd import dist
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        # started as a plain process: become N ranks, one per GPU (the driver's own launch form:
+        # python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
+        sys.exit(dist.respawn_under_launcher(os.path.abspath(__file__), sys.argv[1:], args.gpus))
+    assert torch.cuda.is_available(), "bench.py needs an MI355X (no CPU fallback exists)"
+    # one rank per GPU over RCCL.  (OMNI_BENCH_DIST_BACKEND=gloo lets the multi-rank path be exercised with several ranks
+    # sharing one GPU on a single-GPU box; the real launch is nccl = RCCL with LOCAL_RANK == device index.)
+    backend = os.environ.get("OMNI_BENCH_DIST_BACKEND", "nccl")
+    if dist.env_rank()[2] != args.gpus:
+        raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started WORLD_SIZE={dist.env_rank()[2]} ranks")
+    rank, local, world, dev = dist.init(backend)
+    local = dev.index
+
+    from omnifusion_amd import _lib
+    from omnifusion_amd.model.spherical_model import spherical_fusion
+    from omnifusion_amd.weights import make_state_dict
+    _lib.load()
+    if world > 1:                                              # sharded runs reproduce single-GPU results bit for bit whatever the
+        from omnifusion_amd.model._engine import Engine       # per-rank batch (SURVEY 8d parity gate): one split-K plan for all sizes
+        Engine.latency_plan = False
+
+    B = args.batch
+    g = torch.Generator(device="cpu").manual_seed(1234 + rank)
+    rgb = torch.rand((B, 3, ERP_H, ERP_W), generator=g).to(dev)               # synthetic RGB panoramas (BGR/255-like range)
+    net = spherical_fusion(NROWS, NPATCH, (128, 128), FOV).cuda(local)
+    net.load_state_dict(make_state_dict(42, NPATCH, False))                   # random-init weights of the reference architecture
+    eng = net._eng
+    f16x3 = eng.precision == "f16x3"
+
+    rs, dominant, shares, shares_note = None, None, None, ""
+    if args.full:
+        rs = resample_legs(dev, rank, B, rgb, g, args.steps)
+        dominant = dominant_kernel(dev, B) if (rank == 0 and f16x3) else None
+        if dominant is not None:
+            pm, why = profile_json("conv_pmc.json")                    # tools/pmc_conv.sh: mfma_busy of the same kernel form, hash-matched
+            dominant["mfma_busy_from_profile"] = (pm or {}).get("mfma_busy", {}).get("conv_sh_kernel<128,128,4,2,3,4,PP>")
+            dominant["mfma_busy_note"] = why or (pm or {}).get("note", "")
+        shares, shares_note = profile_json("bench_kernel_shares.json")  # tools/prof_bench.sh: per-kernel-family shares of the timed region's GPU time
+    # Bring the GPU out of its idle power state before anything is counted (sclk idles at ~366 MHz and takes tens of
+    # milliseconds of load to ramp: a 5-step warm-up measured 1600-2200 panoramas/s on a box that then holds 2650).
+    t_heat = time.perf_counter()
+    while time.perf_counter() - t_heat < 0.3:
+        net(rgb, confidence=True)
+        torch.cuda.synchronize()
+    stages = stage_breakdown(net, rgb, B, args.steps) if args.full else None
+
+    # ---- the timed region: W untimed steps, barrier + synchronize, EXACTLY K steps, barrier + synchronize, MAX over ranks
+    # (omnifusion_amd/dist.py).  A step submits one complete forward of the batch; with --depth D > 1 up to D forwards are in
+    # flight on D streams (spherical_fusion.pipelined: consecutive batches overlap, every kernel works on the whole batch) and a
+    # step retires the forward submitted D steps earlier; the closing synchronize waits for all K.
+    depth = max(1, args.depth)
+    run = net.pipelined(depth)
+    pending = collections.deque()
+    state = {"depth": None}
+
+    def step():
+        pending.append(run(rgb, confidence=True))
+        if len(pending) > depth:
+            state["depth"] = pending.popleft().get()
+
+    dt = dist.timed_steps(step, args.steps, args.warmup, dev)
+    while pending:
+        state["depth"] = pending.popleft().get()
+    torch.cuda.synchronize()
+    last = state["depth"]                                                     # what the last timed step's forward returned
+    assert last.shape == (B, 1, ERP_H, ERP_W) and bool(torch.isfinite(last).all())
+
+    out = {
+        "metric": "panoramas/sec at 512x1024 ERP, N=18 256^2 patches; equi2pers+pers2equi GB/s vs HBM peak",
+        "value": world * B * args.steps / dt, "unit": "panoramas/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f16x3 (fp16 hi/lo pairs, fp32 accumulate: fp32-class)" if f16x3 else "f32", "data": "synthetic",
+        "config": {"workload": f"cfg2/cfg4 shard: {B} panoramas/GPU/step, 512x1024 ERP, fov 80, nrows 4 (18 patches); full "
+                               "single-pass spherical_fusion forward (confidence=True) at patch size 128 — the only size the "
+                               "reference network exists at (SURVEY 0.1); random-init weights (seed 42); inputs resident in HBM; "
+                               "resample pair at 18x256^2 reported in roofline_resample",
+                   "per_gpu_batch": B, "global_batch": B * world, "parallelism": f"image-sharded x{world}",
+                   "execution": (f"{depth} forwards in flight per GPU on {depth} streams (spherical_fusion.pipelined)" if depth > 1 else
+                                 "one forward at a time" + (f", two half-batch lanes" if B >= 2 * net.LANES else ""))},
+    }
+    if args.full:
+        out.update(full_legs(args, dev, rank, world, B, g, net, rgb, run, step, pending, state, dt, rs, stages, dominant, shares, shares_note))
+    if args.dump_outputs:
+        depth_all = dist.gather_batch(last, world * B)                        # every rank's panoramas, rank order
+        if rank == 0:
+            write_outputs(args.dump_outputs, {"depth": depth_all.cpu().numpy()})
     if rank == 0:
-        out["cpu_baseline"] = None if args.no_cpu_baseline or world > 1 else cpu_baseline()
+        if args.full:
+            out["cpu_baseline"] = None if args.no_cpu_baseline or world > 1 else cpu_baseline()
         print(json.dumps(out))
     dist.finalize()
 

@@ -9,7 +9,7 @@ tools/pmc_conv.sh $tag > /dev/null 2>&1                      # mfma_busy per ker
 cp $O/${tag}_resample_traffic.json $R/profiles/resample_traffic.json; cp $O/${tag}_network_traffic.json $R/profiles/network_traffic.json; cp $O/conv_pmc.json $R/profiles/conv_pmc.json
 tools/prof_bench.sh $tag > /dev/null 2>&1                    # per-kernel stats of the bench command -> bench_kernel_shares.json (roofline.kernel_time_shares)
 cp $O/bench_kernel_shares.json $R/profiles/bench_kernel_shares.json
-python bench.py > $O/${tag}_bench.log 2>&1; tail -1 $O/${tag}_bench.log > $O/${tag}_bench.json
+python bench.py --full > $O/${tag}_bench.log 2>&1; tail -1 $O/${tag}_bench.log > $O/${tag}_bench.json
 python tools/clocks_under_load.py 2>&1 | grep -v amdgpu.ids > $O/${tag}_clocks_under_load.txt
 cd /tmp && export TMPDIR=/tmp
 for b in 8 1; do

@@ -6,7 +6,7 @@
 tag=$1
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O
 cd $R
-python bench.py > $O/${tag}_bench.log 2>&1; tail -1 $O/${tag}_bench.log > $O/${tag}_bench.json
+python bench.py --full > $O/${tag}_bench.log 2>&1; tail -1 $O/${tag}_bench.log > $O/${tag}_bench.json
 tools/prof_bench.sh $tag > /dev/null 2>&1
 cd /tmp && export TMPDIR=/tmp
 for b in 8 1; do
