@@ -176,6 +176,13 @@ int omni_conv2d_nhwc_f16x3_ws(const float* src1, const float* src2, const void* 
  * (else fp32 NHWC), fmt bit 1: res is fp32 NHWC (else SH), fmt bit 2: latency form — the caller runs so few images (one panorama) that the
  * kernel choice for 16-pixel-wide images should stay with the im2col tiles (results equal up to the K summation order) and the epilogue with
  * the direct 8-byte stores (same bits); wt16 as above.
+ * fmt bit 3 (value 8): "f16x1" — ONE v_mfma_f32_32x32x16_f16 per product block, src_hi . wt_hi with fp32 accumulation: the lo halves of
+ * the activations and of wt16 stay in memory (same layouts, same sizes) but are not multiplied.  Every kernel form this operator dispatches
+ * (whatever omni_set_option chose: tile sizes, ping-pong, loader waves, halo forms, split-K) has its f16x1 instantiation; bias, residual,
+ * activation, split-K reduction and the SH split of the output are those of f16x3.  The mode is per call (no global state): calls of
+ * both modes may be interleaved and may run on concurrent streams.  Accuracy: ~1e-3 relative per product (fp16 operands).
+ * Entry points without an f16x1 form (omni_conv3x3_wino_sh_f16x3, omni_gemm_rows_sh_f16x3, omni_gemm_rows_ln_sh_f16x3,
+ * omni_gemm_sh_f16x3_ln512_ws) return OMNI_ERR_UNSUPPORTED for fmt bit 3.
  * omni_sh_from_f32 / omni_sh_to_f32 convert n elements (n % 32 == 0). */
 int omni_conv2d_sh_f16x3_ws(const void* src1, const void* src2, const void* wt16, const float* bias,
                             const void* res, void* dst, int fmt, int M, int H, int W, int C1, int C2, int Cout,
@@ -197,7 +204,8 @@ int omni_gemm_rows_ln_sh_f16x3(const float* x, const float* ln_weight, const flo
                                const float* res, void* dst, int fmt, int rows, int N, int act, omni_stream_t stream);
 /* F.interpolate(scale_factor 2, bilinear, align_corners=False) + ConvBnReLU (3x3, pad 1) of the decoder, model/spherical_model.py:
  * 279-301, in ONE kernel: the up-sampled tensor never exists.  src SH [M,Hl,Wl,C], dst [M,2Hl,2Wl,Cout] SH (fmt bit 0) or fp32;
- * 2Wl % 32 == 0 and 2Hl % 4 == 0 (else OMNI_ERR_UNSUPPORTED: omni_upsample_bilinear_sh + omni_conv2d_sh_f16x3_ws give the same bits). */
+ * 2Wl % 32 == 0 and 2Hl % 4 == 0 (else OMNI_ERR_UNSUPPORTED: omni_upsample_bilinear_sh + omni_conv2d_sh_f16x3_ws give the same bits).
+ * fmt bit 3: f16x1 as for omni_conv2d_sh_f16x3_ws (the product takes the hi split of the up-sampled value). */
 int omni_conv3x3_up2_sh_f16x3(const void* src, const void* wt16, const float* bias, void* dst, int fmt,
                               int M, int Hl, int Wl, int C, int Cout, int act, omni_stream_t stream);
 /* de_conv4_0 AND the two heads in one pass over the widest tensor of the network (model/spherical_model.py:300-307: F.interpolate + ConvBnReLU 32 -> 32,
@@ -207,6 +215,9 @@ int omni_conv3x3_up2_sh_f16x3(const void* src, const void* wt16, const float* bi
  * the fp32 summation order of the heads (whose products run f16x3 here).  Deterministic. */
 size_t omni_up2_heads_scratch_bytes(int M, int P);
 int omni_conv3x3_up2_heads_sh_f16x3(const void* src, const void* wt16, const float* bias, const void* heads_w16f, float bias_pred, float bias_weight,
+                                    float* scratch, size_t scratch_bytes, float* out_a, float* out_c, int M, int P, int confidence, omni_stream_t stream);
+/* The same operator with de_conv4_0 in f16x1 (see omni_conv2d_sh_f16x3_ws, fmt bit 3); the two heads' own products stay f16x3.  Same arguments. */
+int omni_conv3x3_up2_heads_sh_f16x1(const void* src, const void* wt16, const float* bias, const void* heads_w16f, float bias_pred, float bias_weight,
                                     float* scratch, size_t scratch_bytes, float* out_a, float* out_c, int M, int P, int confidence, omni_stream_t stream);
 /* w [2][9][32] fp32 (HOST memory) -> the 4 KB fragment-ordered f16x3 operand of omni_conv3x3_up2_heads_sh_f16x3 (HOST memory; copy it to the device). */
 int omni_heads_pack_f16x3(const float* w_host, void* dst_host);
@@ -249,6 +260,8 @@ int omni_stem_sh(const float* src, const float* wt, const float* bias, void* dst
 /* the stem as an implicit GEMM on the fp16 matrix cores (f16x3): wt16 = the folded filter bank [64][192], k = (c*7+ky)*8+kx
  * (kx = 7 and k >= 168 zero), split into [64][6][hi32|lo32]; P % 32 == 0 */
 int omni_stem_sh_f16x3(const float* src, const void* wt16, const float* bias, void* dst, int M, int P, omni_stream_t stream);
+/* the same stem in f16x1: one matrix instruction per product block, fp16(input) . wt_hi with fp32 accumulation.  Same arguments. */
+int omni_stem_sh_f16x1(const float* src, const void* wt16, const float* bias, void* dst, int M, int P, omni_stream_t stream);
 int omni_maxpool3x3s2_sh(const void* src, void* dst, int M, int H, int W, int C, omni_stream_t stream);
 int omni_upsample_bilinear_sh(const void* src, void* dst, int M, int H, int W, int C, int Ho, int Wo, omni_stream_t stream);
 int omni_add_hw_sh(void* x, const float* y, int M, int HW, int C, omni_stream_t stream);

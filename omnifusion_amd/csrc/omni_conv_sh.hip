@@ -95,6 +95,16 @@ template <int N> __device__ __forceinline__ void wait_vm()
 // panoramas on two streams (1 of 30 at 16) with the 4-wave halo kernel, none in 3000 with the wait (tools/lanes_trace.py).
 __device__ __forceinline__ void wait_lds_reads() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
+// The arithmetic mode of a convolution kernel (template flag X1, fmt bit 3 of the C ABI): false = "f16x3", three matrix instructions per
+// product block, x = acc + 2^-11 acc1 with acc = A_hi.W_hi and acc1 = A_hi.W_lo + A_lo.W_hi; true = "f16x1", ONE matrix instruction,
+// A_hi.W_hi, with fp32 accumulation: the lo fragments are never read, acc1 is never written and its registers do not exist (the operand
+// tiles still arrive as whole 128-byte hi|lo rows: the loaders and their counted waits are the same code).
+template <bool X1> __device__ __forceinline__ float acc_join(float a1, float a0)
+{
+    if constexpr (X1) return a0;
+    else return fmaf(a1, 4.8828125e-4f, a0);
+}
+
 struct ShConvArgs {
     const void* src1; const void* src2;      // SH activations [M,H,W,C1], [M,H,W,C2] (src2 may be null)
     const void* wt;                          // halfs [Cout][KH*KW*(C1+C2)/32][hi32|lo32], BN folded
@@ -119,7 +129,7 @@ struct ShConvArgs {
 // consecutive channels c0[j] + 8q + 4(lane>>5) .. +3 of its pixel).  Two phases: every bias / residual load is issued
 // before the first store, so the loads overlap instead of serialising load -> wait -> store once per quad.
 // QC: register quads of a tile whose loads are in flight together (4 = all; 2 where the register budget is tight)
-template <int NT, int QC = 4>
+template <int NT, int QC = 4, bool X1 = false>
 __device__ __forceinline__ void epilogue_row(const f16v (&acc)[NT], const f16v (&acc1)[NT], const ShConvArgs& a, size_t r,
                                              const int (&c0)[NT], int lane, bool dst_sh)
 {
@@ -146,7 +156,7 @@ __device__ __forceinline__ void epilogue_row(const f16v (&acc)[NT], const f16v (
                 const int q = q0 + qq, c = c0[j] + 8 * q + 4 * (lane >> 5);
                 f4v v;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaf(acc1[j][4 * q + e], 4.8828125e-4f, acc[j][4 * q + e]);
+                for (int e = 0; e < 4; ++e) v[e] = acc_join<X1>(acc1[j][4 * q + e], acc[j][4 * q + e]);
                 v += bq[j * QC + qq];
                 if (a.res && a.res_f32) v += rf[j * QC + qq];
                 else if (a.res) v += sh_join4(rh[j * QC + qq], rl[j * QC + qq]);
@@ -173,7 +183,7 @@ __device__ __forceinline__ void epilogue_row(const f16v (&acc)[NT], const f16v (
 // POST: the caller may carry a post-activation addend (a.post) — only the halo kernel does; the tile kernel compiles the addend's registers
 // away.  The tasks are processed HALF at a time (loads of a half issued together, then its arithmetic and stores): the live set is what lets
 // conv_sh_kernel<128,128,4,2,3,4> — twelve waves per block, a 168-register budget — run its epilogue without scratch (it carried 236 B).
-template <int NT, bool POST = true>
+template <int NT, bool POST = true, bool X1 = false>
 __device__ __forceinline__ void epilogue_tile_lds(const f16v (&acc)[NT], const f16v (&acc1)[NT], const ShConvArgs& a, size_t r0, int nrows,
                                                   const int (&c0)[NT], int lane, float* tile, size_t r1 = ~(size_t)0)
 {
@@ -187,7 +197,7 @@ __device__ __forceinline__ void epilogue_tile_lds(const f16v (&acc)[NT], const f
             for (int q = 0; q < 4; ++q) {
                 f4v v;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaf(acc1[j][4 * q + e], 4.8828125e-4f, acc[j][4 * q + e]);
+                for (int e = 0; e < 4; ++e) v[e] = acc_join<X1>(acc1[j][4 * q + e], acc[j][4 * q + e]);
                 *reinterpret_cast<f4v*>(tile + px * PITCH + 32 * j + 8 * q + 4 * (lane >> 5)) = v;
             }
     }
@@ -292,9 +302,10 @@ __constant__ float wino_coef[16][4] = {                        // [p = 4 xi + nu
     {1, 0, 1, 0}, {1, 1, 1, 1}, {1, -1, 1, -1}, {0, -1, 0, -1},
     {1, 0, -1, 0}, {1, 1, -1, -1}, {1, -1, -1, 1}, {0, -1, 0, 1},
     {0, 0, -1, 0}, {0, 0, -1, -1}, {0, 0, -1, 1}, {0, 0, 0, 1}};
-template <int BM, int BN, int WM, int WN, int NST = 3, int NL = 0, bool PP = false, bool WINO = false>           // NST stages in flight (the step loop is unrolled by it)
+template <int BM, int BN, int WM, int WN, int NST = 3, int NL = 0, bool PP = false, bool WINO = false, bool X1 = false>   // NST stages in flight (the step loop is unrolled by it); X1: f16x1 (acc_join)
 __global__ __launch_bounds__(64 * (WM * WN + NL)) void conv_sh_kernel(ShConvArgs a)
 {
+    static_assert(!(WINO && X1), "Winograd: f16x3 only");
     static_assert(!PP || (NL > 0 && WM * WN == 8 && NST >= 3), "ping-pong: eight matrix waves (two per SIMD) + loader waves, three stages");
     static_assert(!WINO || (PP && BM / WM == 32 && BN / WN == 32), "Winograd: the ping-pong kernel with 32 x 32 wave tiles");
     constexpr int NW = WM * WN, LW = NL > 0 ? NL : NW, RPP = 8 * LW;   // matrix waves; waves that issue DMA; tile rows covered by one DMA pass of the block
@@ -518,12 +529,12 @@ __global__ __launch_bounds__(64 * (WM * WN + NL)) void conv_sh_kernel(ShConvArgs
 #pragma unroll
                 for (int i = 0; i < TM; ++i) {
                     ah[kc][i] = *reinterpret_cast<const h8v*>(sl + i * 4096 + foa[kc]);
-                    al[kc][i] = *reinterpret_cast<const h8v*>(sl + i * 4096 + foa[2 + kc]);
+                    if constexpr (!X1) al[kc][i] = *reinterpret_cast<const h8v*>(sl + i * 4096 + foa[2 + kc]);
                 }
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     bh[kc][j] = *reinterpret_cast<const h8v*>(sl + j * 4096 + fob[kc]);
-                    bl[kc][j] = *reinterpret_cast<const h8v*>(sl + j * 4096 + fob[2 + kc]);
+                    if constexpr (!X1) bl[kc][j] = *reinterpret_cast<const h8v*>(sl + j * 4096 + fob[2 + kc]);
                 }
             }
             wait_lds_reads();                                        // the fragments are in registers before the phase ends (the buffer may be refilled two phases later)
@@ -537,8 +548,10 @@ __global__ __launch_bounds__(64 * (WM * WN + NL)) void conv_sh_kernel(ShConvArgs
 #pragma unroll
                     for (int j = 0; j < TN; ++j) {
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[kc][j], ah[kc][i], acc[i][j], 0, 0, 0);
-                        acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[kc][j], ah[kc][i], acc1[i][j], 0, 0, 0);
-                        acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[kc][j], al[kc][i], acc1[i][j], 0, 0, 0);
+                        if constexpr (!X1) {
+                            acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[kc][j], ah[kc][i], acc1[i][j], 0, 0, 0);
+                            acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[kc][j], al[kc][i], acc1[i][j], 0, 0, 0);
+                        }
                     }
             if constexpr (OMNI_PP_PRIO) __builtin_amdgcn_s_setprio(0);
         };
@@ -659,12 +672,12 @@ __global__ __launch_bounds__(64 * (WM * WN + NL)) void conv_sh_kernel(ShConvArgs
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 ah[kc][i] = *reinterpret_cast<const h8v*>(sl + i * 4096 + foa[kc]);
-                al[kc][i] = *reinterpret_cast<const h8v*>(sl + i * 4096 + foa[2 + kc]);
+                if constexpr (!X1) al[kc][i] = *reinterpret_cast<const h8v*>(sl + i * 4096 + foa[2 + kc]);
             }
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 bh[kc][j] = *reinterpret_cast<const h8v*>(sl + j * 4096 + fob[kc]);
-                bl[kc][j] = *reinterpret_cast<const h8v*>(sl + j * 4096 + fob[2 + kc]);
+                if constexpr (!X1) bl[kc][j] = *reinterpret_cast<const h8v*>(sl + j * 4096 + fob[2 + kc]);
             }
         }
 #pragma unroll
@@ -676,8 +689,10 @@ __global__ __launch_bounds__(64 * (WM * WN + NL)) void conv_sh_kernel(ShConvArgs
                 for (int j = 0; j < TN; ++j) {
                     if (!OMNI_ABL(64) && !OMNI_DBG(a, 64)) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[kc][j], ah[kc][i], acc[i][j], 0, 0, 0);
                     else { acc[i][j][0] += (float)bh[kc][j][0] * (float)ah[kc][i][0]; }
-                    if (!OMNI_ABL(16) && !OMNI_DBG(a, 16)) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[kc][j], ah[kc][i], acc1[i][j], 0, 0, 0);   // precision map: weight-lo term
-                    if (!OMNI_ABL(32) && !OMNI_DBG(a, 32)) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[kc][j], al[kc][i], acc1[i][j], 0, 0, 0);   // ... activation-lo term
+                    if constexpr (!X1) {
+                        if (!OMNI_ABL(16) && !OMNI_DBG(a, 16)) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[kc][j], ah[kc][i], acc1[i][j], 0, 0, 0);   // precision map: weight-lo term
+                        if (!OMNI_ABL(32) && !OMNI_DBG(a, 32)) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[kc][j], al[kc][i], acc1[i][j], 0, 0, 0);   // ... activation-lo term
+                    }
                 }
             if (kc == 0) {                                       // stage ks+NST-1, issued under the first half's matrix work
                 __builtin_amdgcn_sched_barrier(0);
@@ -710,7 +725,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NL)) void conv_sh_kernel(ShConvArgs
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             const int r0 = row0 + wm * (BM / WM) + i * 32;
-            if (r0 < a.rows) epilogue_tile_lds<TN, false>(acc[i], acc1[i], a, (size_t)r0, min(32, a.rows - r0), c0, lane, tile);
+            if (r0 < a.rows) epilogue_tile_lds<TN, false, X1>(acc[i], acc1[i], a, (size_t)r0, min(32, a.rows - r0), c0, lane, tile);
             if (i + 1 < TM) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // (the tile is read back before it is written again)
         }
         if (OMNI_ABL(32768)) { if (wave == 0) cstamp(2); __syncthreads(); cdump(); }
@@ -728,7 +743,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NL)) void conv_sh_kernel(ShConvArgs
                     const int c = col0 + wn * (BN / WN) + j * 32 + 8 * q + 4 * (lane >> 5);
                     f4v v;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaf(acc1[i][j][4 * q + e], 4.8828125e-4f, acc[i][j][4 * q + e]);
+                    for (int e = 0; e < 4; ++e) v[e] = acc_join<X1>(acc1[i][j][4 * q + e], acc[i][j][4 * q + e]);
                     *reinterpret_cast<f4v*>(a.ws + ((size_t)blockIdx.y * a.rows + r) * a.Cout + c) = v;
                 }
         } else {
@@ -738,13 +753,13 @@ __global__ __launch_bounds__(64 * (WM * WN + NL)) void conv_sh_kernel(ShConvArgs
                 for (int j = 0; j < TN; ++j) {
                     const f16v ea[1] = {acc[i][j]}, eb[1] = {acc1[i][j]};
                     const int cj[1] = {col0 + wn * (BN / WN) + j * 32};
-                    epilogue_row<1, 2>(ea, eb, a, (size_t)r, cj, lane, a.dst_sh != 0);
+                    epilogue_row<1, 2, X1>(ea, eb, a, (size_t)r, cj, lane, a.dst_sh != 0);
                 }
             } else {
                 int c0[TN];
 #pragma unroll
                 for (int j = 0; j < TN; ++j) c0[j] = col0 + wn * (BN / WN) + j * 32;
-                epilogue_row<TN>(acc[i], acc1[i], a, (size_t)r, c0, lane, a.dst_sh != 0);
+                epilogue_row<TN, 4, X1>(acc[i], acc1[i], a, (size_t)r, c0, lane, a.dst_sh != 0);
             }
         }
     }
@@ -775,7 +790,7 @@ constexpr int HT_W = 32, HPW = HT_W + 2;
 // conv_sh_kernel's im2col tiles (every pixel group fetched once per tap) a K-step brings the weights only: 0.6x the LDS-DMA pieces per
 // matrix instruction at 128 x 128, which is what bounds those layers (tools/convabl.sh: the operand traffic of a layer3 convolution costs
 // as much time as its matrix instructions and overlaps them for a third).  Needs H == W == IW and rows % (TH*32) == 0.
-template <int BN, int TH, bool UP2 = false, int IW = 0>
+template <int BN, int TH, bool UP2 = false, int IW = 0, bool X1 = false>      // X1: f16x1 (acc_join)
 __global__ __launch_bounds__(64 * TH, (TH == 8 && BN == 32) ? 4 : 1) void conv3x3_halo_sh_kernel(ShConvArgs a)      // (8 rows x 32 channels: 128 registers, two 8-wave blocks per CU)
 {
     static_assert(!UP2 || (TH == 4 && IW == 0), "the cell decomposition of the up-sampling halo is written for 4-row tiles of wide images");
@@ -961,15 +976,19 @@ __global__ __launch_bounds__(64 * TH, (TH == 8 && BN == 32) ? 4 : 1) void conv3x
 #pragma unroll
                 for (int kc = 0; kc < 2; ++kc) {
                     const h8v ah = OMNI_ABL(512) ? (h8v)((_Float16)1.0f) : *reinterpret_cast<const h8v*>(lds + (a0 ^ (kc * 32)));
-                    const h8v al = OMNI_ABL(512) ? (h8v)((_Float16)1.0f) : *reinterpret_cast<const h8v*>(lds + (a0 ^ (64 + kc * 32)));
+                    h8v al;
+                    if constexpr (!X1) al = OMNI_ABL(512) ? (h8v)((_Float16)1.0f) : *reinterpret_cast<const h8v*>(lds + (a0 ^ (64 + kc * 32)));
 #pragma unroll
                     for (int j = 0; j < TN; ++j) {
                         const unsigned char* bp = sB + (kx * BN + j * 32) * 128;
                         const h8v bh = OMNI_ABL(512) ? (h8v)((_Float16)1.0f) : *reinterpret_cast<const h8v*>(bp + fo[kc]);
-                        const h8v bl = OMNI_ABL(512) ? (h8v)((_Float16)1.0f) : *reinterpret_cast<const h8v*>(bp + fo[2 + kc]);
+                        h8v bl;
+                        if constexpr (!X1) bl = OMNI_ABL(512) ? (h8v)((_Float16)1.0f) : *reinterpret_cast<const h8v*>(bp + fo[2 + kc]);
                         if (!OMNI_ABL(64)) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, ah, acc[j], 0, 0, 0);
-                        if (!OMNI_ABL(16) && !OMNI_DBG(a, 16)) acc1[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl, ah, acc1[j], 0, 0, 0);
-                        if (!OMNI_ABL(32) && !OMNI_DBG(a, 32)) acc1[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, al, acc1[j], 0, 0, 0);
+                        if constexpr (!X1) {
+                            if (!OMNI_ABL(16) && !OMNI_DBG(a, 16)) acc1[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl, ah, acc1[j], 0, 0, 0);
+                            if (!OMNI_ABL(32) && !OMNI_DBG(a, 32)) acc1[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, al, acc1[j], 0, 0, 0);
+                        }
                     }
                 }
             }
@@ -994,14 +1013,14 @@ __global__ __launch_bounds__(64 * TH, (TH == 8 && BN == 32) ? 4 : 1) void conv3x
         wait_lds_reads();
         __syncthreads();                                          // every wave is done with the halo and the weights
         hstamp(2);
-        epilogue_tile_lds<TN>(acc, acc1, a, (size_t)(r - (lane & 31)), 32, c0, lane, reinterpret_cast<float*>(lds) + wave * (32 * (32 * TN + 4)));
+        epilogue_tile_lds<TN, true, X1>(acc, acc1, a, (size_t)(r - (lane & 31)), 32, c0, lane, reinterpret_cast<float*>(lds) + wave * (32 * (32 * TN + 4)));
         hstamp(62);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         hstamp(3); hdump();
         return;
     }
     hstamp(2);
-    epilogue_row<TN>(acc, acc1, a, (size_t)r, c0, lane, a.dst_sh != 0);
+    epilogue_row<TN, 4, X1>(acc, acc1, a, (size_t)r, c0, lane, a.dst_sh != 0);
     hstamp(3); hdump();
 }
 
@@ -1029,7 +1048,7 @@ __global__ __launch_bounds__(64 * TH, (TH == 8 && BN == 32) ? 4 : 1) void conv3x
 constexpr int HR_PITCH = 36;                                 // floats per (tile row, (dy, head)) record of `hr`: 32 sums, pixel -1, pixel 32, 2 of padding (16-byte rows)
 struct HeadsArgs { const void* w16; float* hr; };           // w16: the heads' weights in fragment order (Engine: heads.w16f), [hi kc0, hi kc1, lo kc0, lo kc1][64 lanes] x 16 B
 
-template <bool HEADS>
+template <bool HEADS, bool X1 = false>                       // X1: f16x1 for the convolution (acc_join); the heads' own products stay f16x3
 __global__ __launch_bounds__(HEADS ? 64 * (4 + OMNI_G1_PW) : 512) void conv3x3_up2_g1_kernel(ShConvArgs a, int ntiles, HeadsArgs hd)
 {
     constexpr int BN = 32, TH = 4, NW = 4, RPP = 8 * NW;
@@ -1104,7 +1123,7 @@ __global__ __launch_bounds__(HEADS ? 64 * (4 + OMNI_G1_PW) : 512) void conv3x3_u
                 const int a0 = ao[tap];
                 const unsigned char* bp = lds + W_OFF + (tap / 3) * B_BYTES + ((tap % 3) * BN) * 128;
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
+                for (int k = 0; k < (X1 ? 2 : 4); ++k) {                   // (f16x1: the hi pieces only)
                     if (OMNI_ABL(512)) { fa[bf][k] = (h8v)((_Float16)(float)(a0 & 3)); fb[bf][k] = (h8v)((_Float16)(float)(fo[k] & 3)); continue; }   // (ablation: no fragment reads)
                     fa[bf][k] = *reinterpret_cast<const h8v*>(ha + (a0 ^ (k * 32)));
                     fb[bf][k] = *reinterpret_cast<const h8v*>(bp + fo[k]);
@@ -1119,7 +1138,7 @@ __global__ __launch_bounds__(HEADS ? 64 * (4 + OMNI_G1_PW) : 512) void conv3x3_u
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int kc = 0; kc < 2; ++kc) {
-                    if (OMNI_ABL(8192)) {                         // (ablation: four accumulators instead of two — another summation order)
+                    if (!X1 && OMNI_ABL(8192)) {                  // (ablation: four accumulators instead of two — another summation order)
                         if (kc == 0) { acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fb[bf][kc], fa[bf][kc], acc, 0, 0, 0);
                                        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(fb[bf][2 + kc], fa[bf][kc], acc1, 0, 0, 0);
                                        accx = __builtin_amdgcn_mfma_f32_32x32x16_f16(fb[bf][kc], fa[bf][2 + kc], accx, 0, 0, 0); }
@@ -1130,8 +1149,10 @@ __global__ __launch_bounds__(HEADS ? 64 * (4 + OMNI_G1_PW) : 512) void conv3x3_u
                     }
                     if (!OMNI_ABL(64)) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(fb[bf][kc], fa[bf][kc], acc, 0, 0, 0);
                     else acc[0] += (float)fb[bf][kc][0] * (float)fa[bf][kc][0] + (float)fb[bf][2 + kc][0] * (float)fa[bf][2 + kc][0];
-                    if (!OMNI_ABL(16)) acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(fb[bf][2 + kc], fa[bf][kc], acc1, 0, 0, 0);
-                    if (!OMNI_ABL(32)) acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(fb[bf][kc], fa[bf][2 + kc], acc1, 0, 0, 0);
+                    if constexpr (!X1) {
+                        if (!OMNI_ABL(16)) acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(fb[bf][2 + kc], fa[bf][kc], acc1, 0, 0, 0);
+                        if (!OMNI_ABL(32)) acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(fb[bf][kc], fa[bf][2 + kc], acc1, 0, 0, 0);
+                    }
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -1144,7 +1165,7 @@ __global__ __launch_bounds__(HEADS ? 64 * (4 + OMNI_G1_PW) : 512) void conv3x3_u
                 for (int q = 0; q < 4; ++q) {
                     f4v v;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaf(acc1[4 * q + e], 4.8828125e-4f, acc[4 * q + e]);
+                    for (int e = 0; e < 4; ++e) v[e] = acc_join<X1>(acc1[4 * q + e], acc[4 * q + e]);
                     v += bq[q];
                     if (a.act == OMNI_ACT_RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
                     h4v hi, lo; sh_split4(v, hi, lo);            // (the split every SH epilogue does: range guard included)
@@ -1184,7 +1205,7 @@ __global__ __launch_bounds__(HEADS ? 64 * (4 + OMNI_G1_PW) : 512) void conv3x3_u
                 for (int q = 0; q < 4; ++q) {
                     f4v v;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaf(acc1[4 * q + e], 4.8828125e-4f, acc[4 * q + e]);
+                    for (int e = 0; e < 4; ++e) v[e] = acc_join<X1>(acc1[4 * q + e], acc[4 * q + e]);
                     v += bq[q];
                     if (a.act == OMNI_ACT_RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
                     else if (a.act == OMNI_ACT_GELU) {
@@ -1304,6 +1325,7 @@ __global__ __launch_bounds__(HEADS ? 64 * (4 + OMNI_G1_PW) : 512) void conv3x3_u
 // Output: SH [M, Po, Po, 64].
 constexpr int SM_TH = 8, SM_TW = 16, SM_IH = 2 * SM_TH + 5, SM_IW = 2 * SM_TW + 5, SM_IP = 40, SM_G = 6;
 
+template <bool X1 = false>                                         // X1: f16x1 (acc_join)
 __global__ __launch_bounds__(256) void stem_f16x3_kernel(const float* __restrict__ src, const void* __restrict__ wt16,
                                                          const float* __restrict__ bias, void* __restrict__ dst, int M, int P, int Po, int epi_lds)
 {
@@ -1385,17 +1407,21 @@ __global__ __launch_bounds__(256) void stem_f16x3_kernel(const float* __restrict
                 h8v ah, al;
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    const h2v xh = *reinterpret_cast<const h2v*>(imh + ro + 2 * u), xl = *reinterpret_cast<const h2v*>(iml + ro + 2 * u);
-                    ah[2 * u] = xh[0]; ah[2 * u + 1] = xh[1]; al[2 * u] = xl[0]; al[2 * u + 1] = xl[1];
+                    const h2v xh = *reinterpret_cast<const h2v*>(imh + ro + 2 * u);
+                    ah[2 * u] = xh[0]; ah[2 * u + 1] = xh[1];
+                    if constexpr (!X1) { const h2v xl = *reinterpret_cast<const h2v*>(iml + ro + 2 * u); al[2 * u] = xl[0]; al[2 * u + 1] = xl[1]; }
                 }
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const unsigned char* bp = wl + g * 8192 + j * 4096;
                     const h8v bh = *reinterpret_cast<const h8v*>(bp + fo[kc]);
-                    const h8v bl = *reinterpret_cast<const h8v*>(bp + fo[2 + kc]);
+                    h8v bl;
+                    if constexpr (!X1) bl = *reinterpret_cast<const h8v*>(bp + fo[2 + kc]);
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, ah, acc[j], 0, 0, 0);
-                    acc1[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl, ah, acc1[j], 0, 0, 0);
-                    acc1[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, al, acc1[j], 0, 0, 0);
+                    if constexpr (!X1) {
+                        acc1[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl, ah, acc1[j], 0, 0, 0);
+                        acc1[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, al, acc1[j], 0, 0, 0);
+                    }
                 }
             }
         const size_t r = ((size_t)m * Po + oy0 + py) * Po + ox0 + px;
@@ -1406,10 +1432,10 @@ __global__ __launch_bounds__(256) void stem_f16x3_kernel(const float* __restrict
             for (int j = 0; j < 2; ++j) {
                 const f16v ea[1] = {acc[j]}, eb[1] = {acc1[j]};
                 const int cj[1] = {32 * j};
-                epilogue_tile_lds<1>(ea, eb, e, ra, 32, cj, lane, etile[wave], ra + Po);
+                epilogue_tile_lds<1, true, X1>(ea, eb, e, ra, 32, cj, lane, etile[wave], ra + Po);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             }
-        } else epilogue_row<2>(acc, acc1, e, r, c0, lane, true);
+        } else epilogue_row<2, 4, X1>(acc, acc1, e, r, c0, lane, true);
     }
 }
 
@@ -1421,6 +1447,7 @@ __global__ __launch_bounds__(256) void stem_f16x3_kernel(const float* __restrict
 // With ONE consumer per SIMD a tile cost its K loop (2.8 us: 144 LDS reads whose latency nothing hid) PLUS its epilogue (2.7 us) — 95 us for 144
 // patches with the matrix instructions themselves worth 12 (profiles/r05g_stem_ablations.txt); two consumers per SIMD run one's epilogue under the
 // other's K loop.  The A fragments are read twice (LDS traffic per tile 2.3 -> 3.1 k cycles); every output element is the same sum as before.
+template <bool X1 = false>                                         // X1: f16x1 (acc_join)
 __global__ __launch_bounds__(768) void stem_f16x3_pc_kernel(const float* __restrict__ src, const void* __restrict__ wt16,
                                                          const float* __restrict__ bias, void* __restrict__ dst, int M, int P, int Po, int epi_lds, int tpb)
 {
@@ -1550,15 +1577,19 @@ __global__ __launch_bounds__(768) void stem_f16x3_pc_kernel(const float* __restr
                 h8v ah, al;
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    const h2v xh = *reinterpret_cast<const h2v*>(ih + ro + 2 * u), xl = *reinterpret_cast<const h2v*>(il + ro + 2 * u);
-                    ah[2 * u] = xh[0]; ah[2 * u + 1] = xh[1]; al[2 * u] = xl[0]; al[2 * u + 1] = xl[1];
+                    const h2v xh = *reinterpret_cast<const h2v*>(ih + ro + 2 * u);
+                    ah[2 * u] = xh[0]; ah[2 * u + 1] = xh[1];
+                    if constexpr (!X1) { const h2v xl = *reinterpret_cast<const h2v*>(il + ro + 2 * u); al[2 * u] = xl[0]; al[2 * u + 1] = xl[1]; }
                 }
                 const unsigned char* bp = wl + g * 8192 + cj * 4096;
                 const h8v bh = *reinterpret_cast<const h8v*>(bp + fo[kc]);
-                const h8v bl = *reinterpret_cast<const h8v*>(bp + fo[2 + kc]);
+                h8v bl;
+                if constexpr (!X1) bl = *reinterpret_cast<const h8v*>(bp + fo[2 + kc]);
                 acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, ah, acc[0], 0, 0, 0);
-                acc1[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl, ah, acc1[0], 0, 0, 0);
-                acc1[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, al, acc1[0], 0, 0, 0);
+                if constexpr (!X1) {
+                    acc1[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl, ah, acc1[0], 0, 0, 0);
+                    acc1[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, al, acc1[0], 0, 0, 0);
+                }
             }
     };
     auto epi = [&](int T, const f16v (&acc)[1], const f16v (&acc1)[1]) {
@@ -1567,9 +1598,9 @@ __global__ __launch_bounds__(768) void stem_f16x3_pc_kernel(const float* __restr
         const int c0[1] = {32 * cj};
         if (e.epi_lds) {                                          // 151 MB of output at 8 panoramas: as 16-byte pieces (the wave's two rows of 16 pixels)
             const size_t ra = ((size_t)m * Po + oy0 + 2 * pr) * Po + ox0;
-            epilogue_tile_lds<1>(acc, acc1, e, ra, 32, c0, lane, etile[wave], ra + Po);
+            epilogue_tile_lds<1, true, X1>(acc, acc1, e, ra, 32, c0, lane, etile[wave], ra + Po);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        } else epilogue_row<1>(acc, acc1, e, ((size_t)m * Po + oy0 + py) * Po + ox0 + px, c0, lane, true);
+        } else epilogue_row<1, 4, X1>(acc, acc1, e, ((size_t)m * Po + oy0 + py) * Po + ox0 + px, c0, lane, true);
     };
     f16v acc[1], acc1[1];
     int b = 0;
@@ -1910,17 +1941,17 @@ __global__ __launch_bounds__(256) void wino_input_sh_kernel(const void* __restri
     }
 }
 
-template <int BM, int BN, int WM, int WN, int NST = 3, int NL = 0>
+template <bool X1, int BM, int BN, int WM, int WN, int NST = 3, int NL = 0>
 void launch_sh(ShConvArgs a, hipStream_t s)
 {
     const int tiles = ((a.rows + BM - 1) / BM) * (a.Cout / BN);
     if constexpr (NL > 0 && WM * WN == 8) {
         if (omni_options().conv_pingpong) {                       // the SIMD's two matrix waves in anti-phase (same bits)
-            hipLaunchKernelGGL((conv_sh_kernel<BM, BN, WM, WN, NST, NL, true>), dim3(tiles, a.splitk > 1 ? a.splitk : 1), dim3(64 * (WM * WN + NL)), 0, s, a);
+            hipLaunchKernelGGL((conv_sh_kernel<BM, BN, WM, WN, NST, NL, true, false, X1>), dim3(tiles, a.splitk > 1 ? a.splitk : 1), dim3(64 * (WM * WN + NL)), 0, s, a);
             return;
         }
     }
-    hipLaunchKernelGGL((conv_sh_kernel<BM, BN, WM, WN, NST, NL>), dim3(tiles, a.splitk > 1 ? a.splitk : 1), dim3(64 * (WM * WN + NL)), 0, s, a);
+    hipLaunchKernelGGL((conv_sh_kernel<BM, BN, WM, WN, NST, NL, false, false, X1>), dim3(tiles, a.splitk > 1 ? a.splitk : 1), dim3(64 * (WM * WN + NL)), 0, s, a);
 }
 
 }  // namespace
@@ -1960,6 +1991,7 @@ extern "C" int omni_gemm_sh_f16x3_ln512_ws(const void* x, const void* wt16, cons
 {
     if (!x || !wt16 || !tok || !ln_g || !ln_b || !y) OMNI_FAIL(OMNI_ERR_INVALID, "omni_gemm_sh_f16x3_ln512: null pointer");
     if (rows <= 0 || K <= 0 || K % 32) OMNI_FAIL(OMNI_ERR_INVALID, "omni_gemm_sh_f16x3_ln512: bad shape");
+    if (fmt & 8) OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_gemm_sh_f16x3_ln512: no f16x1 form (fmt bit 3)");
     const int S = std::min(splitk, K / 32);
     if (S < 2) OMNI_FAIL(OMNI_ERR_INVALID, "omni_gemm_sh_f16x3_ln512: needs a split-K plan (splitk >= 2); an unsplit GEMM writes its result in its own epilogue");
     const int rc = conv2d_sh_impl(x, nullptr, wt16, bias, res, tok, 2, rows, 1, 1, K, 0, 512, 1, 1, 1, 0, OMNI_ACT_NONE, S, ws, ws_bytes, nullptr, 0, stream, false);
@@ -1971,6 +2003,78 @@ extern "C" int omni_gemm_sh_f16x3_ln512_ws(const void* x, const void* wt16, cons
     return OMNI_OK;
 }
 extern "C" int omni_conv2d_splitk_plan(long long rows, int Cout, int ksteps);            // omni_conv.hip: the two-launch plan
+
+// The kernel choice of conv2d_sh_impl (everything but the checks and the split-K second pass), once per arithmetic mode: X1 (fmt bit 3) picks the
+// f16x1 instantiation of whichever form the shape and the tuning options select — the same forms, the same block counts.
+template <bool X1>
+static void conv_sh_select(const ShConvArgs& a, int fmt, hipStream_t s)
+{
+    const int KH = a.KH, KW = a.KW, stride = a.stride, pad = a.pad, H = a.H, W = a.W, M = a.M, Cout = a.Cout;
+    const int ksteps = KH * KW * ((a.C1 + a.C2) / 32);
+    const long long rows = a.rows;
+    // small square images: the halo kernel over bands of whole image rows (IW > 0) — 16 x 16 (layer2, de_conv1_x: 61.6 -> 49.3 us per layer2
+    // convolution at 8 panoramas) by default, 8 x 8 as well with conv_img = 2 (layer3: 52.7 -> 50.9)
+    // (the choice must not depend on the number of images: a panorama's bits are the same in every batch size; a caller that runs ONE panorama,
+    //  where the launch would be a quarter block per CU, asks for the tile kernel with fmt bit 2)
+    if (a.splitk <= 1 && KH == 3 && KW == 3 && stride == 1 && pad == 1 && H == W && (W == 16 || (W == 8 && omni_options().conv_img >= 2)) && rows % 128 == 0 &&
+        Cout % 64 == 0 && !(fmt & 4) && omni_options().conv_img > 0 && !omni_options().conv_nohalo) {
+        const int grid = (int)(rows / 128) * (Cout / 64);
+        if (omni_options().conv_halo_bn == 32) {
+            if (W == 16) hipLaunchKernelGGL((conv3x3_halo_sh_kernel<32, 4, false, 16, X1>), dim3(2 * grid), dim3(256), 0, s, a);
+            else         hipLaunchKernelGGL((conv3x3_halo_sh_kernel<32, 4, false, 8, X1>), dim3(2 * grid), dim3(256), 0, s, a);
+        }
+        else if (W == 16) hipLaunchKernelGGL((conv3x3_halo_sh_kernel<64, 4, false, 16, X1>), dim3(grid), dim3(256), 0, s, a);
+        else         hipLaunchKernelGGL((conv3x3_halo_sh_kernel<64, 4, false, 8, X1>), dim3(grid), dim3(256), 0, s, a);
+        return;
+    }
+    if (a.splitk <= 1 && KH == 3 && KW == 3 && stride == 1 && pad == 1 && W % HT_W == 0 && H % 4 == 0 && !omni_options().conv_nohalo) {
+        const int th = (H % 8 == 0 && omni_options().conv_halo_th == 8) ? 8 : 4;
+        const int grid = M * (H / th) * (W / HT_W);
+        if (th == 8) {
+            if (Cout % 64 == 0 && omni_options().conv_halo_bn != 32) hipLaunchKernelGGL((conv3x3_halo_sh_kernel<64, 8, false, 0, X1>), dim3(grid * (Cout / 64)), dim3(512), 0, s, a);
+            else                hipLaunchKernelGGL((conv3x3_halo_sh_kernel<32, 8, false, 0, X1>), dim3(grid * (Cout / 32)), dim3(512), 0, s, a);
+        } else {
+            // (fmt bit 2, ONE panorama: the launch is a fraction of a block per CU and costs the length of a block's life — 32-channel blocks are twice as many and
+            //  half as long; option conv_halo_bn_lat)
+            const bool bn32 = omni_options().conv_halo_bn == 32 || ((fmt & 4) && omni_options().conv_halo_bn_lat == 32);
+            if (Cout % 64 == 0 && !bn32) hipLaunchKernelGGL((conv3x3_halo_sh_kernel<64, 4, false, 0, X1>), dim3(grid * (Cout / 64)), dim3(256), 0, s, a);
+            else                hipLaunchKernelGGL((conv3x3_halo_sh_kernel<32, 4, false, 0, X1>), dim3(grid * (Cout / 32)), dim3(256), 0, s, a);
+        }
+        return;
+    }
+    // tile: results do not depend on it (every output element is the same k-ordered chain), so it is a pure tuning choice
+    // -1 auto (= 8): the largest 8-wave tile the layer allows (256x128, 128x128, else 128x64: 3/8, 1/2, 3/4 of the L2 -> LDS bytes per MFMA
+    // of a 64x64 tile) wherever the launch still has >= 128 blocks, 64x64 below that.  Measured interleaved in one process
+    // (tools/pipe_ab.py, tools/plain_ab.py): +5.1 % panoramas/s with three forwards in flight (+1.2 % of it from 256x128), +1.7 % for plain
+    // calls at 8 panoramas, -1 % at 4, 0 at 1.
+    // 0: 64x64 everywhere; 1: 128x64 (4 waves); 2: 128x128 (4 waves); 3 / 4: the 8-wave forms everywhere; 5..7: auto without 256x128, with 64 / 128 / 256 blocks
+    int tile = omni_options().conv_sh_tile;
+    if (tile < 0) tile = 8;
+    if (Cout % 64 != 0) launch_sh<X1, 128, 32, 4, 1>(a, s);
+    else if (tile == 2 && Cout % 128 == 0) launch_sh<X1, 128, 128, 2, 2>(a, s);
+    else if (tile == 1) launch_sh<X1, 128, 64, 2, 2>(a, s);
+    else if (tile == 3) launch_sh<X1, 128, 64, 4, 2>(a, s);            // 8 waves
+    else if (tile == 4 && Cout % 128 == 0) launch_sh<X1, 128, 128, 4, 2>(a, s);
+    else if (tile == 8 && Cout % 128 == 0 && ((rows + 255) / 256) * (long long)(Cout / 128) * a.splitk >= std::max(1, omni_options().conv_big_blocks)) launch_sh<X1, 256, 128, 4, 2>(a, s);   // each wave a 64x64 tile: 0.67 KB of LDS reads per MFMA instead of 1
+    // (128x128 and 128x64 with four LOADER waves beside the eight matrix waves: layer3 51.3 -> 45.8 us, de_conv0_0 90 -> 79, layer4 43.3 -> 41.3, same bits;
+    //  tile = 9: without them.  256x128 has no registers to spare for a third wave per SIMD.)
+    else if (tile == 8 && Cout % 128 == 0 && ((rows + 127) / 128) * (long long)(Cout / 128) * a.splitk >= 128) launch_sh<X1, 128, 128, 4, 2, 3, 4>(a, s);
+    else if (tile == 8 && ((rows + 127) / 128) * (long long)(Cout / 64) * a.splitk >= 128) launch_sh<X1, 128, 64, 4, 2, 3, 4>(a, s);
+    else if (tile == 9 && Cout % 128 == 0 && ((rows + 255) / 256) * (long long)(Cout / 128) * a.splitk >= 128) launch_sh<X1, 256, 128, 4, 2>(a, s);
+    else if (tile == 9 && Cout % 128 == 0 && ((rows + 127) / 128) * (long long)(Cout / 128) * a.splitk >= 128) launch_sh<X1, 128, 128, 4, 2>(a, s);
+    else if (tile == 9 && ((rows + 127) / 128) * (long long)(Cout / 64) * a.splitk >= 128) launch_sh<X1, 128, 64, 4, 2>(a, s);
+    else if (tile >= 5 && tile <= 7 && Cout % 128 == 0 && ((rows + 127) / 128) * (long long)(Cout / 128) * a.splitk >= (32ll << (tile - 4))) launch_sh<X1, 128, 128, 4, 2>(a, s);
+    else if (tile >= 5 && tile <= 7 && ((rows + 127) / 128) * (long long)(Cout / 64) * a.splitk >= (32ll << (tile - 4))) launch_sh<X1, 128, 64, 4, 2>(a, s);
+    // one round of at most one block per CU (the transformer GEMMs; every deep layer at batch 1): the K loop is pure latency,
+    // keep 5 stages in flight instead of 2 (96 KiB of LDS, which a single resident block can afford)
+    else if (((rows + 63) / 64) * (long long)(Cout / 64) * a.splitk <= 256 && ksteps >= 8 && !omni_options().conv_nodeep) {
+        // (conv_deep_loaders = 1: four loader waves beside the four matrix waves — at one block per CU a K-step is the four DMA pieces a matrix wave issues,
+        //  ~400 cycles for its 192 of matrix work)
+        if (omni_options().conv_deep_loaders) launch_sh<X1, 64, 64, 2, 2, 6, 4>(a, s);
+        else launch_sh<X1, 64, 64, 2, 2, 6>(a, s);
+    }
+    else launch_sh<X1, 64, 64, 2, 2>(a, s);
+}
 
 static int conv2d_sh_impl(const void* src1, const void* src2, const void* wt16, const float* bias,
                           const void* res, void* dst, int fmt, int M, int H, int W, int C1, int C2, int Cout,
@@ -2016,70 +2120,8 @@ static int conv2d_sh_impl(const void* src1, const void* src2, const void* wt16, 
         a.post_rows = (unsigned)(post_elems / (size_t)Cout);
     }
     hipStream_t s = (hipStream_t)stream;
-    // small square images: the halo kernel over bands of whole image rows (IW > 0) — 16 x 16 (layer2, de_conv1_x: 61.6 -> 49.3 us per layer2
-    // convolution at 8 panoramas) by default, 8 x 8 as well with conv_img = 2 (layer3: 52.7 -> 50.9)
-    // (the choice must not depend on the number of images: a panorama's bits are the same in every batch size; a caller that runs ONE panorama,
-    //  where the launch would be a quarter block per CU, asks for the tile kernel with fmt bit 2)
-    if (a.splitk <= 1 && KH == 3 && KW == 3 && stride == 1 && pad == 1 && H == W && (W == 16 || (W == 8 && omni_options().conv_img >= 2)) && rows % 128 == 0 &&
-        Cout % 64 == 0 && !(fmt & 4) && omni_options().conv_img > 0 && !omni_options().conv_nohalo) {
-        const int grid = (int)(rows / 128) * (Cout / 64);
-        if (omni_options().conv_halo_bn == 32) {
-            if (W == 16) hipLaunchKernelGGL((conv3x3_halo_sh_kernel<32, 4, false, 16>), dim3(2 * grid), dim3(256), 0, s, a);
-            else         hipLaunchKernelGGL((conv3x3_halo_sh_kernel<32, 4, false, 8>), dim3(2 * grid), dim3(256), 0, s, a);
-        }
-        else if (W == 16) hipLaunchKernelGGL((conv3x3_halo_sh_kernel<64, 4, false, 16>), dim3(grid), dim3(256), 0, s, a);
-        else         hipLaunchKernelGGL((conv3x3_halo_sh_kernel<64, 4, false, 8>), dim3(grid), dim3(256), 0, s, a);
-        OMNI_HIP(hipGetLastError());
-        return OMNI_OK;
-    }
-    if (a.splitk <= 1 && KH == 3 && KW == 3 && stride == 1 && pad == 1 && W % HT_W == 0 && H % 4 == 0 && !omni_options().conv_nohalo) {
-        const int th = (H % 8 == 0 && omni_options().conv_halo_th == 8) ? 8 : 4;
-        const int grid = M * (H / th) * (W / HT_W);
-        if (th == 8) {
-            if (Cout % 64 == 0 && omni_options().conv_halo_bn != 32) hipLaunchKernelGGL((conv3x3_halo_sh_kernel<64, 8>), dim3(grid * (Cout / 64)), dim3(512), 0, s, a);
-            else                hipLaunchKernelGGL((conv3x3_halo_sh_kernel<32, 8>), dim3(grid * (Cout / 32)), dim3(512), 0, s, a);
-        } else {
-            // (fmt bit 2, ONE panorama: the launch is a fraction of a block per CU and costs the length of a block's life — 32-channel blocks are twice as many and
-            //  half as long; option conv_halo_bn_lat)
-            const bool bn32 = omni_options().conv_halo_bn == 32 || ((fmt & 4) && omni_options().conv_halo_bn_lat == 32);
-            if (Cout % 64 == 0 && !bn32) hipLaunchKernelGGL((conv3x3_halo_sh_kernel<64, 4>), dim3(grid * (Cout / 64)), dim3(256), 0, s, a);
-            else                hipLaunchKernelGGL((conv3x3_halo_sh_kernel<32, 4>), dim3(grid * (Cout / 32)), dim3(256), 0, s, a);
-        }
-        OMNI_HIP(hipGetLastError());
-        return OMNI_OK;
-    }
-    // tile: results do not depend on it (every output element is the same k-ordered chain), so it is a pure tuning choice
-    // -1 auto (= 8): the largest 8-wave tile the layer allows (256x128, 128x128, else 128x64: 3/8, 1/2, 3/4 of the L2 -> LDS bytes per MFMA
-    // of a 64x64 tile) wherever the launch still has >= 128 blocks, 64x64 below that.  Measured interleaved in one process
-    // (tools/pipe_ab.py, tools/plain_ab.py): +5.1 % panoramas/s with three forwards in flight (+1.2 % of it from 256x128), +1.7 % for plain
-    // calls at 8 panoramas, -1 % at 4, 0 at 1.
-    // 0: 64x64 everywhere; 1: 128x64 (4 waves); 2: 128x128 (4 waves); 3 / 4: the 8-wave forms everywhere; 5..7: auto without 256x128, with 64 / 128 / 256 blocks
-    int tile = omni_options().conv_sh_tile;
-    if (tile < 0) tile = 8;
-    if (Cout % 64 != 0) launch_sh<128, 32, 4, 1>(a, s);
-    else if (tile == 2 && Cout % 128 == 0) launch_sh<128, 128, 2, 2>(a, s);
-    else if (tile == 1) launch_sh<128, 64, 2, 2>(a, s);
-    else if (tile == 3) launch_sh<128, 64, 4, 2>(a, s);            // 8 waves
-    else if (tile == 4 && Cout % 128 == 0) launch_sh<128, 128, 4, 2>(a, s);
-    else if (tile == 8 && Cout % 128 == 0 && ((rows + 255) / 256) * (long long)(Cout / 128) * a.splitk >= std::max(1, omni_options().conv_big_blocks)) launch_sh<256, 128, 4, 2>(a, s);   // each wave a 64x64 tile: 0.67 KB of LDS reads per MFMA instead of 1
-    // (128x128 and 128x64 with four LOADER waves beside the eight matrix waves: layer3 51.3 -> 45.8 us, de_conv0_0 90 -> 79, layer4 43.3 -> 41.3, same bits;
-    //  tile = 9: without them.  256x128 has no registers to spare for a third wave per SIMD.)
-    else if (tile == 8 && Cout % 128 == 0 && ((rows + 127) / 128) * (long long)(Cout / 128) * a.splitk >= 128) launch_sh<128, 128, 4, 2, 3, 4>(a, s);
-    else if (tile == 8 && ((rows + 127) / 128) * (long long)(Cout / 64) * a.splitk >= 128) launch_sh<128, 64, 4, 2, 3, 4>(a, s);
-    else if (tile == 9 && Cout % 128 == 0 && ((rows + 255) / 256) * (long long)(Cout / 128) * a.splitk >= 128) launch_sh<256, 128, 4, 2>(a, s);
-    else if (tile == 9 && Cout % 128 == 0 && ((rows + 127) / 128) * (long long)(Cout / 128) * a.splitk >= 128) launch_sh<128, 128, 4, 2>(a, s);
-    else if (tile == 9 && ((rows + 127) / 128) * (long long)(Cout / 64) * a.splitk >= 128) launch_sh<128, 64, 4, 2>(a, s);
-    else if (tile >= 5 && tile <= 7 && Cout % 128 == 0 && ((rows + 127) / 128) * (long long)(Cout / 128) * a.splitk >= (32ll << (tile - 4))) launch_sh<128, 128, 4, 2>(a, s);
-    else if (tile >= 5 && tile <= 7 && ((rows + 127) / 128) * (long long)(Cout / 64) * a.splitk >= (32ll << (tile - 4))) launch_sh<128, 64, 4, 2>(a, s);
-    // one round of at most one block per CU (the transformer GEMMs; every deep layer at batch 1): the K loop is pure latency,
-    // keep 5 stages in flight instead of 2 (96 KiB of LDS, which a single resident block can afford)
-    else if (((rows + 63) / 64) * (long long)(Cout / 64) * a.splitk <= 256 && ksteps >= 8 && !omni_options().conv_nodeep) {
-        // (conv_deep_loaders = 1: four loader waves beside the four matrix waves — at one block per CU a K-step is the four DMA pieces a matrix wave issues,
-        //  ~400 cycles for its 192 of matrix work)
-        if (omni_options().conv_deep_loaders) launch_sh<64, 64, 2, 2, 6, 4>(a, s);
-        else launch_sh<64, 64, 2, 2, 6>(a, s);
-    }
-    else launch_sh<64, 64, 2, 2>(a, s);
+    if (fmt & 8) conv_sh_select<true>(a, fmt, s);            // f16x1: every form below has its X1 instantiation
+    else         conv_sh_select<false>(a, fmt, s);
     OMNI_HIP(hipGetLastError());
     if (a.splitk > 1 && reduce) {
         const size_t n4 = (size_t)rows * Cout / 4;
@@ -2113,6 +2155,7 @@ extern "C" int omni_conv3x3_wino_sh_f16x3(const void* V, const void* wt16, const
     if (!V || !wt16 || !dst) OMNI_FAIL(OMNI_ERR_INVALID, "omni_conv3x3_wino_sh: null pointer");
     if (M <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || C <= 0 || C % 32 || Cout <= 0 || Cout % 64) OMNI_FAIL(OMNI_ERR_INVALID, "omni_conv3x3_wino_sh: even image sides, C % 32 == 0, Cout % 64 == 0");
     if (splitk != 1 && splitk != 2 && splitk != 4) OMNI_FAIL(OMNI_ERR_INVALID, "omni_conv3x3_wino_sh: splitk must be 1, 2 or 4 (it divides the sixteen positions)");
+    if (fmt & 8) OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_conv3x3_wino_sh: no f16x1 form (fmt bit 3)");
     const long long nt = (long long)M * (H / 2) * (W / 2), pix = (long long)M * H * W;
     if (16 * nt * C * 4 >= (1ll << 31) || (long long)Cout * 16 * C * 4 >= (1ll << 31) || pix >= (1ll << 31)) OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_conv3x3_wino_sh: an operand of 2 GiB or more");
     if (splitk > 1 && (!ws || ws_bytes < (size_t)splitk * pix * Cout * sizeof(float))) OMNI_FAIL(OMNI_ERR_INVALID, "omni_conv3x3_wino_sh: split workspace too small");
@@ -2157,15 +2200,21 @@ extern "C" int omni_conv3x3_up2_sh_f16x3(const void* src, const void* wt16, cons
     a.M = M; a.H = H; a.W = W; a.C1 = C; a.C2 = 0; a.Cout = Cout; a.KH = 3; a.KW = 3; a.stride = 1; a.pad = 1; a.act = act;
     a.Ho = H; a.Wo = W; a.rows = M * H * W; a.splitk = 1; a.ws = nullptr; a.post = nullptr; a.post_rows = 1; a.wino_th = a.wino_tw = a.wino_pix = 0;
     const int grid = M * (H / 4) * (W / HT_W);
+    const bool x1 = (fmt & 8) != 0;                                   // f16x1
     if (C == 32 && Cout == 32 && omni_options().conv_up2_persist) {    // de_conv4_0: resident weights, one persistent block of 8 waves per CU
-        hipLaunchKernelGGL(conv3x3_up2_g1_kernel<false>, dim3(grid < 256 ? (grid + 7) / 8 * 8 : 256), dim3(512), 0, (hipStream_t)stream, a, grid, HeadsArgs{nullptr, nullptr});
+        const dim3 g1(grid < 256 ? (grid + 7) / 8 * 8 : 256);
+        if (x1) hipLaunchKernelGGL((conv3x3_up2_g1_kernel<false, true>), g1, dim3(512), 0, (hipStream_t)stream, a, grid, HeadsArgs{nullptr, nullptr});
+        else    hipLaunchKernelGGL(conv3x3_up2_g1_kernel<false>, g1, dim3(512), 0, (hipStream_t)stream, a, grid, HeadsArgs{nullptr, nullptr});
         OMNI_HIP(hipGetLastError());
         return OMNI_OK;
     }
     // (the up-sampling halo is COMPUTED per block — ~700 vector instructions per 2 x 2 cell: blocks of 32 output channels would do it twice — 64 per block here whatever conv_halo_bn says:
     //  de_conv2_0 51 -> 64 us, de_conv3_0 180 -> 240 us with 32, profiles/r06e_halo_bn.txt)
-    if (Cout % 64 == 0 && !((fmt & 4) && omni_options().conv_halo_up2_bn_lat == 32)) hipLaunchKernelGGL((conv3x3_halo_sh_kernel<64, 4, true>), dim3(grid * (Cout / 64)), dim3(256), 0, (hipStream_t)stream, a);
-    else                hipLaunchKernelGGL((conv3x3_halo_sh_kernel<32, 4, true>), dim3(grid * (Cout / 32)), dim3(256), 0, (hipStream_t)stream, a);
+    const bool bn64 = Cout % 64 == 0 && !((fmt & 4) && omni_options().conv_halo_up2_bn_lat == 32);
+    if (bn64 && x1)  hipLaunchKernelGGL((conv3x3_halo_sh_kernel<64, 4, true, 0, true>), dim3(grid * (Cout / 64)), dim3(256), 0, (hipStream_t)stream, a);
+    else if (bn64)   hipLaunchKernelGGL((conv3x3_halo_sh_kernel<64, 4, true>), dim3(grid * (Cout / 64)), dim3(256), 0, (hipStream_t)stream, a);
+    else if (x1)     hipLaunchKernelGGL((conv3x3_halo_sh_kernel<32, 4, true, 0, true>), dim3(grid * (Cout / 32)), dim3(256), 0, (hipStream_t)stream, a);
+    else             hipLaunchKernelGGL((conv3x3_halo_sh_kernel<32, 4, true>), dim3(grid * (Cout / 32)), dim3(256), 0, (hipStream_t)stream, a);
     OMNI_HIP(hipGetLastError());
     return OMNI_OK;
 }
@@ -2180,8 +2229,9 @@ extern "C" size_t omni_up2_heads_scratch_bytes(int M, int P)
     if (M <= 0 || P <= 0 || P % 32) return 0;
     return (size_t)M * (P / 4) * (P / 32) * 4 * 6 * HR_PITCH * sizeof(float);
 }
-extern "C" int omni_conv3x3_up2_heads_sh_f16x3(const void* src, const void* wt16, const float* bias, const void* heads_w16f, float bias_pred, float bias_weight,
-                                               float* scratch, size_t scratch_bytes, float* out_a, float* out_c, int M, int P, int confidence, omni_stream_t stream)
+template <bool X1>
+static int up2_heads_impl(const void* src, const void* wt16, const float* bias, const void* heads_w16f, float bias_pred, float bias_weight,
+                          float* scratch, size_t scratch_bytes, float* out_a, float* out_c, int M, int P, int confidence, omni_stream_t stream)
 {
     if (!src || !wt16 || !heads_w16f || !scratch || !out_a) OMNI_FAIL(OMNI_ERR_INVALID, "omni_conv3x3_up2_heads_sh: null pointer");
     if (M <= 0 || P <= 0 || P % 32) OMNI_FAIL(OMNI_ERR_INVALID, "omni_conv3x3_up2_heads_sh: the patch size must be a multiple of 32");
@@ -2193,13 +2243,24 @@ extern "C" int omni_conv3x3_up2_heads_sh_f16x3(const void* src, const void* wt16
     a.M = M; a.H = P; a.W = P; a.C1 = 32; a.C2 = 0; a.Cout = 32; a.KH = 3; a.KW = 3; a.stride = 1; a.pad = 1; a.act = OMNI_ACT_RELU;
     a.Ho = P; a.Wo = P; a.rows = M * P * P; a.splitk = 1; a.ws = nullptr; a.post = nullptr; a.post_rows = 1; a.wino_th = a.wino_tw = a.wino_pix = 0;
     const int grid = M * (P / 4) * (P / HT_W);
-    hipLaunchKernelGGL(conv3x3_up2_g1_kernel<true>, dim3(grid < 256 ? (grid + 7) / 8 * 8 : 256), dim3(64 * (4 + OMNI_G1_PW)), 0, (hipStream_t)stream, a, grid, HeadsArgs{heads_w16f, scratch});
+    hipLaunchKernelGGL((conv3x3_up2_g1_kernel<true, X1>), dim3(grid < 256 ? (grid + 7) / 8 * 8 : 256), dim3(64 * (4 + OMNI_G1_PW)), 0, (hipStream_t)stream, a, grid, HeadsArgs{heads_w16f, scratch});
     OMNI_HIP(hipGetLastError());
     const size_t n = (size_t)M * P * P / 4;
     hipLaunchKernelGGL(heads_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)scratch, bias_pred, bias_weight,
                        out_a, out_c, M, P, confidence);
     OMNI_HIP(hipGetLastError());
     return OMNI_OK;
+}
+extern "C" int omni_conv3x3_up2_heads_sh_f16x3(const void* src, const void* wt16, const float* bias, const void* heads_w16f, float bias_pred, float bias_weight,
+                                               float* scratch, size_t scratch_bytes, float* out_a, float* out_c, int M, int P, int confidence, omni_stream_t stream)
+{
+    return up2_heads_impl<false>(src, wt16, bias, heads_w16f, bias_pred, bias_weight, scratch, scratch_bytes, out_a, out_c, M, P, confidence, stream);
+}
+// the same with de_conv4_0 in f16x1 (one matrix instruction per product block); the heads' own products stay f16x3
+extern "C" int omni_conv3x3_up2_heads_sh_f16x1(const void* src, const void* wt16, const float* bias, const void* heads_w16f, float bias_pred, float bias_weight,
+                                               float* scratch, size_t scratch_bytes, float* out_a, float* out_c, int M, int P, int confidence, omni_stream_t stream)
+{
+    return up2_heads_impl<true>(src, wt16, bias, heads_w16f, bias_pred, bias_weight, scratch, scratch_bytes, out_a, out_c, M, P, confidence, stream);
 }
 
 // The heads' weights w [2 heads][9 taps][32 channels] (fp32, host or device memory readable by the host — 2.3 KB, packed once per checkpoint) in the
@@ -2246,6 +2307,7 @@ extern "C" int omni_gemm_rows_sh_f16x3(const void* x, const void* wt16, const fl
     if (!x || !wt16 || !dst) OMNI_FAIL(OMNI_ERR_INVALID, "omni_gemm_rows_sh: null pointer");
     if (rows <= 0 || rows > 32 || N <= 0 || N % 32) OMNI_FAIL(OMNI_ERR_INVALID, "omni_gemm_rows_sh: 1..32 rows, N a multiple of 32");
     if (K != 512 && K != 2048) OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_gemm_rows_sh: K must be 512 or 2048");
+    if (fmt & 8) OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_gemm_rows_sh: no f16x1 form (fmt bit 3)");
     RowsGemmArgs a;
     a.x = x; a.wt = wt16; a.bias = bias; a.res = res; a.dst = dst; a.rows = rows; a.K = K; a.N = N; a.act = act; a.dst_sh = fmt & 1;
     a.parts = nullptr; a.nparts = 0; a.pbias = nullptr; a.pres = nullptr; a.xout = nullptr;
@@ -2262,6 +2324,7 @@ extern "C" int omni_gemm_rows_ln_sh_f16x3(const float* x, const float* lg, const
 {
     if (!x || !lg || !lb || !wt16 || !dst) OMNI_FAIL(OMNI_ERR_INVALID, "omni_gemm_rows_ln_sh: null pointer");
     if (rows <= 0 || rows > 32 || N <= 0 || N % 32) OMNI_FAIL(OMNI_ERR_INVALID, "omni_gemm_rows_ln_sh: 1..32 rows, N a multiple of 32");
+    if (fmt & 8) OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_gemm_rows_ln_sh: no f16x1 form (fmt bit 3)");
     RowsGemmArgs a;
     a.x = x; a.wt = wt16; a.bias = bias; a.res = res; a.dst = dst; a.rows = rows; a.K = 512; a.N = N; a.act = act; a.dst_sh = fmt & 1;
     a.parts = nullptr; a.nparts = 0; a.pbias = nullptr; a.pres = nullptr; a.xout = nullptr;
@@ -2322,7 +2385,8 @@ extern "C" int omni_splitk_reduce_ln512(const float* parts, int nparts, const fl
 // conv1 7x7 s2 p3 (3 -> 64) + bn1 + ReLU on the fp16 matrix cores.  src planar [M,3,P,P]; wt16: the folded filter bank as
 // [64][192] with k = (c*7 + ky)*8 + kx (kx = 7 and k >= 168: zeros), split like every other f16x3 weight matrix
 // ([64][6][hi32|lo32]); dst SH [M,P/2,P/2,64].
-extern "C" int omni_stem_sh_f16x3(const float* src, const void* wt16, const float* bias, void* dst, int M, int P, omni_stream_t stream)
+template <bool X1>
+static int stem_sh_impl(const float* src, const void* wt16, const float* bias, void* dst, int M, int P, omni_stream_t stream)
 {
     if (!src || !wt16 || !dst) OMNI_FAIL(OMNI_ERR_INVALID, "omni_stem: null pointer");
     if (P % 32 || M <= 0) OMNI_FAIL(OMNI_ERR_INVALID, "omni_stem_sh_f16x3: patch size must be a multiple of 32");
@@ -2335,11 +2399,20 @@ extern "C" int omni_stem_sh_f16x3(const float* src, const void* wt16, const floa
         int tpb = tps / split;
         const int ncu = omni_num_cus();
         if (split == 1 && ntiles > ncu * tps) tpb = (ntiles + ncu - 1) / ncu;
-        hipLaunchKernelGGL(stem_f16x3_pc_kernel, dim3((unsigned)((ntiles + tpb - 1) / tpb)), dim3(768), 0, (hipStream_t)stream, src, wt16, bias, dst, M, P, Po, omni_options().conv_epi_lds, tpb);
+        hipLaunchKernelGGL(stem_f16x3_pc_kernel<X1>, dim3((unsigned)((ntiles + tpb - 1) / tpb)), dim3(768), 0, (hipStream_t)stream, src, wt16, bias, dst, M, P, Po, omni_options().conv_epi_lds, tpb);
     }
-    else hipLaunchKernelGGL(stem_f16x3_kernel, dim3(strips, split), dim3(256), 0, (hipStream_t)stream, src, wt16, bias, dst, M, P, Po, omni_options().conv_epi_lds);
+    else hipLaunchKernelGGL(stem_f16x3_kernel<X1>, dim3(strips, split), dim3(256), 0, (hipStream_t)stream, src, wt16, bias, dst, M, P, Po, omni_options().conv_epi_lds);
     OMNI_HIP(hipGetLastError());
     return OMNI_OK;
+}
+extern "C" int omni_stem_sh_f16x3(const float* src, const void* wt16, const float* bias, void* dst, int M, int P, omni_stream_t stream)
+{
+    return stem_sh_impl<false>(src, wt16, bias, dst, M, P, stream);
+}
+// the same with one matrix instruction per product block (f16x1: input hi x weight hi)
+extern "C" int omni_stem_sh_f16x1(const float* src, const void* wt16, const float* bias, void* dst, int M, int P, omni_stream_t stream)
+{
+    return stem_sh_impl<true>(src, wt16, bias, dst, M, P, stream);
 }
 
 // layout conversions (n = number of elements, a multiple of 32 channels per pixel)

@@ -19,6 +19,7 @@ from ..equi_pers.pers2equi_v3 import pers2equi, pers2equi_conf
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 _LAYERS = [("layer1", 3, 1), ("layer2", 4, 2), ("layer3", 6, 2), ("layer4", 3, 2)]
 _BN_EPS = 1e-5
+PRECISIONS = ("f16x3", "f16x1", "fp32")
 
 
 def _p(t):
@@ -46,7 +47,7 @@ def strip_module_prefix(sd):
 
 
 class Engine:
-    def __init__(self, nrows, npatches, patch_size, fov, iterative):
+    def __init__(self, nrows, npatches, patch_size, fov, iterative, precision=None):
         self.nrows, self.npatches, self.iterative = nrows, npatches, iterative
         self.patch_size = pair(patch_size)
         self.fov = pair(fov)
@@ -55,20 +56,32 @@ class Engine:
         self.w = None          # packed weights (device tensors)
         self.device = None
         # "f16x3": conv products on the fp16 matrix cores with split operands (fp32-class accuracy, 3/16 of the MFMA time),
-        # activations between the convolutions in the split-half layout; "fp32": the exact fp32 MFMA, fp32 NHWC activations.
-        # OMNI_NET_PRECISION overrides.
-        import os
-        self.precision = os.environ.get("OMNI_NET_PRECISION", "f16x3")
+        # activations between the convolutions in the split-half layout; "f16x1": the same layout and weights, but every convolution
+        # of the encoder / decoder multiplies the hi halves only (one MFMA per product block, ~1e-3 relative; the transformer's
+        # GEMMs and the heads' own products stay f16x3); "fp32": the exact fp32 MFMA, fp32 NHWC activations.
+        # `precision` (the constructor's keyword) first, then OMNI_NET_PRECISION, then "f16x3".
+        self.precision = precision if precision is not None else os.environ.get("OMNI_NET_PRECISION", "f16x3")
 
     @property
     def sh(self):
-        return self.precision == "f16x3"
+        """activations between the convolutions are split-half (SH) tensors"""
+        return self.precision in ("f16x3", "f16x1")
+
+    @property
+    def terms(self):
+        """fp16 matrix instructions per product block of the convolutions: 3 (f16x3), 1 (f16x1); 0 for the exact fp32 path"""
+        return {"f16x3": 3, "f16x1": 1}.get(self.precision, 0)
+
+    @property
+    def _x1(self):
+        """fmt bit 3 of the SH convolution entry points: the f16x1 instantiation"""
+        return 8 if self.terms == 1 else 0
 
     def lane(self):
         """A second execution context over the SAME packed weights (own split-K workspace and per-call state): the model
         runs the two halves of a batch on two streams so that one half's kernel tails overlap the other half's work."""
-        e = Engine(self.nrows, self.npatches, self.patch_size, self.fov, self.iterative)
-        e.precision, e.w, e.device, e.head_bias = self.precision, self.w, self.device, getattr(self, "head_bias", None)
+        e = Engine(self.nrows, self.npatches, self.patch_size, self.fov, self.iterative, precision=self.precision)
+        e.w, e.device, e.head_bias = self.w, self.device, getattr(self, "head_bias", None)
         return e
 
     # ------------------------------------------------------------------ packing
@@ -183,12 +196,12 @@ class Engine:
             # whose plan splits K (few rows: small patches, nrows = 3, a lone panorama) adds it as a pass of its own instead
             late_post, post = post, None
         if self.sh and post is not None:                            # `+ post` after the activation, inside the epilogue (SH mode, never split)
-            rc = lib.omni_conv2d_sh_f16x3_post_ws(_p(x), _p(x2), _p(self.w[key + ".w16"]), b, _p(res), _p(out), 0 if out_f32 else 1,
+            rc = lib.omni_conv2d_sh_f16x3_post_ws(_p(x), _p(x2), _p(self.w[key + ".w16"]), b, _p(res), _p(out), (0 if out_f32 else 1) | self._x1,
                                                   M, H, Wd, C1, C2, Cout, k, k, stride, pad, act, S, _p(ws), ctypes.c_size_t(nb),
                                                   _p(post), ctypes.c_size_t(post.numel()), self._s)
         elif self.sh:
             lat = 4 if (self._bs == 1 and self.latency_plan) else 0     # fmt bit 2: a lone panorama keeps the im2col tiles for 16-wide images
-            rc = lib.omni_conv2d_sh_f16x3_ws(_p(x), _p(x2), _p(self.w[key + ".w16"]), b, _p(res), _p(out), (0 if out_f32 else 1) | lat,
+            rc = lib.omni_conv2d_sh_f16x3_ws(_p(x), _p(x2), _p(self.w[key + ".w16"]), b, _p(res), _p(out), (0 if out_f32 else 1) | lat | self._x1,
                                              M, H, Wd, C1, C2, Cout, k, k, stride, pad, act, S, _p(ws), ctypes.c_size_t(nb), self._s)
         else:
             rc = lib.omni_conv2d_nhwc_f32_ws(_p(x), _p(x2), _p(self.w[key + ".w"]), b, _p(res), _p(out), M, H, Wd, C1, C2, Cout,
@@ -342,7 +355,8 @@ class Engine:
         if self.sh and self.fuse_up and Wo % 32 == 0 and Ho % 4 == 0:
             if out is None:
                 out = torch.empty((M, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
-            _lib.check(_lib.load().omni_conv3x3_up2_sh_f16x3(_p(x), _p(self.w[key + ".w16"]), _p(self.w[key + ".b"]), _p(out), (0 if out_f32 else 1) | (4 if (self._bs == 1 and self.latency_plan) else 0),
+            _lib.check(_lib.load().omni_conv3x3_up2_sh_f16x3(_p(x), _p(self.w[key + ".w16"]), _p(self.w[key + ".b"]), _p(out),
+                                                             (0 if out_f32 else 1) | (4 if (self._bs == 1 and self.latency_plan) else 0) | self._x1,
                                                              M, H, Wd, C, Cout, act, self._s), "up+conv " + key)
             return out
         return self._conv(self._up(x, M, H, Wd, C, Ho, Wo), key, M, Ho, Wo, C, Cout, 3, 1, 1, act, out_f32=out_f32, out=out)
@@ -365,8 +379,10 @@ class Engine:
         pat = patches.view(M, 3, P, P)
         for m0, m1 in self._chunks(bs, N, self.front_chunk):        # stem -> maxpool per chunk: conv1 is re-read while still cached
             Mc = m1 - m0
+            if self.terms == 1 and P % 32:
+                raise ValueError(f"precision f16x1 needs a patch size that is a multiple of 32 (got {P})")
             if sh and P % 32 == 0:
-                _lib.check(lib.omni_stem_sh_f16x3(_p(pat[m0:m1]), _p(self.w["stem.w16"]), _p(self.w["stem.b"]), _p(conv1[m0:m1]), Mc, P, self._s), "stem")
+                _lib.check((lib.omni_stem_sh_f16x1 if self._x1 else lib.omni_stem_sh_f16x3)(_p(pat[m0:m1]), _p(self.w["stem.w16"]), _p(self.w["stem.b"]), _p(conv1[m0:m1]), Mc, P, self._s), "stem")
             else:
                 _lib.check((lib.omni_stem_sh if sh else lib.omni_stem_f32)(_p(pat[m0:m1]), _p(self.w["stem.w"]), _p(self.w["stem.b"]),
                                                                             _p(conv1[m0:m1]), Mc, P, self._s), "stem")
@@ -455,7 +471,7 @@ class Engine:
             if fused:                                                # de_conv4_0 + pred / weight_pred in one pass: its 302-MB output (8 panoramas) never exists
                 nb = int(lib.omni_up2_heads_scratch_bytes(Mc, P))
                 hs = new((nb + 3) // 4)
-                _lib.check(lib.omni_conv3x3_up2_heads_sh_f16x3(_p(x), _p(self.w["de_conv4_0.w16"]), _p(self.w["de_conv4_0.b"]), _p(self.w["heads.w16f"]),
+                _lib.check((lib.omni_conv3x3_up2_heads_sh_f16x1 if self._x1 else lib.omni_conv3x3_up2_heads_sh_f16x3)(_p(x), _p(self.w["de_conv4_0.w16"]), _p(self.w["de_conv4_0.b"]), _p(self.w["heads.w16f"]),
                                                                ctypes.c_float(self.head_bias[0]), ctypes.c_float(self.head_bias[1]), _p(hs), ctypes.c_size_t(nb),
                                                                _p(av[m0:m1]), _p(cv[m0:m1]) if cv is not None else None, Mc, P, 1 if confidence else 0, self._s), "up+conv+heads")
                 continue

@@ -29,7 +29,7 @@ import threading
 import torch
 from torch import nn
 
-from ._engine import Engine, strip_module_prefix
+from ._engine import Engine, PRECISIONS, strip_module_prefix
 from ..equi_pers.equi2pers_v3 import equi2pers_patches
 from .. import _lib
 from ..weights import schema
@@ -204,11 +204,15 @@ class spherical_fusion(nn.Module):
     # path (split-K is planned for a nominal batch, every output element is one k-ordered chain).  OMNI_LANES=1 disables.
     LANES = int(os.environ.get("OMNI_LANES", "2"))
 
-    def __init__(self, nrows=4, npatches=18, patch_size=(128, 128), fov=(80, 80)):
+    def __init__(self, nrows=4, npatches=18, patch_size=(128, 128), fov=(80, 80), *, precision=None):
+        """precision: "f16x3" (fp32-class), "f16x1" (one fp16 product per convolution block: faster, ~1e-3 relative per convolution,
+        see DESIGN.md 5) or "fp32"; None = OMNI_NET_PRECISION, else "f16x3".  Weights, state_dict and outputs keep their formats in every mode."""
         super().__init__()
+        if precision is not None and precision not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS} (or None), got {precision!r}")
         self.nrows, self.npatches, self.patch_size, self.fov = nrows, npatches, patch_size, fov
         _build_tree(self, schema(npatches, self._ITERATIVE))
-        self._eng = Engine(nrows, npatches, patch_size, fov, self._ITERATIVE)
+        self._eng = Engine(nrows, npatches, patch_size, fov, self._ITERATIVE, precision=precision)
         self._loaded = False          # a checkpoint has been loaded (the zero-initialised master copy is not a model)
         self._dirty = True            # packed buffers are out of date w.r.t. the master copy
         self._lanes = None
@@ -258,7 +262,7 @@ class spherical_fusion(nn.Module):
             if not self._loaded:
                 raise RuntimeError("no weights loaded: call load_state_dict() first")
             if ctx.eng is None or ctx.version != self._master_version:
-                eng = Engine(self.nrows, self.npatches, self.patch_size, self.fov, self._ITERATIVE)
+                eng = Engine(self.nrows, self.npatches, self.patch_size, self.fov, self._ITERATIVE, precision=self._eng.precision)
                 with torch.cuda.device(dev):
                     eng.pack(nn.Module.state_dict(self), dev)
                 ctx.eng, ctx.lanes, ctx.version = eng, None, self._master_version
@@ -283,6 +287,11 @@ class spherical_fusion(nn.Module):
                 yield
             finally:
                 ctx.lanes = d["_lanes"]
+
+    @property
+    def precision(self):
+        """the arithmetic mode of the convolutions ("f16x3", "f16x1" or "fp32"), fixed at construction"""
+        return self._eng.precision
 
     def state_dict_schema(self):
         return schema(self.npatches, self._ITERATIVE)

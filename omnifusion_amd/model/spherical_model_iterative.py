@@ -18,8 +18,8 @@ from .. import _lib
 class spherical_fusion(_single):
     _ITERATIVE = True
 
-    def __init__(self, nrows=4, npatches=18, patch_size=(256, 256), fov=(80, 80)):
-        super().__init__(nrows, npatches, patch_size, fov)
+    def __init__(self, nrows=4, npatches=18, patch_size=(256, 256), fov=(80, 80), *, precision=None):
+        super().__init__(nrows, npatches, patch_size, fov, precision=precision)
 
     @torch.no_grad()
     def forward(self, high_res, iter, confidence=False):

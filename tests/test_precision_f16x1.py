@@ -1,0 +1,170 @@
+"""CPU: the f16x1 precision mode — one fp16 matrix instruction per convolution product block (A_hi . W_hi, fp32 accumulation).
+
+The public surface (constructor keyword, `net.precision`, unchanged state_dict schema), the C ABI (two new entry points, fmt bit 3
+documented in the header) and the generated code: every f16x1 kernel exists beside its f16x3 sibling with a third of its matrix
+instructions and fewer LDS fragment reads, and the f16x3 kernels' instruction counts are pinned to those of the code before the mode
+existed (their disassembly was compared instruction for instruction when the mode was added)."""
+import collections
+import os
+import re
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+NEW_SYMBOLS = ("omni_stem_sh_f16x1", "omni_conv3x3_up2_heads_sh_f16x1")
+FAMILIES = ("conv_sh_kernel", "conv3x3_halo_sh_kernel", "conv3x3_up2_g1_kernel", "stem_f16x3_kernel", "stem_f16x3_pc_kernel")
+
+# (v_mfma, ds_read, instructions) of every f16x3 instantiation; template arguments as the mangled name lists them, the last one is X1 = 0
+F16X3_PINNED = {
+    "conv3x3_halo_sh_kernel<32,4,0,16,0>": (54, 78, 4213),
+    "conv3x3_halo_sh_kernel<32,4,0,8,0>": (54, 78, 4238),
+    "conv3x3_halo_sh_kernel<64,4,0,16,0>": (108, 116, 7494),
+    "conv3x3_halo_sh_kernel<64,4,0,8,0>": (108, 116, 7538),
+    "conv3x3_halo_sh_kernel<64,8,0,0,0>": (108, 116, 7316),
+    "conv3x3_halo_sh_kernel<32,8,0,0,0>": (108, 150, 4489),
+    "conv3x3_halo_sh_kernel<64,4,0,0,0>": (108, 116, 7548),
+    "conv3x3_halo_sh_kernel<32,4,0,0,0>": (54, 78, 4251),
+    "conv3x3_halo_sh_kernel<64,4,1,0,0>": (108, 116, 8529),
+    "conv3x3_halo_sh_kernel<32,4,1,0,0>": (54, 78, 5221),
+    "conv_sh_kernel<128,32,4,1,3,0,0,0,0>": (30, 44, 4748),
+    "conv_sh_kernel<128,128,2,2,3,0,0,0,0>": (120, 96, 14313),
+    "conv_sh_kernel<128,64,2,2,3,0,0,0,0>": (60, 68, 8031),
+    "conv_sh_kernel<128,64,4,2,3,0,0,0,0>": (30, 44, 4252),
+    "conv_sh_kernel<128,128,4,2,3,0,0,0,0>": (60, 68, 7382),
+    "conv_sh_kernel<256,128,4,2,3,0,0,0,0>": (120, 96, 14088),
+    "conv_sh_kernel<128,128,4,2,3,4,1,0,0>": (120, 128, 8377),
+    "conv_sh_kernel<128,128,4,2,3,4,0,0,0>": (60, 68, 8047),
+    "conv_sh_kernel<128,64,4,2,3,4,1,0,0>": (60, 84, 4981),
+    "conv_sh_kernel<128,64,4,2,3,4,0,0,0>": (30, 44, 4767),
+    "conv_sh_kernel<64,64,2,2,6,4,0,0,0>": (66, 92, 4938),
+    "conv_sh_kernel<64,64,2,2,6,0,0,0,0>": (66, 92, 4891),
+    "conv_sh_kernel<64,64,2,2,3,0,0,0,0>": (30, 44, 4307),
+    "conv_sh_kernel<128,64,4,2,3,4,1,1,0>": (60, 80, 9647),       # the experimental Winograd form (f16x3 only)
+    "conv3x3_up2_g1_kernel<0,0>": (54, 72, 4156),
+    "conv3x3_up2_g1_kernel<1,0>": (60, 72, 3389),
+    "stem_f16x3_pc_kernel<0>": (72, 148, 4636),
+    "stem_f16x3_kernel<0>": (72, 100, 2753),
+}
+HEADS_MFMA = 6          # conv3x3_up2_g1_kernel<HEADS = 1>: the heads' own products, f16x3 in both modes
+
+
+@pytest.fixture(autouse=True)
+def _default_env(monkeypatch):
+    monkeypatch.delenv("OMNI_NET_PRECISION", raising=False)
+
+
+def _classes():
+    from omnifusion_amd.model.spherical_model import spherical_fusion as single
+    from omnifusion_amd.model.spherical_model_iterative import spherical_fusion as iterative
+    return single, iterative
+
+
+def test_constructors_take_and_report_the_precision():
+    single, iterative = _classes()
+    for cls in (single, iterative):
+        kw = {} if cls is single else {"patch_size": (128, 128)}
+        assert cls(**kw).precision == "f16x3"
+        net = cls(**kw, precision="f16x1")
+        assert net.precision == "f16x1"
+        assert net._eng.sh and net._eng.terms == 1
+        assert cls(**kw, precision="f16x3")._eng.terms == 3
+        fp = cls(**kw, precision="fp32")
+        assert fp.precision == "fp32" and not fp._eng.sh
+
+
+def test_keyword_beats_the_environment_and_none_defers_to_it(monkeypatch):
+    single, _ = _classes()
+    monkeypatch.setenv("OMNI_NET_PRECISION", "fp32")
+    assert single().precision == "fp32"
+    assert single(precision="f16x1").precision == "f16x1"
+
+
+def test_unknown_precision_keyword_raises():
+    single, iterative = _classes()
+    for bad in ("f16x2", "fp16", "", "F16X1"):
+        with pytest.raises(ValueError):
+            single(precision=bad)
+        with pytest.raises(ValueError):
+            iterative(patch_size=(128, 128), precision=bad)
+    with pytest.raises(TypeError):                                 # keyword-only
+        single(4, 18, (128, 128), (80, 80), "f16x1")
+
+
+def test_state_dict_schema_is_the_default_one():
+    single, iterative = _classes()
+    for cls, kw in ((single, {}), (iterative, {"patch_size": (128, 128)})):
+        a, b = cls(**kw).state_dict(), cls(**kw, precision="f16x1").state_dict()
+        assert list(a) == list(b)
+        assert all(a[k].shape == b[k].shape and a[k].dtype == b[k].dtype for k in a)
+
+
+def test_lanes_carry_the_precision():
+    from omnifusion_amd.model._engine import Engine
+    e = Engine(4, 18, 128, 80, False, precision="f16x1")
+    assert e.lane().precision == "f16x1" and e.lane()._x1 == 8
+    assert Engine(4, 18, 128, 80, False, precision="f16x3").lane()._x1 == 0
+
+
+def test_new_entry_points_declared_exported_and_bound():
+    from omnifusion_amd import _lib, build
+    header = open(os.path.join(ROOT, "include", "omnifusion.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    for name in NEW_SYMBOLS:
+        assert re.search(r"\bint\s+" + name + r"\s*\(", code), name
+        assert name in _lib.EXPORTS
+    assert "fmt bit 3" in header
+    build.build()
+    L = _lib.load()
+    for name in NEW_SYMBOLS:
+        assert hasattr(L, name)
+    assert L.omni_version() == 200
+
+
+def _conv_sh_kernels():
+    from omnifusion_amd import build, isa
+    build.build()
+    asm = isa.disassemble(os.path.join(ROOT, "omnifusion_amd", "csrc", "omni_conv_sh.o"))
+    body, cur = collections.OrderedDict(), None
+    for line in asm.splitlines():
+        if line.endswith(">:"):
+            cur = line.split("<", 1)[1][:-2]
+            body[cur] = []
+        elif cur and line.startswith("\t"):
+            ins = line.split("//")[0].strip()
+            if ins and ins != "...":
+                body[cur].append(ins)
+    out = {}
+    for name, ins in body.items():
+        m = re.match(r"_ZN12_GLOBAL__N_1\d+(" + "|".join(FAMILIES) + r")I(.*?)EEEv", name)
+        if m:
+            args = re.findall(r"L[ib](\d+)E", m.group(2) + "E")
+            out[f"{m.group(1)}<{','.join(args)}>"] = (sum(i.startswith("v_mfma") for i in ins), sum(i.startswith("ds_read") for i in ins), len(ins))
+    return out
+
+
+def test_isa_f16x1_kernels_have_a_third_of_the_matrix_instructions():
+    k = _conv_sh_kernels()
+    siblings = {n: re.sub(r"(,|<)1>$", r"\g<1>0>", n) for n in k if re.search(r"(,|<)1>$", n)}
+    # every f16x3 form but the experimental Winograd one has an f16x1 instantiation
+    expect = {n for n in F16X3_PINNED if n != "conv_sh_kernel<128,64,4,2,3,4,1,1,0>"}
+    assert set(siblings.values()) == expect, set(siblings.values()) ^ expect
+    assert len(siblings) == 27
+    for n, s in siblings.items():
+        m1, r1, _ = k[n]
+        m3, r3, _ = k[s]
+        heads = HEADS_MFMA if s == "conv3x3_up2_g1_kernel<1,0>" else 0
+        assert m1 > 0 and 3 * (m1 - heads) == m3 - heads, (n, m1, m3)
+        assert r1 < r3, (n, r1, r3)
+
+
+def test_isa_f16x3_kernels_are_unchanged():
+    k = _conv_sh_kernels()
+    for n, want in F16X3_PINNED.items():
+        assert k.get(n) == want, (n, k.get(n), want)
+
+
+def test_isa_check_passes_with_the_new_instantiations():
+    from omnifusion_amd import build, isa
+    build.build()
+    assert isa.check() == []

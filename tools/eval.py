@@ -50,6 +50,8 @@ def main():
     ap.add_argument("--ply-every", type=int, default=0); ap.add_argument("--out", default="results")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--depth", type=int, default=3, help="forwards in flight (spherical_fusion.pipelined); 1 = the loop of test.py as written")
+    ap.add_argument("--precision", default=None, choices=["f16x3", "f16x1", "fp32"],
+                    help="arithmetic mode of the convolutions (spherical_fusion(precision=...)); default: OMNI_NET_PRECISION, else f16x3")
     args = ap.parse_args()
     from omnifusion_amd import dist
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -66,7 +68,7 @@ def main():
         from omnifusion_amd.model.spherical_model_iterative import spherical_fusion
     else:
         from omnifusion_amd.model.spherical_model import spherical_fusion
-    network = spherical_fusion(args.nrows, N, (args.patchsize, args.patchsize), (args.fov, args.fov))        # test.py:104
+    network = spherical_fusion(args.nrows, N, (args.patchsize, args.patchsize), (args.fov, args.fov), precision=args.precision)   # test.py:104
     if world > 1:                                              # a shard of ONE panorama must give the bits of the unsharded run
         from omnifusion_amd.model._engine import Engine
         Engine.latency_plan = False
