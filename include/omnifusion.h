@@ -353,6 +353,23 @@ int omni_berhu_grad_f32(const float* pred, const float* gt, const float* mask, c
  * (x, y, z float32 = uv2xyz(coords2uv(pixel)) * depth, util.py:159-174; three uint8 colours = uint8(rgb * 255)). */
 int omni_pointcloud_ply_f32(const float* depth, const float* rgb, unsigned char* records, int B, int H, int W, omni_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Depth-image-based rendering (csrc/omni_dibr.hip): a panorama as seen from a camera moved by a stereo baseline, by a forward
+ * bilinear splat.  Layouts: img/recon [B,C,H,W], depth [B,1,H,W], coords [B,2,H,W] (u = column, v = row), mask [B,1,H,W] uint8
+ * (NULL: not written).  The sums are 64-bit fixed-point integers: the result is bit-identical from run to run, under graph replay and
+ * for a batch against its items one at a time.  `workspace` (omni_dibr_workspace_bytes(B, C, H, W) bytes, any content) is zeroed
+ * inside the call; nothing is allocated and the host is never synchronised.  Non-finite img / depth values make the targets they
+ * reach NaN. */
+size_t omni_dibr_workspace_bytes(int B, int C, int H, int W);
+/* supervision/splatting.py:73-80 */
+int omni_splat_render_f32(const float* img, const float* depth, const float* coords, float max_depth,
+                          float* recon, unsigned char* mask /* nullable */, int B, int C, int H, int W,
+                          void* workspace, omni_stream_t stream);
+/* util.py:384-413; mode 0 = vertical, 1 = horizontal; grid_batched: grids are [B,2,H,W] instead of [1,2,H,W] */
+int omni_dibr_f32(const float* img, const float* depth, const float* uvgrid, const float* sgrid, int grid_batched,
+                  float baseline, int mode, float* recon, unsigned char* mask /* nullable */,
+                  int B, int C, int H, int W, void* workspace, omni_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,7 @@ EXPORTS = [
     "omni_png_info", "omni_png_decode", "omni_png_decode_batch", "omni_zlib_inflate", "omni_png_checksums",
     "omni_preprocess_rgb_u8", "omni_preprocess_depth_u16", "omni_berhu_workspace_bytes", "omni_berhu_loss_f32", "omni_berhu_grad_f32",
     "omni_pointcloud_ply_f32",
+    "omni_dibr_workspace_bytes", "omni_splat_render_f32", "omni_dibr_f32",
 ]
 
 
@@ -59,6 +60,10 @@ def load():
     lib.omni_last_error.restype = ctypes.c_char_p
     lib.omni_version.restype = ctypes.c_int
     lib.omni_up2_heads_scratch_bytes.restype = ctypes.c_size_t
+    lib.omni_dibr_workspace_bytes.restype = ctypes.c_size_t
+    lib.omni_splat_render_f32.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_float] + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
+    lib.omni_dibr_f32.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_float, ctypes.c_int] + [ctypes.c_void_p] * 2 + \
+        [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
     for name in EXPORTS:
         getattr(lib, name)          # AttributeError here = header/library mismatch
     _lib = lib

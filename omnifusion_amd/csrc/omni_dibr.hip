@@ -1,0 +1,354 @@
+// omni_dibr.hip — depth-image-based rendering (DIBR) of a panorama from a displaced viewpoint, gfx950 only.
+//
+//   omni_splat_render_f32   supervision/splatting.py:73-80 `render(img, depth, coords, max_depth)`: forward bilinear splat of
+//                           img * w and of w (w = 1 / exp(2 depth / max_depth)), then recon = acc / wacc, mask = wacc > 1e-3
+//   omni_dibr_f32           util.py:384-413 `dibr_vertical` / `dibr_horizontal`: the same splat, the target coordinates evaluated
+//                           in registers from depth, sgrid and uvgrid (spherical/derivatives.py:53-71,93-105,168-177)
+//
+// Determinism: the reference accumulates with fp32 scatter_add, whose sum depends on the order of arrival.  Here every
+// contribution x is rounded ONCE to a fixed-point integer q = rint(x * 2^s) and added with a 64-bit integer atomic
+// (global_atomic_add_x2, no return): integer addition is associative, so the sums are the same bits in any order — run to run, under
+// graph replay, and for a batch against its items one at a time (s is chosen per batch item, from that item's data only).
+//
+// Scale: a pre-pass stores, per batch item, max |img * w| and max w over the finite values (as uint bits: non-negative floats order
+// like their bits).  With e = ceil(log2 max) and L = ceil(log2 (H*W)), s = 62 - L - e.  Every |q| <= 2^(62-L), a target receives at
+// most one contribution per source pixel (a source's four corners are distinct pixels), so no sum can exceed 2^62.  At 512 x 1024 and
+// max w = 1 the weight resolution is 2^-43.
+//
+// Non-finite values: a source whose weight is not finite poisons the targets it reaches (recon NaN, mask 0); a source whose img * w is
+// not finite poisons them for recon only.  The reference propagates inf / NaN through its float sums instead.
+// Sources whose coordinates are not finite are dropped (render only: the DIBR modes clean their coordinates as the reference does).
+#include "omni_internal.h"
+
+namespace {
+
+constexpr int DIBR_RENDER = -1, DIBR_VERTICAL = 0, DIBR_HORIZONTAL = 1;
+
+__device__ __forceinline__ float dibr_weight(float depth, float max_depth)
+{
+    return 1.0f / expf(2.0f * depth / max_depth);                   // splatting.py:68-70, IEEE division
+}
+
+__device__ __forceinline__ bool finite(float x) { return fabsf(x) <= 3.402823466e38f; }
+
+// e = ceil(log2 m) of the per-item maximum (bits of a non-negative float), clamped so that both 2^s and 2^-s are normal floats
+__device__ __forceinline__ int dibr_exponent(unsigned bits)
+{
+    const float m = __uint_as_float(bits);
+    if (!(m > 0.0f)) return 0;
+    int k;
+    const float f = frexpf(m, &k);                                  // m = f * 2^k, f in [0.5, 1)
+    const int e = (f == 0.5f) ? k - 1 : k;
+    return e < -60 ? -60 : e;
+}
+
+__device__ __forceinline__ float pow2f(int s) { return __int_as_float((127 + s) << 23); }     // s in [-126, 127]
+
+// ---------------------------------------------------------------- pass 1: per-item scale
+__global__ __launch_bounds__(256) void dibr_max_kernel(const float* __restrict__ img, const float* __restrict__ depth, float max_depth,
+                                                       int C, size_t HW, unsigned* __restrict__ maxbits /* [2][B] */)
+{
+    const int b = blockIdx.y, B = gridDim.y;
+    float mi = 0.0f, mw = 0.0f;
+    for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < HW; p += (size_t)gridDim.x * 256) {
+        const float w = dibr_weight(depth[(size_t)b * HW + p], max_depth);
+        if (!finite(w)) continue;
+        mw = fmaxf(mw, w);
+        for (int c = 0; c < C; ++c) {
+            const float v = img[((size_t)b * C + c) * HW + p] * w;
+            if (finite(v)) mi = fmaxf(mi, fabsf(v));
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { mi = fmaxf(mi, __shfl_xor(mi, o)); mw = fmaxf(mw, __shfl_xor(mw, o)); }
+    __shared__ float part[2][4];
+    if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = mi; part[1][threadIdx.x >> 6] = mw; }
+    __syncthreads();
+    if (threadIdx.x == 0) {                                          // one atomic pair per block (same-address atomics serialise)
+        atomicMax(maxbits + b, __float_as_uint(fmaxf(fmaxf(part[0][0], part[0][1]), fmaxf(part[0][2], part[0][3]))));
+        atomicMax(maxbits + B + b, __float_as_uint(fmaxf(fmaxf(part[1][0], part[1][1]), fmaxf(part[1][2], part[1][3]))));
+    }
+}
+
+__global__ __launch_bounds__(256) void dibr_zero_kernel(uint4* __restrict__ p, size_t n16)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) p[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// ---------------------------------------------------------------- pass 2: the splat
+// A block takes a tile of TILE_R x 64 source pixels of one batch item (a row across the lanes of a wave, TILE_R / 4 rows per wave).
+// The targets of a tile usually fall in a small box (DIBR displacements are smooth): when the box of all surviving corners fits
+// DIBR_WIN int64 words per channel set, the block sums into LDS (ds_add_u64) and then adds each touched target to global memory once
+// (one 64-bit atomic per target and channel instead of one per corner and channel).  Otherwise (a tile across the seam wrap, noisy
+// depth) every contribution goes straight to a global atomic.  Either way the integer sums are the same bits.
+constexpr int TILE_R = 16, TILE_C = 64, DIBR_WIN = 6144;            // 48 KiB of LDS per block
+
+struct Src { float cw[4], w; int u0, v0, live; };
+
+template <int MODE>
+__device__ __forceinline__ Src dibr_source(const float* __restrict__ depth, const float* __restrict__ coords, const float* __restrict__ uvgrid,
+                                           const float* __restrict__ sgrid, int grid_batched, float baseline, float max_depth,
+                                           int b, int H, int W, size_t HW, size_t p)
+{
+    Src r;
+    r.live = 0;
+    const float d = depth[(size_t)b * HW + p];
+    float u, v;
+    if (MODE == DIBR_RENDER) {
+        u = coords[((size_t)b * 2) * HW + p];
+        v = coords[((size_t)b * 2 + 1) * HW + p];
+        if (!finite(u) || !finite(v)) return r;                     // undefined in the reference (an out-of-range scatter index): dropped
+    } else {
+        const size_t g = (grid_batched ? (size_t)b * 2 * HW : 0) + p;
+        const float hs = (float)((double)H / 3.14159265358979323846);     // fp32(h / numpy.pi), derivatives.py:65,103,175
+        const float th = sgrid[g + HW];
+        if (MODE == DIBR_VERTICAL) {
+            float dth = cosf(th) * baseline / d * hs;                // :168-177, torch's op order
+            if (!finite(dth)) dth = 0.0f;                            // NaN and +-inf -> 0
+            u = uvgrid[g];
+            v = uvgrid[g + HW] + dth;
+        } else {
+            const float ph = sgrid[g], fH = (float)H;
+            float dph = sinf(ph) / (d * cosf(th)) * baseline * hs;   // :53-71 (clip variant): clamp(-h, h), then NaN -> 0
+            dph = dph != dph ? 0.0f : fminf(fmaxf(dph, -fH), fH);
+            float dth = cosf(ph) * sinf(th) * baseline / d * hs;     // :93-105: clamp(0, h); a NaN stays (torch.clamp propagates it)
+            if (dth == dth) dth = fminf(fmaxf(dth, 0.0f), fH);
+            u = uvgrid[g] + dph;
+            v = uvgrid[g + HW] + dth;
+            u = fmodf(u + 512.0f, 512.0f);                            // util.py:409: the literal 512, not W
+        }
+        if (!finite(u)) u = 0.0f;                                    // util.py:395-396,410-411: absolute 0, not zero displacement
+        if (!finite(v)) v = 0.0f;
+    }
+    // splatting.py:9-44
+    const float u0 = floorf(u), v0 = floorf(v), u1 = u0 + 1.0f, v1 = v0 + 1.0f;
+    const bool iu0 = u0 >= 0.0f && u0 <= (float)(W - 1), iu1 = u1 >= 0.0f && u1 <= (float)(W - 1);
+    const bool iv0 = v0 >= 0.0f && v0 <= (float)(H - 1), iv1 = v1 >= 0.0f && v1 <= (float)(H - 1);
+    const float u0w = iu0 ? u1 - u : 0.0f, u1w = iu1 ? u - u0 : 0.0f;
+    const float v0w = iv0 ? v1 - v : 0.0f, v1w = iv1 ? v - v0 : 0.0f;
+    r.cw[0] = u0w * v0w; r.cw[1] = u1w * v0w; r.cw[2] = u0w * v1w; r.cw[3] = u1w * v1w;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (!(r.cw[k] >= 1e-3f)) r.cw[k] = 0.0f;                     // weight_threshold, :40-44
+        r.live |= r.cw[k] != 0.0f;
+    }
+    if (r.live) {                                                    // a surviving corner lies inside the image: these ints are in range
+        r.u0 = (int)fmaxf(u0, -1.0f);
+        r.v0 = (int)fmaxf(v0, -1.0f);
+    }
+    r.w = dibr_weight(d, max_depth);
+    return r;
+}
+
+__device__ __forceinline__ long long fixq(float x, float scale) { return (long long)rintf(x * scale); }   // x * 2^s is exact; one rounding
+
+__device__ __forceinline__ int block_reduce(int v, bool is_max, int* red)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(v, o); v = is_max ? max(v, t) : min(v, t); }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    v = red[0];
+#pragma unroll
+    for (int k = 1; k < 4; ++k) v = is_max ? max(v, red[k]) : min(v, red[k]);
+    return v;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void dibr_splat_kernel(const float* __restrict__ img, const float* __restrict__ depth,
+                                                         const float* __restrict__ coords, const float* __restrict__ uvgrid,
+                                                         const float* __restrict__ sgrid, int grid_batched, float baseline, float max_depth,
+                                                         int B, int C, int H, int W, int log2hw, int tiles_c, const unsigned* __restrict__ maxbits,
+                                                         unsigned long long* __restrict__ acc /* [B][C+1][H][W] */,
+                                                         unsigned* __restrict__ poison /* [B][H][W] */)
+{
+    __shared__ unsigned long long win[DIBR_WIN];
+    __shared__ int red[4];
+    constexpr int SPT = TILE_R / 4;                                  // source rows per thread
+    const size_t HW = (size_t)H * W;
+    const int b = blockIdx.y;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int x = (int)(blockIdx.x % tiles_c) * TILE_C + lane;
+    const int y0 = (int)(blockIdx.x / tiles_c) * TILE_R + wv * SPT;
+    Src src[SPT];
+    int rmin = 1 << 30, rmax = -1, cmin = 1 << 30, cmax = -1;
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) {
+        src[j].live = 0;
+        if (x < W && y0 + j < H)
+            src[j] = dibr_source<MODE>(depth, coords, uvgrid, sgrid, grid_batched, baseline, max_depth, b, H, W, HW, (size_t)(y0 + j) * W + x);
+        if (src[j].live) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (src[j].cw[k] != 0.0f) {
+                    const int r = src[j].v0 + (k >> 1), c = src[j].u0 + (k & 1);
+                    rmin = min(rmin, r); rmax = max(rmax, r); cmin = min(cmin, c); cmax = max(cmax, c);
+                }
+        }
+    }
+    rmin = block_reduce(rmin, false, red); rmax = block_reduce(rmax, true, red);
+    cmin = block_reduce(cmin, false, red); cmax = block_reduce(cmax, true, red);
+    if (rmax < 0) return;                                            // no surviving corner in the whole tile (block-uniform)
+    const int R = rmax - rmin + 1, Cc = cmax - cmin + 1, box = R * Cc;
+#ifdef OMNI_DIBR_NO_LDS
+    const bool use_lds = false;                                      // (A/B build for tools/dibr_bench.py: global atomics only)
+#else
+    const bool use_lds = (long long)box * (C + 1) <= DIBR_WIN;        // block-uniform
+#endif
+
+    const int L = log2hw;
+    const float sc_w = pow2f(62 - L - dibr_exponent(maxbits[B + b]));
+    const float sc_i = pow2f(62 - L - dibr_exponent(maxbits[b]));
+    if (use_lds) {
+        for (int e = threadIdx.x; e < box * (C + 1); e += 256) win[e] = 0ull;
+        __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) {
+        if (!src[j].live) continue;
+        const Src& sj = src[j];
+        const size_t p = (size_t)(y0 + j) * W + x;
+        int tgt[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int r = sj.v0 + (k >> 1), c = sj.u0 + (k & 1);
+            tgt[k] = use_lds ? (r - rmin) * Cc + (c - cmin) : r * W + c;
+        }
+        auto add = [&](int ch, int k, long long q) {
+            if (q == 0) return;
+            if (use_lds) atomicAdd(win + (size_t)ch * box + tgt[k], (unsigned long long)q);
+            else atomicAdd(acc + ((size_t)b * (C + 1) + ch) * HW + tgt[k], (unsigned long long)q);   // two's complement: signed sums wrap
+        };
+        unsigned pbits = 0;
+        if (!finite(sj.w)) {
+            pbits = 3u;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (sj.cw[k] != 0.0f) add(C, k, fixq(sj.w * sj.cw[k], sc_w));
+            for (int c = 0; c < C; ++c) {
+                const float xv = img[((size_t)b * C + c) * HW + p] * sj.w;   // splatting.py:76 img * weights, then * corner weight (:49-52)
+                if (!finite(xv)) { pbits |= 1u; continue; }
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (sj.cw[k] != 0.0f) add(c, k, fixq(xv * sj.cw[k], sc_i));
+            }
+        }
+        if (pbits) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (sj.cw[k] != 0.0f) atomicOr(poison + (size_t)b * HW + (size_t)(sj.v0 + (k >> 1)) * W + (sj.u0 + (k & 1)), pbits);
+        }
+    }
+    if (use_lds) {
+        __syncthreads();
+        for (int e = threadIdx.x; e < box; e += 256) {
+            const int r = e / Cc, c = e - r * Cc;
+            const size_t t = (size_t)(rmin + r) * W + (cmin + c);
+            for (int ch = 0; ch <= C; ++ch) {
+                const unsigned long long q = win[(size_t)ch * box + e];
+                if (q) atomicAdd(acc + ((size_t)b * (C + 1) + ch) * HW + t, q);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------- pass 3: int64 sums -> recon, mask (splatting.py:63-66,78-79)
+__global__ __launch_bounds__(256) void dibr_normalise_kernel(const long long* __restrict__ acc, const unsigned* __restrict__ poison,
+                                                             const unsigned* __restrict__ maxbits, int B, int C, size_t HW, int log2hw,
+                                                             float* __restrict__ recon, unsigned char* __restrict__ mask)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)B * HW) return;
+    const int b = (int)(i / HW);
+    const size_t p = i - (size_t)b * HW;
+    const unsigned pb = poison[i];
+    const float inv_w = pow2f(-(62 - log2hw - dibr_exponent(maxbits[B + b])));
+    const float inv_i = pow2f(-(62 - log2hw - dibr_exponent(maxbits[b])));
+    const float wsum = (float)acc[((size_t)b * (C + 1) + C) * HW + p] * inv_w;
+    const float den = wsum + (wsum <= 1e-8f ? 1e-8f : 0.0f);         // weights + epsilon * (weights <= epsilon)
+    for (int c = 0; c < C; ++c) {
+        const float a = (float)acc[((size_t)b * (C + 1) + c) * HW + p] * inv_i;
+        recon[((size_t)b * C + c) * HW + p] = pb ? __int_as_float(0x7fc00000) : a / den;
+    }
+    if (mask) mask[i] = (wsum > 1e-3f && !(pb & 2u)) ? 1 : 0;
+}
+
+struct WsLayout { size_t hdr, acc, poison, total; };
+
+WsLayout ws_layout(int B, int C, int H, int W)
+{
+    WsLayout l;
+    const size_t n = (size_t)B * H * W;
+    l.hdr = 0;
+    l.acc = ((size_t)2 * B * sizeof(unsigned) + 255) / 256 * 256;
+    l.poison = l.acc + sizeof(long long) * (size_t)(C + 1) * n;
+    l.total = (l.poison + sizeof(unsigned) * n + 255) / 256 * 256;
+    return l;
+}
+
+int dibr_run(int mode, const float* img, const float* depth, const float* coords, const float* uvgrid, const float* sgrid, int grid_batched,
+             float baseline, float max_depth, float* recon, unsigned char* mask, int B, int C, int H, int W, void* workspace, hipStream_t s,
+             const char* what)
+{
+    if (!img || !depth || !recon || !workspace || (mode == DIBR_RENDER ? !coords : (!uvgrid || !sgrid)))
+        OMNI_FAIL(OMNI_ERR_INVALID, std::string(what) + ": null device pointer");
+    if (B < 1 || C < 1 || H < 1 || W < 1 || (long long)H * W > (1ll << 30) || (long long)B * H * W > (1ll << 31) - 1)
+        OMNI_FAIL(OMNI_ERR_INVALID, std::string(what) + ": bad shape");
+    if (!(max_depth > 0.0f) || !(max_depth <= 3.402823466e38f)) OMNI_FAIL(OMNI_ERR_INVALID, std::string(what) + ": max_depth must be finite and > 0");
+    if (mode != DIBR_RENDER && !(fabsf(baseline) <= 3.402823466e38f)) OMNI_FAIL(OMNI_ERR_INVALID, std::string(what) + ": baseline must be finite");
+    if ((uintptr_t)workspace & 15) OMNI_FAIL(OMNI_ERR_INVALID, std::string(what) + ": workspace must be 16-byte aligned");
+    const WsLayout l = ws_layout(B, C, H, W);
+    char* ws = (char*)workspace;
+    unsigned* maxbits = (unsigned*)(ws + l.hdr);
+    unsigned long long* acc = (unsigned long long*)(ws + l.acc);
+    unsigned* poison = (unsigned*)(ws + l.poison);
+    const size_t HW = (size_t)H * W, n = (size_t)B * HW;
+    int log2hw = 0;
+    while ((1ull << log2hw) < HW) ++log2hw;
+    // zeroed by a kernel (not hipMemsetAsync): the call is captured into graphs with the same meaning
+    hipLaunchKernelGGL(dibr_zero_kernel, dim3(2048), dim3(256), 0, s, (uint4*)workspace, l.total / 16);
+    const unsigned gx = (unsigned)((HW + 255) / 256 < 128 ? (HW + 255) / 256 : 128);   // enough waves in flight; 2 x 128 same-address atomics per item
+    hipLaunchKernelGGL(dibr_max_kernel, dim3(gx, B), dim3(256), 0, s, img, depth, max_depth, C, HW, maxbits);
+    const int tiles_c = (W + TILE_C - 1) / TILE_C, tiles = tiles_c * ((H + TILE_R - 1) / TILE_R);
+    const dim3 sg(tiles, B);
+    if (mode == DIBR_RENDER)
+        hipLaunchKernelGGL(dibr_splat_kernel<DIBR_RENDER>, sg, dim3(256), 0, s, img, depth, coords, nullptr, nullptr, 0, 0.0f, max_depth,
+                           B, C, H, W, log2hw, tiles_c, (const unsigned*)maxbits, acc, poison);
+    else if (mode == DIBR_VERTICAL)
+        hipLaunchKernelGGL(dibr_splat_kernel<DIBR_VERTICAL>, sg, dim3(256), 0, s, img, depth, nullptr, uvgrid, sgrid, grid_batched, baseline,
+                           max_depth, B, C, H, W, log2hw, tiles_c, (const unsigned*)maxbits, acc, poison);
+    else
+        hipLaunchKernelGGL(dibr_splat_kernel<DIBR_HORIZONTAL>, sg, dim3(256), 0, s, img, depth, nullptr, uvgrid, sgrid, grid_batched, baseline,
+                           max_depth, B, C, H, W, log2hw, tiles_c, (const unsigned*)maxbits, acc, poison);
+    const unsigned g = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(dibr_normalise_kernel, dim3(g), dim3(256), 0, s, (const long long*)acc, (const unsigned*)poison, (const unsigned*)maxbits,
+                       B, C, HW, log2hw, recon, mask);
+    OMNI_HIP(hipGetLastError());
+    return OMNI_OK;
+}
+
+}  // namespace
+
+extern "C" size_t omni_dibr_workspace_bytes(int B, int C, int H, int W)
+{
+    if (B < 1 || C < 1 || H < 1 || W < 1) return 0;
+    return ws_layout(B, C, H, W).total;
+}
+
+extern "C" int omni_splat_render_f32(const float* img, const float* depth, const float* coords, float max_depth, float* recon, unsigned char* mask,
+                                     int B, int C, int H, int W, void* workspace, omni_stream_t stream)
+{
+    return dibr_run(DIBR_RENDER, img, depth, coords, nullptr, nullptr, 0, 0.0f, max_depth, recon, mask, B, C, H, W, workspace,
+                    (hipStream_t)stream, "omni_splat_render_f32");
+}
+
+extern "C" int omni_dibr_f32(const float* img, const float* depth, const float* uvgrid, const float* sgrid, int grid_batched, float baseline,
+                             int mode, float* recon, unsigned char* mask, int B, int C, int H, int W, void* workspace, omni_stream_t stream)
+{
+    if (mode != DIBR_VERTICAL && mode != DIBR_HORIZONTAL) OMNI_FAIL(OMNI_ERR_INVALID, "omni_dibr_f32: mode must be 0 (vertical) or 1 (horizontal)");
+    if (grid_batched != 0 && grid_batched != 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_dibr_f32: grid_batched must be 0 or 1");
+    return dibr_run(mode, img, depth, nullptr, uvgrid, sgrid, grid_batched, baseline, 8.0f, recon, mask, B, C, H, W, workspace,
+                    (hipStream_t)stream, "omni_dibr_f32");
+}

@@ -1,0 +1,82 @@
+"""render — host-side mirror of /root/reference/supervision/splatting.py:73-80 (forward bilinear splatting), on the device.
+
+    recon, mask = render(img, depth, coords, max_depth=20.0)     # img [B,C,H,W], depth [B,1,H,W], coords [B,2,H,W] (u = column, v = row)
+
+Same name, arguments and values as the reference: each source pixel splats img * w and w (w = 1 / exp(2 depth / max_depth)) onto
+the four pixels around (u, v) with bilinear weights (corners off the image, and corner weights below 1e-3, are dropped); then
+recon = sum(img * w) / sum(w) and mask = sum(w) > 1e-3 (a bool tensor [B,1,H,W]).  Everything runs in libomnifusion_hip.so
+(csrc/omni_dibr.hip): one pre-pass, one splat kernel with 64-bit fixed-point integer atomics, one normalise kernel.  Unlike the
+reference's fp32 scatter_add the sums do not depend on the order of arrival: the result is the same bits on every run.
+
+Inference only (no backward); `render_to` (:83-88) is not provided.  Divergences: DESIGN.md §7 (d5, NaN poisoning).
+"""
+import ctypes
+
+import torch
+
+from .. import _lib
+
+
+def _p(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _check(name, t, ndim=4):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a tensor")
+    if t.requires_grad:
+        raise ValueError(f"{name} requires grad: DIBR / render are inference only (no backward)")
+    if not t.is_cuda:
+        raise ValueError(f"{name} must be a tensor on an MI355X device; there is no CPU path")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32 (got {t.dtype})")
+    if t.dim() != ndim:
+        raise ValueError(f"{name} must have {ndim} dimensions [B,.,H,W] (got shape {tuple(t.shape)})")
+
+
+def inference_only(**tensors):
+    for name, t in tensors.items():
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise ValueError(f"{name} requires grad: DIBR / render are inference only (no backward)")
+
+
+def check_image_depth(img, depth):
+    """Validate img [B,C,H,W] and depth [B,1,H,W] (GPU float32, no grad); returns B, C, H, W."""
+    _check("img", img)
+    _check("depth", depth)
+    B, C, H, W = img.shape
+    if depth.shape != (B, 1, H, W):
+        raise ValueError(f"depth must be [B,1,H,W] = {(B, 1, H, W)} (got {tuple(depth.shape)})")
+    if depth.device != img.device:
+        raise ValueError("img and depth must live on the same device")
+    if B < 1 or C < 1 or H < 1 or W < 1:
+        raise ValueError("empty tensor")
+    return B, C, H, W
+
+
+def run(img, depth, want_mask, launch):
+    """Allocate recon / mask / workspace on img's device and call `launch(lib, recon, mask, workspace, stream)`."""
+    lib = _lib.load()
+    B, C, H, W = img.shape
+    recon = torch.empty((B, C, H, W), dtype=torch.float32, device=img.device)
+    mask = torch.empty((B, 1, H, W), dtype=torch.uint8, device=img.device) if want_mask else None
+    ws = torch.empty(lib.omni_dibr_workspace_bytes(B, C, H, W), dtype=torch.uint8, device=img.device)
+    with torch.cuda.device(img.device):
+        launch(lib, recon, mask, ws, _lib.stream_of(img))
+    return recon, (mask.view(torch.bool) if want_mask else None)
+
+
+def render(img, depth, coords, max_depth=20.0):
+    inference_only(img=img, depth=depth, coords=coords)
+    B, C, H, W = check_image_depth(img, depth)
+    _check("coords", coords)
+    if coords.shape != (B, 2, H, W):
+        raise ValueError(f"coords must be [B,2,H,W] = {(B, 2, H, W)} (got {tuple(coords.shape)})")
+    if coords.device != img.device:
+        raise ValueError("coords must live on img's device")
+    img, depth, coords = img.contiguous(), depth.contiguous(), coords.contiguous()
+
+    def launch(lib, recon, mask, ws, stream):
+        _lib.check(lib.omni_splat_render_f32(_p(img), _p(depth), _p(coords), float(max_depth), _p(recon), _p(mask),
+                                             B, C, H, W, _p(ws), stream), "splatting.render")
+    return run(img, depth, True, launch)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Evaluation harness — the loop of /root/reference/test.py:193-203,244-258 on the MI355X path.
 
-    python tools/eval.py [--checkpoint ckpt.pth] [--iterative --iter 2] [--batches 8 --batch 4] [--ply-every 20 --out results/]
+    python tools/eval.py [--checkpoint ckpt.pth] [--iterative --iter 2] [--batches 8 --batch 4] [--ply-every 20 --out results/ [--dibr-baseline 0.26]]
                          [--from-host]  [--gpus N]
 
     network = spherical_fusion(...); network.load_state_dict(ckpt); network.cuda(); network.eval()          test.py:104-111
@@ -48,6 +48,8 @@ def main():
     ap.add_argument("--height", type=int, default=512); ap.add_argument("--width", type=int, default=1024)
     ap.add_argument("--src-scale", type=int, default=1, help="decoded frames are this many times larger than the network input (INTER_AREA on the device)")
     ap.add_argument("--ply-every", type=int, default=0); ap.add_argument("--out", default="results")
+    ap.add_argument("--dibr-baseline", type=float, default=0.0,
+                    help="with --ply-every: also render item 0 from a camera moved by this baseline (m), both DIBR modes -> dibr_{v,h}_<k>.npy")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--depth", type=int, default=3, help="forwards in flight (spherical_fusion.pipelined); 1 = the loop of test.py as written")
     ap.add_argument("--precision", default=None, choices=["f16x3", "f16x1", "fp32"],
@@ -62,6 +64,8 @@ def main():
     from omnifusion_amd.data import DeviceFeeder, preprocess_depth
     from omnifusion_amd.eval import DepthMetrics
     from omnifusion_amd.ply import write_ply_pointcloud
+    from omnifusion_amd.spherical import create_image_grid, create_spherical_grid
+    from omnifusion_amd.util import dibr_horizontal, dibr_vertical
     from omnifusion_amd.weights import make_state_dict
     N = {3: 10, 4: 18, 5: 26, 6: 46}[args.nrows]
     if args.iterative:
@@ -92,6 +96,11 @@ def main():
         out = out[-1] if args.iterative else out
         if args.ply_every and batch_idx % args.ply_every == 0 and rank == 0:
             write_ply_pointcloud(os.path.join(args.out, f"test_pred_{batch_idx}"), out, rgb)                 # test.py:233-238 (before the in-place scaling)
+            if args.dibr_baseline:                                                                           # util.py:384-413 on the prediction
+                uv = create_image_grid(args.width, args.height, device=dev); sg = create_spherical_grid(args.width, device=dev)
+                for tag, fn in (("v", dibr_vertical), ("h", dibr_horizontal)):
+                    view = fn(out[:1].detach().contiguous(), rgb[:1].contiguous(), uv, sg, args.dibr_baseline)
+                    np.save(os.path.join(args.out, f"dibr_{tag}_{batch_idx}.npy"), view[0].cpu().numpy())
         if world > 1:
             # test.py:161 takes ONE median scaling factor over the whole batch (batch_size = 2): a per-shard median gives other averages than
             # the single-GPU run.  The shards' depth maps, ground truth and masks are gathered (one all_gather of equal blocks each: teardown
