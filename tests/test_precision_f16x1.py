@@ -124,22 +124,25 @@ def test_new_entry_points_declared_exported_and_bound():
 def _conv_sh_kernels():
     from omnifusion_amd import build, isa
     build.build()
-    asm = isa.disassemble(os.path.join(ROOT, "omnifusion_amd", "csrc", "omni_conv_sh.o"))
-    body, cur = collections.OrderedDict(), None
-    for line in asm.splitlines():
-        if line.endswith(">:"):
-            cur = line.split("<", 1)[1][:-2]
-            body[cur] = []
-        elif cur and line.startswith("\t"):
-            ins = line.split("//")[0].strip()
-            if ins and ins != "...":
-                body[cur].append(ins)
+    body = []
+    for obj in isa.objects():                                      # the convolution kernels live in several units: every product object is read
+        cur = None
+        for line in isa.disassemble(obj).splitlines():
+            if line.endswith(">:"):
+                cur = []
+                body.append((line.split("<", 1)[1][:-2], cur))
+            elif cur is not None and line.startswith("\t"):
+                ins = line.split("//")[0].strip()
+                if ins and ins != "...":
+                    cur.append(ins)
     out = {}
-    for name, ins in body.items():
+    for name, ins in body:
         m = re.match(r"_ZN12_GLOBAL__N_1\d+(" + "|".join(FAMILIES) + r")I(.*?)EEEv", name)
         if m:
             args = re.findall(r"L[ib](\d+)E", m.group(2) + "E")
-            out[f"{m.group(1)}<{','.join(args)}>"] = (sum(i.startswith("v_mfma") for i in ins), sum(i.startswith("ds_read") for i in ins), len(ins))
+            key = f"{m.group(1)}<{','.join(args)}>"
+            assert key not in out, f"{key} is defined in two objects"
+            out[key] = (sum(i.startswith("v_mfma") for i in ins), sum(i.startswith("ds_read") for i in ins), len(ins))
     return out
 
 
