@@ -369,6 +369,45 @@ int omni_splat_render_f32(const float* img, const float* depth, const float* coo
 int omni_dibr_f32(const float* img, const float* depth, const float* uvgrid, const float* sgrid, int grid_batched,
                   float baseline, int mode, float* recon, unsigned char* mask /* nullable */,
                   int B, int C, int H, int W, void* workspace, omni_stream_t stream);
+/* The same two forwards (same launches, same recon / mask bits), also writing the splatted weight sum wt [B,1,H,W] float32 — what the
+ * backward needs (NaN where a non-finite weight reached the target). */
+int omni_splat_render_wt_f32(const float* img, const float* depth, const float* coords, float max_depth,
+                             float* recon, unsigned char* mask /* nullable */, float* wt, int B, int C, int H, int W,
+                             void* workspace, omni_stream_t stream);
+int omni_dibr_wt_f32(const float* img, const float* depth, const float* uvgrid, const float* sgrid, int grid_batched,
+                     float baseline, int mode, float* recon, unsigned char* mask /* nullable */, float* wt,
+                     int B, int C, int H, int W, void* workspace, omni_stream_t stream);
+/* Backward of the splat: grad_recon = dL/drecon [B,C,H,W]; recon, wt: the forward's outputs.  A gather: every source
+ * pixel re-derives its corners exactly as the forward does and reads its <= 4 targets; no atomics, nothing to zero, deterministic.
+ * Each of grad_img [B,C,H,W], grad_depth [B,1,H,W], grad_coords [B,2,H,W] is written only if non-NULL (at least one must be).
+ * The corner selection, floor and the clean-ups are constants of the backward, as in the reference's autograd; the DIBR modes chain
+ * dL/du, dL/dv into the depth through the displacement.  Where depth == 0 or the displacement is not finite the depth gradient of
+ * the DIBR modes is 0 (the reference: NaN).  `workspace`: omni_dibr_bwd_workspace_bytes(B, C, H, W) bytes, any content. */
+size_t omni_dibr_bwd_workspace_bytes(int B, int C, int H, int W);
+int omni_splat_render_bwd_f32(const float* grad_recon, const float* recon, const float* wt, const float* img, const float* depth,
+                              const float* coords, float max_depth, float* grad_img, float* grad_depth, float* grad_coords,
+                              int B, int C, int H, int W, void* workspace, omni_stream_t stream);
+int omni_dibr_bwd_f32(const float* grad_recon, const float* recon, const float* wt, const float* img, const float* depth,
+                      const float* uvgrid, const float* sgrid, int grid_batched, float baseline, int mode,
+                      float* grad_img, float* grad_depth, int B, int C, int H, int W, void* workspace, omni_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Photometric loss of view synthesis (csrc/omni_photometric.hip).  pred / gt [B,C,H,W] float32; `win`: HOST pointer to the `window`
+ * 1-D window weights (odd window, 3 .. 11); mode 0 = 'gaussian' (zero-padded), 1 = 'box' (valid average, the map zero-padded).
+ * omni_ssim_f32: the SSIM map of supervision/ssim.py `ssim_loss`.
+ * omni_photometric_loss_f32: supervision/photometric.py:34-51; mask [B,mask_c,H,W], weights [B,weights_c,H,W] float32 with 1 or C
+ * channels; *loss stays on the device.  `workspace` (omni_photometric_workspace_bytes bytes) carries the per-item counts to
+ * omni_photometric_grad_f32, which writes dloss/dpred * (*grad_out); `scratch`: omni_photometric_grad_scratch_bytes bytes. */
+int omni_ssim_f32(const float* pred, const float* gt, int B, int C, int H, int W, int window, const float* win, int mode,
+                  float* ssim, omni_stream_t stream);
+size_t omni_photometric_workspace_bytes(int B, int C, int H, int W);
+size_t omni_photometric_grad_scratch_bytes(int B, int C, int H, int W);
+int omni_photometric_loss_f32(const float* pred, const float* gt, const float* mask, int mask_c, const float* weights, int weights_c,
+                              int B, int C, int H, int W, int window, const float* win, int mode, float alpha,
+                              void* workspace, float* loss, omni_stream_t stream);
+int omni_photometric_grad_f32(const float* pred, const float* gt, const float* mask, int mask_c, const float* weights, int weights_c,
+                              int B, int C, int H, int W, int window, const float* win, int mode, float alpha,
+                              const void* workspace, void* scratch, const float* grad_out, float* grad_pred, omni_stream_t stream);
 
 #ifdef __cplusplus
 }

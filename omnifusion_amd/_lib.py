@@ -40,6 +40,9 @@ EXPORTS = [
     "omni_preprocess_rgb_u8", "omni_preprocess_depth_u16", "omni_berhu_workspace_bytes", "omni_berhu_loss_f32", "omni_berhu_grad_f32",
     "omni_pointcloud_ply_f32",
     "omni_dibr_workspace_bytes", "omni_splat_render_f32", "omni_dibr_f32",
+    "omni_splat_render_wt_f32", "omni_dibr_wt_f32", "omni_dibr_bwd_workspace_bytes", "omni_splat_render_bwd_f32", "omni_dibr_bwd_f32",
+    "omni_ssim_f32", "omni_photometric_workspace_bytes", "omni_photometric_grad_scratch_bytes", "omni_photometric_loss_f32",
+    "omni_photometric_grad_f32",
 ]
 
 
@@ -64,6 +67,17 @@ def load():
     lib.omni_splat_render_f32.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_float] + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
     lib.omni_dibr_f32.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_float, ctypes.c_int] + [ctypes.c_void_p] * 2 + \
         [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
+    vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    lib.omni_splat_render_wt_f32.argtypes = [vp] * 3 + [cf] + [vp] * 3 + [ci] * 4 + [vp] * 2
+    lib.omni_dibr_wt_f32.argtypes = [vp] * 4 + [ci, cf, ci] + [vp] * 3 + [ci] * 4 + [vp] * 2
+    lib.omni_dibr_bwd_workspace_bytes.restype = ctypes.c_size_t
+    lib.omni_splat_render_bwd_f32.argtypes = [vp] * 6 + [cf] + [vp] * 3 + [ci] * 4 + [vp] * 2
+    lib.omni_dibr_bwd_f32.argtypes = [vp] * 7 + [ci, cf, ci] + [vp] * 2 + [ci] * 4 + [vp] * 2
+    lib.omni_ssim_f32.argtypes = [vp] * 2 + [ci] * 5 + [vp, ci, vp, vp]
+    lib.omni_photometric_workspace_bytes.restype = ctypes.c_size_t
+    lib.omni_photometric_grad_scratch_bytes.restype = ctypes.c_size_t
+    lib.omni_photometric_loss_f32.argtypes = [vp, vp, vp, ci, vp, ci] + [ci] * 5 + [vp, ci, cf] + [vp] * 3
+    lib.omni_photometric_grad_f32.argtypes = [vp, vp, vp, ci, vp, ci] + [ci] * 5 + [vp, ci, cf] + [vp] * 5
     for name in EXPORTS:
         getattr(lib, name)          # AttributeError here = header/library mismatch
     _lib = lib

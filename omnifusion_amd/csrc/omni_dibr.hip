@@ -4,6 +4,8 @@
 //                           img * w and of w (w = 1 / exp(2 depth / max_depth)), then recon = acc / wacc, mask = wacc > 1e-3
 //   omni_dibr_f32           util.py:384-413 `dibr_vertical` / `dibr_horizontal`: the same splat, the target coordinates evaluated
 //                           in registers from depth, sgrid and uvgrid (spherical/derivatives.py:53-71,93-105,168-177)
+//   omni_*_wt_f32           the same forwards, also writing the splatted weight sum Wt [B,1,H,W] (what the backward needs)
+//   omni_splat_render_bwd_f32 / omni_dibr_bwd_f32   the backwards: a gather, no atomics (DESIGN.md §11 "Backward")
 //
 // Determinism: the reference accumulates with fp32 scatter_add, whose sum depends on the order of arrival.  Here every
 // contribution x is rounded ONCE to a fixed-point integer q = rint(x * 2^s) and added with a 64-bit integer atomic
@@ -85,13 +87,22 @@ constexpr int TILE_R = 16, TILE_C = 64, DIBR_WIN = 6144;            // 48 KiB of
 
 struct Src { float cw[4], w; int u0, v0, live; };
 
-template <int MODE>
+// What the backward needs on top of Src: the four 1-D weights (0 where the corner is off the image), d weight / d coordinate of each
+// (-1, +1 or 0) and d u / d depth, d v / d depth of the DIBR modes with the reference's gates (a cleaned-up or clamped displacement
+// passes no gradient); `dead`: depth == 0 or a non-finite raw displacement — the depth gradient is 0 there.
+struct SrcGrad { float uw[2], vw[2], duw[2], dvw[2], du_dd, dv_dd; int dead; };
+
+template <int MODE, bool GRAD = false>
 __device__ __forceinline__ Src dibr_source(const float* __restrict__ depth, const float* __restrict__ coords, const float* __restrict__ uvgrid,
                                            const float* __restrict__ sgrid, int grid_batched, float baseline, float max_depth,
-                                           int b, int H, int W, size_t HW, size_t p)
+                                           int b, int H, int W, size_t HW, size_t p, SrcGrad* sg = nullptr)
 {
     Src r;
     r.live = 0;
+    if (GRAD) {
+        sg->du_dd = sg->dv_dd = 0.0f; sg->dead = 0;
+        sg->uw[0] = sg->uw[1] = sg->vw[0] = sg->vw[1] = sg->duw[0] = sg->duw[1] = sg->dvw[0] = sg->dvw[1] = 0.0f;
+    }
     const float d = depth[(size_t)b * HW + p];
     float u, v;
     if (MODE == DIBR_RENDER) {
@@ -104,19 +115,26 @@ __device__ __forceinline__ Src dibr_source(const float* __restrict__ depth, cons
         const float th = sgrid[g + HW];
         if (MODE == DIBR_VERTICAL) {
             float dth = cosf(th) * baseline / d * hs;                // :168-177, torch's op order
+            if (GRAD) { sg->dead = !finite(dth) || d == 0.0f; sg->dv_dd = sg->dead ? 0.0f : -dth / d; }
             if (!finite(dth)) dth = 0.0f;                            // NaN and +-inf -> 0
             u = uvgrid[g];
             v = uvgrid[g + HW] + dth;
         } else {
             const float ph = sgrid[g], fH = (float)H;
             float dph = sinf(ph) / (d * cosf(th)) * baseline * hs;   // :53-71 (clip variant): clamp(-h, h), then NaN -> 0
-            dph = dph != dph ? 0.0f : fminf(fmaxf(dph, -fH), fH);
             float dth = cosf(ph) * sinf(th) * baseline / d * hs;     // :93-105: clamp(0, h); a NaN stays (torch.clamp propagates it)
+            if (GRAD) {                                              // clamp passes the gradient inside [min, max] (bounds included)
+                sg->dead = !finite(dph) || !finite(dth) || d == 0.0f;
+                sg->du_dd = (!sg->dead && dph >= -fH && dph <= fH) ? -dph / d : 0.0f;
+                sg->dv_dd = (!sg->dead && dth >= 0.0f && dth <= fH) ? -dth / d : 0.0f;
+            }
+            dph = dph != dph ? 0.0f : fminf(fmaxf(dph, -fH), fH);
             if (dth == dth) dth = fminf(fmaxf(dth, 0.0f), fH);
             u = uvgrid[g] + dph;
             v = uvgrid[g + HW] + dth;
             u = fmodf(u + 512.0f, 512.0f);                            // util.py:409: the literal 512, not W
         }
+        if (GRAD) { if (!finite(u)) sg->du_dd = 0.0f; if (!finite(v)) sg->dv_dd = 0.0f; }
         if (!finite(u)) u = 0.0f;                                    // util.py:395-396,410-411: absolute 0, not zero displacement
         if (!finite(v)) v = 0.0f;
     }
@@ -127,6 +145,11 @@ __device__ __forceinline__ Src dibr_source(const float* __restrict__ depth, cons
     const float u0w = iu0 ? u1 - u : 0.0f, u1w = iu1 ? u - u0 : 0.0f;
     const float v0w = iv0 ? v1 - v : 0.0f, v1w = iv1 ? v - v0 : 0.0f;
     r.cw[0] = u0w * v0w; r.cw[1] = u1w * v0w; r.cw[2] = u0w * v1w; r.cw[3] = u1w * v1w;
+    if (GRAD) {
+        sg->uw[0] = u0w; sg->uw[1] = u1w; sg->vw[0] = v0w; sg->vw[1] = v1w;
+        sg->duw[0] = iu0 ? -1.0f : 0.0f; sg->duw[1] = iu1 ? 1.0f : 0.0f;
+        sg->dvw[0] = iv0 ? -1.0f : 0.0f; sg->dvw[1] = iv1 ? 1.0f : 0.0f;
+    }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         if (!(r.cw[k] >= 1e-3f)) r.cw[k] = 0.0f;                     // weight_threshold, :40-44
@@ -257,7 +280,8 @@ __global__ __launch_bounds__(256) void dibr_splat_kernel(const float* __restrict
 // ---------------------------------------------------------------- pass 3: int64 sums -> recon, mask (splatting.py:63-66,78-79)
 __global__ __launch_bounds__(256) void dibr_normalise_kernel(const long long* __restrict__ acc, const unsigned* __restrict__ poison,
                                                              const unsigned* __restrict__ maxbits, int B, int C, size_t HW, int log2hw,
-                                                             float* __restrict__ recon, unsigned char* __restrict__ mask)
+                                                             float* __restrict__ recon, unsigned char* __restrict__ mask,
+                                                             float* __restrict__ wt /* nullable: the weight sum, for the backward */)
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (size_t)B * HW) return;
@@ -273,6 +297,115 @@ __global__ __launch_bounds__(256) void dibr_normalise_kernel(const long long* __
         recon[((size_t)b * C + c) * HW + p] = pb ? __int_as_float(0x7fc00000) : a / den;
     }
     if (mask) mask[i] = (wsum > 1e-3f && !(pb & 2u)) ? 1 : 0;
+    if (wt) wt[i] = (pb & 2u) ? __int_as_float(0x7fc00000) : wsum;
+}
+
+// ---------------------------------------------------------------- backward (DESIGN.md §11 "Backward")
+// recon_c[t] = S_c[t] / den[t], S_c[t] = sum c_ik w_i img_ic, Wt[t] = sum c_ik w_i.  With G = dL/drecon:
+//   A_c[t] = G_c[t] / den[t]  (= dL/dS_c)         Bt[t] = -sum_c G_c[t] recon_c[t] / den[t]  (= dL/dWt)
+// Pass 1 writes them as ONE record of RS = roundup4(C + 1) floats per target (A_0 .. A_{C-1}, Bt, padding): the gather of pass 2 then
+// costs one 16-byte read per corner at C = 3 instead of 2 C + 1 four-byte ones.
+__global__ __launch_bounds__(256) void dibr_bwd_prep_kernel(const float* __restrict__ G, const float* __restrict__ recon, const float* __restrict__ wt,
+                                                            int B, int C, size_t HW, int RS, float* __restrict__ rec /* [B][HW][RS] */)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)B * HW) return;
+    const int b = (int)(i / HW);
+    const size_t p = i - (size_t)b * HW;
+    const float wsum = wt[i];
+    const float den = wsum + (wsum <= 1e-8f ? 1e-8f : 0.0f);
+    float* r = rec + i * RS;
+    float bt = 0.0f;
+    for (int c = 0; c < C; ++c) {
+        const float g = G[((size_t)b * C + c) * HW + p];
+        r[c] = g / den;
+        bt -= g * recon[((size_t)b * C + c) * HW + p] / den;
+    }
+    r[C] = bt;
+    for (int c = C + 1; c < RS; ++c) r[c] = 0.0f;
+}
+
+// Pass 2: one thread per SOURCE pixel (a block = 4 rows x 64 columns of one item).  It re-derives its corners with dibr_source — the
+// function the forward splat uses, so both agree on which corners survived — reads the records of at most four targets and writes its
+// own gradients: nothing is accumulated across threads, so there are no atomics and the summation order is a constant.
+template <int MODE>
+__global__ __launch_bounds__(256) void dibr_bwd_gather_kernel(const float* __restrict__ img, const float* __restrict__ depth,
+                                                              const float* __restrict__ coords, const float* __restrict__ uvgrid,
+                                                              const float* __restrict__ sgrid, int grid_batched, float baseline, float max_depth,
+                                                              int C, int H, int W, int tiles_c, int RS, const float* __restrict__ rec,
+                                                              float* __restrict__ gimg, float* __restrict__ gdepth, float* __restrict__ gcoords)
+{
+    const size_t HW = (size_t)H * W;
+    const int b = blockIdx.y;
+    const int x = (int)(blockIdx.x % tiles_c) * TILE_C + (threadIdx.x & 63);
+    const int y = (int)(blockIdx.x / tiles_c) * 4 + (threadIdx.x >> 6);
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)y * W + x;
+    SrcGrad sg;
+    const Src s = dibr_source<MODE, true>(depth, coords, uvgrid, sgrid, grid_batched, baseline, max_depth, b, H, W, HW, p, &sg);
+    if (!s.live) {                                                   // no surviving corner: this source reached nothing
+        if (gimg) for (int c = 0; c < C; ++c) gimg[((size_t)b * C + c) * HW + p] = 0.0f;
+        if (gdepth) gdepth[(size_t)b * HW + p] = 0.0f;
+        if (gcoords) { gcoords[((size_t)b * 2) * HW + p] = 0.0f; gcoords[((size_t)b * 2 + 1) * HW + p] = 0.0f; }
+        return;
+    }
+    const float* rk[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        rk[k] = (s.cw[k] != 0.0f) ? rec + ((size_t)b * HW + (size_t)(s.v0 + (k >> 1)) * W + (s.u0 + (k & 1))) * RS : nullptr;
+    float q[4] = {0.0f, 0.0f, 0.0f, 0.0f};                          // q_ik = sum_c img_ic A_c[t_ik] + Bt[t_ik]
+    const bool need_q = gdepth || gcoords;
+    if (RS == 4) {                                                   // C <= 3: the whole record is one 16-byte read
+        float4 v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = rk[k] ? *(const float4*)rk[k] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        for (int c = 0; c < C; ++c) {
+            float a[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) a[k] = c == 0 ? v[k].x : (c == 1 ? v[k].y : v[k].z);
+            if (gimg) gimg[((size_t)b * C + c) * HW + p] = s.w * (((s.cw[0] * a[0] + s.cw[1] * a[1]) + s.cw[2] * a[2]) + s.cw[3] * a[3]);
+            if (need_q) {
+                const float iv = img[((size_t)b * C + c) * HW + p];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) q[k] += iv * a[k];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] += C == 1 ? v[k].y : (C == 2 ? v[k].z : v[k].w);
+    } else {
+        for (int c = 0; c < C; ++c) {
+            float a[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) a[k] = rk[k] ? rk[k][c] : 0.0f;
+            if (gimg) gimg[((size_t)b * C + c) * HW + p] = s.w * (((s.cw[0] * a[0] + s.cw[1] * a[1]) + s.cw[2] * a[2]) + s.cw[3] * a[3]);
+            if (need_q) {
+                const float iv = img[((size_t)b * C + c) * HW + p];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) q[k] += iv * a[k];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] += rk[k] ? rk[k][C] : 0.0f;
+    }
+    if (!need_q) return;
+    float gw = 0.0f, gu = 0.0f, gv = 0.0f;                           // dL/dw_i, dL/du_i, dL/dv_i
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (!rk[k]) continue;                                        // a dropped corner is a constant 0 (its gate is detached)
+        gw += s.cw[k] * q[k];
+        const float gc = s.w * q[k];                                 // dL/dc_ik
+        gu += gc * (sg.duw[k & 1] * sg.vw[k >> 1]);
+        gv += gc * (sg.uw[k & 1] * sg.dvw[k >> 1]);
+    }
+    if (gcoords) {
+        gcoords[((size_t)b * 2) * HW + p] = gu;
+        gcoords[((size_t)b * 2 + 1) * HW + p] = gv;
+    }
+    if (gdepth) {
+        float gd = -(2.0f / max_depth) * s.w * gw;                   // through w = 1 / exp(2 d / max_depth)
+        if (MODE != DIBR_RENDER) gd = sg.dead ? 0.0f : (gd + gu * sg.du_dd) + gv * sg.dv_dd;
+        gdepth[(size_t)b * HW + p] = gd;
+    }
 }
 
 struct WsLayout { size_t hdr, acc, poison, total; };
@@ -289,8 +422,8 @@ WsLayout ws_layout(int B, int C, int H, int W)
 }
 
 int dibr_run(int mode, const float* img, const float* depth, const float* coords, const float* uvgrid, const float* sgrid, int grid_batched,
-             float baseline, float max_depth, float* recon, unsigned char* mask, int B, int C, int H, int W, void* workspace, hipStream_t s,
-             const char* what)
+             float baseline, float max_depth, float* recon, unsigned char* mask, float* wt, int B, int C, int H, int W, void* workspace,
+             hipStream_t s, const char* what)
 {
     if (!img || !depth || !recon || !workspace || (mode == DIBR_RENDER ? !coords : (!uvgrid || !sgrid)))
         OMNI_FAIL(OMNI_ERR_INVALID, std::string(what) + ": null device pointer");
@@ -324,7 +457,38 @@ int dibr_run(int mode, const float* img, const float* depth, const float* coords
                            max_depth, B, C, H, W, log2hw, tiles_c, (const unsigned*)maxbits, acc, poison);
     const unsigned g = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(dibr_normalise_kernel, dim3(g), dim3(256), 0, s, (const long long*)acc, (const unsigned*)poison, (const unsigned*)maxbits,
-                       B, C, HW, log2hw, recon, mask);
+                       B, C, HW, log2hw, recon, mask, wt);
+    OMNI_HIP(hipGetLastError());
+    return OMNI_OK;
+}
+
+int dibr_bwd_run(int mode, const float* grad_recon, const float* recon, const float* wt, const float* img, const float* depth, const float* coords,
+                 const float* uvgrid, const float* sgrid, int grid_batched, float baseline, float max_depth, float* gimg, float* gdepth,
+                 float* gcoords, int B, int C, int H, int W, void* workspace, hipStream_t s, const char* what)
+{
+    if (!grad_recon || !recon || !wt || !img || !depth || !workspace || (mode == DIBR_RENDER ? !coords : (!uvgrid || !sgrid)))
+        OMNI_FAIL(OMNI_ERR_INVALID, std::string(what) + ": null device pointer");
+    if (!gimg && !gdepth && !gcoords) OMNI_FAIL(OMNI_ERR_INVALID, std::string(what) + ": no gradient requested");
+    if (B < 1 || C < 1 || H < 1 || W < 1 || (long long)H * W > (1ll << 30) || (long long)B * H * W > (1ll << 31) - 1)
+        OMNI_FAIL(OMNI_ERR_INVALID, std::string(what) + ": bad shape");
+    if (!(max_depth > 0.0f) || !(max_depth <= 3.402823466e38f)) OMNI_FAIL(OMNI_ERR_INVALID, std::string(what) + ": max_depth must be finite and > 0");
+    if (mode != DIBR_RENDER && !(fabsf(baseline) <= 3.402823466e38f)) OMNI_FAIL(OMNI_ERR_INVALID, std::string(what) + ": baseline must be finite");
+    if ((uintptr_t)workspace & 15) OMNI_FAIL(OMNI_ERR_INVALID, std::string(what) + ": workspace must be 16-byte aligned");
+    const size_t HW = (size_t)H * W, n = (size_t)B * HW;
+    const int RS = (C + 1 + 3) & ~3;
+    float* rec = (float*)workspace;
+    hipLaunchKernelGGL(dibr_bwd_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, grad_recon, recon, wt, B, C, HW, RS, rec);
+    const int tiles_c = (W + TILE_C - 1) / TILE_C, tiles = tiles_c * ((H + 3) / 4);
+    const dim3 sgd(tiles, B);
+    if (mode == DIBR_RENDER)
+        hipLaunchKernelGGL(dibr_bwd_gather_kernel<DIBR_RENDER>, sgd, dim3(256), 0, s, img, depth, coords, nullptr, nullptr, 0, 0.0f, max_depth,
+                           C, H, W, tiles_c, RS, (const float*)rec, gimg, gdepth, gcoords);
+    else if (mode == DIBR_VERTICAL)
+        hipLaunchKernelGGL(dibr_bwd_gather_kernel<DIBR_VERTICAL>, sgd, dim3(256), 0, s, img, depth, nullptr, uvgrid, sgrid, grid_batched, baseline,
+                           max_depth, C, H, W, tiles_c, RS, (const float*)rec, gimg, gdepth, nullptr);
+    else
+        hipLaunchKernelGGL(dibr_bwd_gather_kernel<DIBR_HORIZONTAL>, sgd, dim3(256), 0, s, img, depth, nullptr, uvgrid, sgrid, grid_batched, baseline,
+                           max_depth, C, H, W, tiles_c, RS, (const float*)rec, gimg, gdepth, nullptr);
     OMNI_HIP(hipGetLastError());
     return OMNI_OK;
 }
@@ -340,8 +504,30 @@ extern "C" size_t omni_dibr_workspace_bytes(int B, int C, int H, int W)
 extern "C" int omni_splat_render_f32(const float* img, const float* depth, const float* coords, float max_depth, float* recon, unsigned char* mask,
                                      int B, int C, int H, int W, void* workspace, omni_stream_t stream)
 {
-    return dibr_run(DIBR_RENDER, img, depth, coords, nullptr, nullptr, 0, 0.0f, max_depth, recon, mask, B, C, H, W, workspace,
+    return dibr_run(DIBR_RENDER, img, depth, coords, nullptr, nullptr, 0, 0.0f, max_depth, recon, mask, nullptr, B, C, H, W, workspace,
                     (hipStream_t)stream, "omni_splat_render_f32");
+}
+
+extern "C" int omni_splat_render_wt_f32(const float* img, const float* depth, const float* coords, float max_depth, float* recon, unsigned char* mask,
+                                        float* wt, int B, int C, int H, int W, void* workspace, omni_stream_t stream)
+{
+    if (!wt) OMNI_FAIL(OMNI_ERR_INVALID, "omni_splat_render_wt_f32: null device pointer");
+    return dibr_run(DIBR_RENDER, img, depth, coords, nullptr, nullptr, 0, 0.0f, max_depth, recon, mask, wt, B, C, H, W, workspace,
+                    (hipStream_t)stream, "omni_splat_render_wt_f32");
+}
+
+extern "C" size_t omni_dibr_bwd_workspace_bytes(int B, int C, int H, int W)
+{
+    if (B < 1 || C < 1 || H < 1 || W < 1) return 0;
+    return sizeof(float) * (size_t)((C + 1 + 3) & ~3) * B * H * W;
+}
+
+extern "C" int omni_splat_render_bwd_f32(const float* grad_recon, const float* recon, const float* wt, const float* img, const float* depth,
+                                         const float* coords, float max_depth, float* grad_img, float* grad_depth, float* grad_coords,
+                                         int B, int C, int H, int W, void* workspace, omni_stream_t stream)
+{
+    return dibr_bwd_run(DIBR_RENDER, grad_recon, recon, wt, img, depth, coords, nullptr, nullptr, 0, 0.0f, max_depth, grad_img, grad_depth,
+                        grad_coords, B, C, H, W, workspace, (hipStream_t)stream, "omni_splat_render_bwd_f32");
 }
 
 extern "C" int omni_dibr_f32(const float* img, const float* depth, const float* uvgrid, const float* sgrid, int grid_batched, float baseline,
@@ -349,6 +535,27 @@ extern "C" int omni_dibr_f32(const float* img, const float* depth, const float* 
 {
     if (mode != DIBR_VERTICAL && mode != DIBR_HORIZONTAL) OMNI_FAIL(OMNI_ERR_INVALID, "omni_dibr_f32: mode must be 0 (vertical) or 1 (horizontal)");
     if (grid_batched != 0 && grid_batched != 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_dibr_f32: grid_batched must be 0 or 1");
-    return dibr_run(mode, img, depth, nullptr, uvgrid, sgrid, grid_batched, baseline, 8.0f, recon, mask, B, C, H, W, workspace,
+    return dibr_run(mode, img, depth, nullptr, uvgrid, sgrid, grid_batched, baseline, 8.0f, recon, mask, nullptr, B, C, H, W, workspace,
                     (hipStream_t)stream, "omni_dibr_f32");
+}
+
+extern "C" int omni_dibr_wt_f32(const float* img, const float* depth, const float* uvgrid, const float* sgrid, int grid_batched, float baseline,
+                                int mode, float* recon, unsigned char* mask, float* wt, int B, int C, int H, int W, void* workspace,
+                                omni_stream_t stream)
+{
+    if (mode != DIBR_VERTICAL && mode != DIBR_HORIZONTAL) OMNI_FAIL(OMNI_ERR_INVALID, "omni_dibr_wt_f32: mode must be 0 (vertical) or 1 (horizontal)");
+    if (grid_batched != 0 && grid_batched != 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_dibr_wt_f32: grid_batched must be 0 or 1");
+    if (!wt) OMNI_FAIL(OMNI_ERR_INVALID, "omni_dibr_wt_f32: null device pointer");
+    return dibr_run(mode, img, depth, nullptr, uvgrid, sgrid, grid_batched, baseline, 8.0f, recon, mask, wt, B, C, H, W, workspace,
+                    (hipStream_t)stream, "omni_dibr_wt_f32");
+}
+
+extern "C" int omni_dibr_bwd_f32(const float* grad_recon, const float* recon, const float* wt, const float* img, const float* depth,
+                                 const float* uvgrid, const float* sgrid, int grid_batched, float baseline, int mode, float* grad_img,
+                                 float* grad_depth, int B, int C, int H, int W, void* workspace, omni_stream_t stream)
+{
+    if (mode != DIBR_VERTICAL && mode != DIBR_HORIZONTAL) OMNI_FAIL(OMNI_ERR_INVALID, "omni_dibr_bwd_f32: mode must be 0 (vertical) or 1 (horizontal)");
+    if (grid_batched != 0 && grid_batched != 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_dibr_bwd_f32: grid_batched must be 0 or 1");
+    return dibr_bwd_run(mode, grad_recon, recon, wt, img, depth, nullptr, uvgrid, sgrid, grid_batched, baseline, 8.0f, grad_img, grad_depth,
+                        nullptr, B, C, H, W, workspace, (hipStream_t)stream, "omni_dibr_bwd_f32");
 }

@@ -1,1 +1,4 @@
-"""Host-side mirror of /root/reference/supervision/ (the loss of the depth training scripts)."""
+"""Host-side mirror of the reference's supervision/ (the losses of the depth training scripts and of view synthesis)."""
+from . import direct, photometric, splatting, ssim  # noqa: F401
+from .photometric import PhotometricLossParameters, calculate_loss  # noqa: F401
+from .ssim import ssim_loss  # noqa: F401
