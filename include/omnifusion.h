@@ -36,7 +36,8 @@ enum omni_status {
     OMNI_ERR_UNSUPPORTED = 3
 };
 
-enum omni_layout { OMNI_LAYOUT_BCHWN = 0, OMNI_LAYOUT_BNCHW = 1, OMNI_LAYOUT_BNHWC = 2 };
+enum omni_layout { OMNI_LAYOUT_BCHWN = 0, OMNI_LAYOUT_BNCHW = 1, OMNI_LAYOUT_BNHWC = 2,
+                   OMNI_LAYOUT_BCHNW = 3 /* [B, C, h, N*w]: views side by side along the width, free-view sampling only */ };
 enum omni_dtype { OMNI_F32 = 0, OMNI_F16 = 1 };
 
 typedef void* omni_stream_t;            /* hipStream_t */
@@ -408,6 +409,31 @@ int omni_photometric_loss_f32(const float* pred, const float* gt, const float* m
 int omni_photometric_grad_f32(const float* pred, const float* gt, const float* mask, int mask_c, const float* weights, int weights_c,
                               int B, int C, int H, int W, int window, const float* win, int mode, float alpha,
                               const void* workspace, void* scratch, const float* grad_out, float* grad_pred, omni_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Free-view sampling (csrc/omni_freeview.hip): N perspective views of h x w pixels at per-view yaw theta / pitch phi
+ * (degrees) and one pair of fields of view (hfov: vertical extent, wfov: horizontal extent, each in (0, 180) degrees), and back.
+ * Replaces equi_pers/equi2pers_torch.py:37 `equi2pers` and equi_pers/pers2equi_torch.py:37 `pers2equi` (grid build + F.grid_sample
+ * bilinear / zeros / align_corners=True) with the reference's arithmetic order and quirks.  float32 only.
+ *
+ * omni_freeview_rotations: the rotations of `rotation_matrix` (equi2pers_torch.py:12-34), evaluated in double and rounded once, written
+ * to HOST memory: rot_fwd[N*9] = R2.R1 per view, rot_inv[N*18] = R2^-1 then R1^-1 per view (either may be NULL).  The caller copies them to
+ * the device once per set of angles; the three launches below read them there, allocate nothing, copy nothing and never synchronise
+ * (capturable on one stream).
+ * omni_freeview_equi2pers_f32: erp [B,C,H,W] -> pers [B,N,C,h,w] (OMNI_LAYOUT_BNCHW) or the reference's [B,C,h,N*w] (OMNI_LAYOUT_BCHNW,
+ * equi2pers_torch.py:86-93).
+ * omni_freeview_pers2equi_f32: pers [N,C,h,w] (one image per view) -> erp [N,C,H,W], zero outside the view, and mask [N,1,H,W] uint8.
+ * omni_freeview_merge_f32 (no reference counterpart): pers [B,N,C,h,w] -> erp [B,C,H,W] = sum_v sample_v mask_v / max(sum_v mask_v, 1),
+ * views summed in index order, and count [H,W] uint8 = sum_v mask_v (a function of the geometry only; N <= 255).  Every per-view sample
+ * is the one omni_freeview_pers2equi_f32 computes; the N intermediate ERP images are never written.
+ * pers / erp outputs must be 16-byte aligned, mask / count 4-byte aligned. */
+int omni_freeview_rotations(const float* theta_deg, const float* phi_deg, int N, float* rot_fwd_host /*N*9*/, float* rot_inv_host /*N*18*/);
+int omni_freeview_equi2pers_f32(const float* erp, float* pers, const float* rot_fwd_dev, int B, int C, int H, int W,
+                                int N, int h, int w, float hfov_deg, float wfov_deg, int layout, omni_stream_t stream);
+int omni_freeview_pers2equi_f32(const float* pers, float* erp, unsigned char* mask, const float* rot_inv_dev,
+                                int N, int C, int h, int w, int H, int W, float hfov_deg, float wfov_deg, omni_stream_t stream);
+int omni_freeview_merge_f32(const float* pers, float* erp, unsigned char* count, const float* rot_inv_dev,
+                            int B, int N, int C, int h, int w, int H, int W, float hfov_deg, float wfov_deg, omni_stream_t stream);
 
 #ifdef __cplusplus
 }

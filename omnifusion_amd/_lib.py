@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("OMNI_LIB_VARIANT") or os.path.join(_HERE, "csrc", "li
 LIB_PATH_DEBUG = os.path.join(_HERE, "csrc", "libomnifusion_hip_dbg.so")     # tools/ only: ablation switches + micro-benchmarks
 
 OMNI_OK, OMNI_ERR_INVALID, OMNI_ERR_HIP, OMNI_ERR_UNSUPPORTED = 0, 1, 2, 3
-LAYOUT_BCHWN, LAYOUT_BNCHW, LAYOUT_BNHWC = 0, 1, 2
+LAYOUT_BCHWN, LAYOUT_BNCHW, LAYOUT_BNHWC, LAYOUT_BCHNW = 0, 1, 2, 3
 F32, F16 = 0, 1
 
 _lib = None
@@ -43,6 +43,7 @@ EXPORTS = [
     "omni_splat_render_wt_f32", "omni_dibr_wt_f32", "omni_dibr_bwd_workspace_bytes", "omni_splat_render_bwd_f32", "omni_dibr_bwd_f32",
     "omni_ssim_f32", "omni_photometric_workspace_bytes", "omni_photometric_grad_scratch_bytes", "omni_photometric_loss_f32",
     "omni_photometric_grad_f32",
+    "omni_freeview_rotations", "omni_freeview_equi2pers_f32", "omni_freeview_pers2equi_f32", "omni_freeview_merge_f32",
 ]
 
 
@@ -78,6 +79,10 @@ def load():
     lib.omni_photometric_grad_scratch_bytes.restype = ctypes.c_size_t
     lib.omni_photometric_loss_f32.argtypes = [vp, vp, vp, ci, vp, ci] + [ci] * 5 + [vp, ci, cf] + [vp] * 3
     lib.omni_photometric_grad_f32.argtypes = [vp, vp, vp, ci, vp, ci] + [ci] * 5 + [vp, ci, cf] + [vp] * 5
+    lib.omni_freeview_rotations.argtypes = [vp, vp, ci, vp, vp]
+    lib.omni_freeview_equi2pers_f32.argtypes = [vp] * 3 + [ci] * 7 + [cf, cf, ci, vp]
+    lib.omni_freeview_pers2equi_f32.argtypes = [vp] * 4 + [ci] * 6 + [cf, cf, vp]
+    lib.omni_freeview_merge_f32.argtypes = [vp] * 4 + [ci] * 7 + [cf, cf, vp]
     for name in EXPORTS:
         getattr(lib, name)          # AttributeError here = header/library mismatch
     _lib = lib

@@ -14,6 +14,13 @@ Differentiable w.r.t. depth and image, like the reference's (photometric self-su
 score it with supervision.photometric.calculate_loss, back-propagate into the depth): a hand-written gather backward chains the
 splat's gradient into the depth through the weight and through the displacement, with the reference's rules for its clean-ups and
 clamps.  uvgrid / sgrid / baseline get no gradient.  Where depth == 0 the depth gradient is 0 (the reference: NaN).
+
+Free-view sampling — mirror of the reference's util.py:40-60:
+
+    pers = transform_equi(equi, THETA, PHI, output_h, output_w, select_pers, h_fov, v_fov)        # [bs*select_pers, C, output_h, N*output_w]
+    equi, mask = transform_pers(pers, THETA, PHI, output_h_pano, output_w_pano, h_fov, v_fov)    # [N,C,H,W], [N,1,1,H,W]
+
+Same names, arguments and shapes; they run equi_pers.equi2pers_torch / pers2equi_torch (csrc/omni_freeview.hip).
 """
 import ctypes
 
@@ -90,3 +97,17 @@ def dibr_vertical(depth, image, uvgrid, sgrid, baseline):
 
 def dibr_horizontal(depth, image, uvgrid, sgrid, baseline):
     return _dibr(depth, image, uvgrid, sgrid, baseline, HORIZONTAL)[0]
+
+
+def transform_equi(equi, THETA, PHI, output_h, output_w, select_pers, h_fov, v_fov):
+    """The reference repeats every panorama select_pers times before sampling; the copies are equal, so the views are sampled once
+    and the result is repeated instead."""
+    from .equi_pers.equi2pers_torch import equi2pers
+    pers = equi2pers(equi, h_fov, v_fov, THETA, PHI, output_h, output_w)
+    return pers.repeat_interleave(int(select_pers), dim=0)
+
+
+def transform_pers(pers, THETA, PHI, output_h_pano, output_w_pano, h_fov, v_fov):
+    from .equi_pers.pers2equi_torch import pers2equi
+    equi, mask = pers2equi(pers, h_fov, v_fov, THETA, PHI, output_h_pano, output_w_pano)
+    return equi, mask.unsqueeze(1)
