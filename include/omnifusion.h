@@ -435,6 +435,24 @@ int omni_freeview_pers2equi_f32(const float* pers, float* erp, unsigned char* ma
 int omni_freeview_merge_f32(const float* pers, float* erp, unsigned char* count, const float* rot_inv_dev,
                             int B, int N, int C, int h, int w, int H, int W, float hfov_deg, float wfov_deg, omni_stream_t stream);
 
+/* The backwards of the three launches above (csrc/omni_freeview_bwd.hip, DESIGN.md §12 "Backward"): each sends w_k * g through the
+ * forward's own tap set, summed as in §11 — every contribution rounded once to a 64-bit fixed-point integer (scale from the largest
+ * finite |g| of the item: a batch item, or a view for pers2equi) and added with an integer atomic, so the bits do not depend on the
+ * order of arrival, the batch split or the stream.  Four launches on the caller's stream, no allocation, no host synchronisation.
+ * omni_freeview_equi2pers_bwd_f32: grad_pers (the layout of the forward's output) -> grad_erp [B,C,H,W], summed over the N views.
+ * omni_freeview_pers2equi_bwd_f32: grad_erp [N,C,H,W] -> grad_pers [N,C,h,w]; an ERP pixel outside the view's mask contributes nothing.
+ * omni_freeview_merge_bwd_f32: grad_erp [B,C,H,W] -> grad_pers [B,N,C,h,w], once per covering view, divided by max(count, 1).
+ * A non-finite g makes NaN exactly the gradient elements it reaches through a corner that lies on the image.
+ * `ws`: omni_freeview_bwd_workspace_bytes(op, items, C, Ht, Wt) bytes, 16-byte aligned, any content; op 0 / 1 / 2 = the three
+ * functions in this order, items = the number of gradient images written (B | N | B * N), Ht x Wt their size; 0 for invalid arguments. */
+size_t omni_freeview_bwd_workspace_bytes(int op, int items, int C, int Ht, int Wt);
+int omni_freeview_equi2pers_bwd_f32(const float* grad_pers, float* grad_erp, const float* rot_fwd_dev, int B, int C, int H, int W,
+                                    int N, int h, int w, float hfov_deg, float wfov_deg, int layout, void* ws, omni_stream_t stream);
+int omni_freeview_pers2equi_bwd_f32(const float* grad_erp, float* grad_pers, const float* rot_inv_dev, int N, int C, int h, int w,
+                                    int H, int W, float hfov_deg, float wfov_deg, void* ws, omni_stream_t stream);
+int omni_freeview_merge_bwd_f32(const float* grad_erp, float* grad_pers, const float* rot_inv_dev, int B, int N, int C, int h, int w,
+                                int H, int W, float hfov_deg, float wfov_deg, void* ws, omni_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,7 @@ EXPORTS = [
     "omni_ssim_f32", "omni_photometric_workspace_bytes", "omni_photometric_grad_scratch_bytes", "omni_photometric_loss_f32",
     "omni_photometric_grad_f32",
     "omni_freeview_rotations", "omni_freeview_equi2pers_f32", "omni_freeview_pers2equi_f32", "omni_freeview_merge_f32",
+    "omni_freeview_bwd_workspace_bytes", "omni_freeview_equi2pers_bwd_f32", "omni_freeview_pers2equi_bwd_f32", "omni_freeview_merge_bwd_f32",
 ]
 
 
@@ -83,6 +84,11 @@ def load():
     lib.omni_freeview_equi2pers_f32.argtypes = [vp] * 3 + [ci] * 7 + [cf, cf, ci, vp]
     lib.omni_freeview_pers2equi_f32.argtypes = [vp] * 4 + [ci] * 6 + [cf, cf, vp]
     lib.omni_freeview_merge_f32.argtypes = [vp] * 4 + [ci] * 7 + [cf, cf, vp]
+    lib.omni_freeview_bwd_workspace_bytes.restype = ctypes.c_size_t
+    lib.omni_freeview_bwd_workspace_bytes.argtypes = [ci] * 5
+    lib.omni_freeview_equi2pers_bwd_f32.argtypes = [vp] * 3 + [ci] * 7 + [cf, cf, ci, vp, vp]
+    lib.omni_freeview_pers2equi_bwd_f32.argtypes = [vp] * 3 + [ci] * 6 + [cf, cf, vp, vp]
+    lib.omni_freeview_merge_bwd_f32.argtypes = [vp] * 3 + [ci] * 7 + [cf, cf, vp, vp]
     for name in EXPORTS:
         getattr(lib, name)          # AttributeError here = header/library mismatch
     _lib = lib

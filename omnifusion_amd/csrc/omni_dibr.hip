@@ -21,6 +21,7 @@
 // not finite poisons them for recon only.  The reference propagates inf / NaN through its float sums instead.
 // Sources whose coordinates are not finite are dropped (render only: the DIBR modes clean their coordinates as the reference does).
 #include "omni_internal.h"
+#include "omni_fixedpoint.h"   // finite, dibr_exponent, pow2f, fixq, dibr_zero_kernel, block_reduce
 
 namespace {
 
@@ -30,21 +31,6 @@ __device__ __forceinline__ float dibr_weight(float depth, float max_depth)
 {
     return 1.0f / expf(2.0f * depth / max_depth);                   // splatting.py:68-70, IEEE division
 }
-
-__device__ __forceinline__ bool finite(float x) { return fabsf(x) <= 3.402823466e38f; }
-
-// e = ceil(log2 m) of the per-item maximum (bits of a non-negative float), clamped so that both 2^s and 2^-s are normal floats
-__device__ __forceinline__ int dibr_exponent(unsigned bits)
-{
-    const float m = __uint_as_float(bits);
-    if (!(m > 0.0f)) return 0;
-    int k;
-    const float f = frexpf(m, &k);                                  // m = f * 2^k, f in [0.5, 1)
-    const int e = (f == 0.5f) ? k - 1 : k;
-    return e < -60 ? -60 : e;
-}
-
-__device__ __forceinline__ float pow2f(int s) { return __int_as_float((127 + s) << 23); }     // s in [-126, 127]
 
 // ---------------------------------------------------------------- pass 1: per-item scale
 __global__ __launch_bounds__(256) void dibr_max_kernel(const float* __restrict__ img, const float* __restrict__ depth, float max_depth,
@@ -70,11 +56,6 @@ __global__ __launch_bounds__(256) void dibr_max_kernel(const float* __restrict__
         atomicMax(maxbits + b, __float_as_uint(fmaxf(fmaxf(part[0][0], part[0][1]), fmaxf(part[0][2], part[0][3]))));
         atomicMax(maxbits + B + b, __float_as_uint(fmaxf(fmaxf(part[1][0], part[1][1]), fmaxf(part[1][2], part[1][3]))));
     }
-}
-
-__global__ __launch_bounds__(256) void dibr_zero_kernel(uint4* __restrict__ p, size_t n16)
-{
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) p[i] = make_uint4(0u, 0u, 0u, 0u);
 }
 
 // ---------------------------------------------------------------- pass 2: the splat
@@ -161,21 +142,6 @@ __device__ __forceinline__ Src dibr_source(const float* __restrict__ depth, cons
     }
     r.w = dibr_weight(d, max_depth);
     return r;
-}
-
-__device__ __forceinline__ long long fixq(float x, float scale) { return (long long)rintf(x * scale); }   // x * 2^s is exact; one rounding
-
-__device__ __forceinline__ int block_reduce(int v, bool is_max, int* red)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(v, o); v = is_max ? max(v, t) : min(v, t); }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = red[0];
-#pragma unroll
-    for (int k = 1; k < 4; ++k) v = is_max ? max(v, red[k]) : min(v, red[k]);
-    return v;
 }
 
 template <int MODE>

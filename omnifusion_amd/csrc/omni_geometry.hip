@@ -68,6 +68,7 @@ const OptName kOpts[] = {
     {"p2e_walk", "OMNI_P2E_WALK", &OmniOptions::p2e_walk, 1},
     {"p2e_tile8", "OMNI_P2E_TILE8", &OmniOptions::p2e_tile8, 1},
     {"p2e_store", "OMNI_P2E_STORE", &OmniOptions::p2e_store, 1},
+    {"fv_bwd_lds", "OMNI_FV_BWD_LDS", &OmniOptions::fv_bwd_lds, 1},
     {"geom_cache_max", "OMNI_GEOM_CACHE_MAX", &OmniOptions::geom_cache_max, 16},
 };
 }  // namespace

@@ -70,6 +70,7 @@ struct OmniOptions {
     int bwd_chunk;        // OMNI_BWD_CHUNK      blocks per XCD chunk of the backward gathers (0: 16; 4 .. 64 measured within 3 %)
     int bwd_lmax;         // OMNI_BWD_LMAX       rows with more entries than this go to the long-row list (0: OMNI_SP_LMAX; read when a table is built)
     int bwd_table_mb;     // OMNI_BWD_TABLE_MB   largest sparse-matrix table of a backward operator kept per geometry, MiB (default 1024; a geometry past it keeps the tile kernels)
+    int fv_bwd_lds;       // OMNI_FV_BWD_LDS     1 (default): the free-view backward scatters sum a block's target box in LDS where it fits | 0: global atomics only (same bits)
     int geom_cache_max;   // OMNI_GEOM_CACHE_MAX geometry handles kept per process (LRU), default 16
 };
 OmniOptions& omni_options();

@@ -1,5 +1,7 @@
 """Shared plumbing of the free-view samplers (equi2pers_torch.py, pers2equi_torch.py, views_to_erp): argument checks, the per-view
-rotation tables and the launches of csrc/omni_freeview.hip.  Nothing here computes a sample: there is no CPU / PyTorch path.
+rotation tables and the launches of csrc/omni_freeview.hip and csrc/omni_freeview_bwd.hip.  Nothing here computes a sample: there is
+no CPU / PyTorch path.  The plain mirrors refuse an input that requires grad; equi_pers/differentiable.py holds the autograd functions
+(same launches, allow_grad=True, and the launch_*_bwd functions below).
 
 The two rotation tables of a set of angles (forward R2.R1, inverse R2^-1 | R1^-1; omni_freeview_rotations, float64 rounded once) are
 built on the host and copied to the device the first time a (theta, phi, device) is seen, then kept (the last 64 sets).  A later call
@@ -21,8 +23,11 @@ def _p(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
-def check_image(name, t, ndim=4):
-    """A float32 tensor on the GPU that does not require grad (the free-view operators have no backward)."""
+NO_BACKWARD = "the plain free-view mirrors have no backward; the differentiable operators are omnifusion_amd.equi_pers.differentiable"
+
+
+def check_image(name, t, ndim=4, allow_grad=False):
+    """A float32 tensor on the GPU; unless allow_grad, one that does not require grad (the plain mirrors have no backward)."""
     if not isinstance(t, torch.Tensor):
         raise ValueError(f"{name} must be a tensor")
     if not t.is_cuda:
@@ -31,8 +36,8 @@ def check_image(name, t, ndim=4):
         raise ValueError(f"{name} must be float32 (got {t.dtype}); float16 storage is not implemented for free-view sampling")
     if t.dim() != ndim:
         raise ValueError(f"{name} must have {ndim} dimensions (got shape {tuple(t.shape)})")
-    if t.requires_grad and torch.is_grad_enabled():
-        raise NotImplementedError(f"{name} requires grad: free-view sampling has no backward")
+    if not allow_grad and t.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError(f"{name} requires grad: {NO_BACKWARD}")
     if t.numel() == 0:
         raise ValueError(f"{name} is empty")
 
@@ -51,7 +56,7 @@ def angles(theta, phi):
     out = []
     for name, a in (("theta", theta), ("phi", phi)):
         if isinstance(a, torch.Tensor) and a.requires_grad:
-            raise NotImplementedError(f"{name} requires grad: free-view sampling has no backward")
+            raise NotImplementedError(f"{name} requires grad: free-view sampling has no gradient with respect to the angles")
         a = torch.as_tensor(a).detach().to("cpu", torch.float32).reshape(-1).contiguous()
         if not bool(torch.isfinite(a).all()):
             raise ValueError(f"{name} must be finite")
@@ -91,8 +96,8 @@ def tables(theta, phi, device):
     return hit
 
 
-def launch_equi2pers(equi_img, hFOV, wFOV, theta, phi, h, w, layout):
-    check_image("equi_img", equi_img)
+def launch_equi2pers(equi_img, hFOV, wFOV, theta, phi, h, w, layout, allow_grad=False):
+    check_image("equi_img", equi_img, allow_grad=allow_grad)
     hFOV, wFOV, h, w = check_view(hFOV, wFOV, h, w)
     B, C, H, W = equi_img.shape
     check_view(hFOV, wFOV, H, W)
@@ -107,9 +112,9 @@ def launch_equi2pers(equi_img, hFOV, wFOV, theta, phi, h, w, layout):
     return pers
 
 
-def launch_pers2equi(pers_img, hFOV, wFOV, theta, phi, H, W):
+def launch_pers2equi(pers_img, hFOV, wFOV, theta, phi, H, W, allow_grad=False):
     """-> (erp [N,C,H,W] float32, mask [N,1,H,W] uint8)"""
-    check_image("pers_img", pers_img)
+    check_image("pers_img", pers_img, allow_grad=allow_grad)
     hFOV, wFOV, H, W = check_view(hFOV, wFOV, H, W)
     N, C, h, w = pers_img.shape
     check_view(hFOV, wFOV, h, w)
@@ -125,7 +130,7 @@ def launch_pers2equi(pers_img, hFOV, wFOV, theta, phi, H, W):
     return erp, mask
 
 
-def views_to_erp(pers, hFOV, wFOV, theta, phi, H, W):
+def views_to_erp(pers, hFOV, wFOV, theta, phi, H, W, allow_grad=False):
     """N views merged onto one panorama per batch item (no reference counterpart).
 
         erp, count = views_to_erp(pers, hFOV, wFOV, theta, phi, H, W)      # pers [B,N,C,h,w] -> erp [B,C,H,W], count [1,1,H,W] uint8
@@ -133,7 +138,7 @@ def views_to_erp(pers, hFOV, wFOV, theta, phi, H, W):
     erp = sum_v sample_v mask_v / max(sum_v mask_v, 1) with the per-view samples and masks of pers2equi_torch.pers2equi, views summed in
     index order; count = sum_v mask_v, the number of views that cover a pixel (the same for every batch item).  One kernel; the N
     per-view panoramas are never written."""
-    check_image("pers", pers, ndim=5)
+    check_image("pers", pers, ndim=5, allow_grad=allow_grad)
     hFOV, wFOV, H, W = check_view(hFOV, wFOV, H, W)
     B, N, C, h, w = pers.shape
     check_view(hFOV, wFOV, h, w)
@@ -149,6 +154,53 @@ def views_to_erp(pers, hFOV, wFOV, theta, phi, H, W):
         _lib.check(_lib.load().omni_freeview_merge_f32(_p(pers), _p(erp), _p(count), _p(inv), B, N, C, h, w, H, W, hFOV, wFOV,
                                                        _lib.stream_of(pers)), "freeview views_to_erp")
     return erp, count
+
+
+# ---------------------------------------------------------------------------------------------------------------- backward launches
+# Each takes the upstream gradient of the forward's output (float32, contiguous, on the device), allocates the gradient and the workspace
+# as torch tensors and launches on the current stream; the rotation tables are the forward's (cached: nothing is uploaded).
+def _bwd(op, grad_out, shape, images, call):
+    lib = _lib.load()
+    grad_in = torch.empty(shape, dtype=torch.float32, device=grad_out.device)
+    nbytes = lib.omni_freeview_bwd_workspace_bytes(op, images, shape[-3], shape[-2], shape[-1])
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=grad_out.device)
+    with torch.cuda.device(grad_out.device):
+        call(lib, grad_in, ws, _lib.stream_of(grad_out))
+    return grad_in
+
+
+def launch_equi2pers_bwd(grad_pers, erp_shape, hFOV, wFOV, theta, phi, h, w, layout):
+    """grad_pers ([B,N,C,h,w] or [B,C,h,N*w], as `layout`) -> grad_equi_img [B,C,H,W]"""
+    B, C, H, W = erp_shape
+    fwd, _ = tables(theta, phi, grad_pers.device)
+    N = fwd.shape[0]
+
+    def call(lib, grad_erp, ws, stream):
+        _lib.check(lib.omni_freeview_equi2pers_bwd_f32(_p(grad_pers), _p(grad_erp), _p(fwd), B, C, H, W, N, h, w, hFOV, wFOV, layout, _p(ws), stream),
+                   "freeview equi2pers backward")
+    return _bwd(0, grad_pers, (B, C, H, W), B, call)
+
+
+def launch_pers2equi_bwd(grad_erp, pers_shape, hFOV, wFOV, theta, phi, H, W):
+    """grad_erp [N,C,H,W] -> grad_pers_img [N,C,h,w]"""
+    N, C, h, w = pers_shape
+    _, inv = tables(theta, phi, grad_erp.device)
+
+    def call(lib, grad_pers, ws, stream):
+        _lib.check(lib.omni_freeview_pers2equi_bwd_f32(_p(grad_erp), _p(grad_pers), _p(inv), N, C, h, w, H, W, hFOV, wFOV, _p(ws), stream),
+                   "freeview pers2equi backward")
+    return _bwd(1, grad_erp, (N, C, h, w), N, call)
+
+
+def launch_views_to_erp_bwd(grad_erp, pers_shape, hFOV, wFOV, theta, phi, H, W):
+    """grad_erp [B,C,H,W] -> grad_pers [B,N,C,h,w]"""
+    B, N, C, h, w = pers_shape
+    _, inv = tables(theta, phi, grad_erp.device)
+
+    def call(lib, grad_pers, ws, stream):
+        _lib.check(lib.omni_freeview_merge_bwd_f32(_p(grad_erp), _p(grad_pers), _p(inv), B, N, C, h, w, H, W, hFOV, wFOV, _p(ws), stream),
+                   "freeview views_to_erp backward")
+    return _bwd(2, grad_erp, (B, N, C, h, w), B * N, call)
 
 
 def cubemap_views():

@@ -9,8 +9,8 @@ this one, do not).  Bilinear, zero padding, align_corners=True; the reference's 
 by (W - 1) / W and does not wrap across the +-180 degree seam.
 
 One kernel of libomnifusion_hip.so (csrc/omni_freeview.hip) computes the coordinates of a view pixel once and samples every image
-plane with them; no grid tensor exists.  float32 on the GPU only, no backward (NotImplementedError if the image requires grad), no CPU
-path.  `equi2pers_planar` returns the same samples as [B,N,C,output_h,output_w].
+plane with them; no grid tensor exists.  float32 on the GPU only, no CPU path.  These plain mirrors have no backward
+(NotImplementedError if the image requires grad): the differentiable operators are equi_pers.differentiable.  `equi2pers_planar` returns the same samples as [B,N,C,output_h,output_w].
 """
 from .. import _lib
 from . import _freeview

@@ -8,8 +8,8 @@ fields of view hFOV (along the height) and wFOV (along the width), is put back o
 the pixel (strictly inside the frustum and in front of the camera), and sample_erp is exactly 0 elsewhere.  Bilinear, zero padding,
 align_corners=True on the reference's coordinate (y + w_len) / (2 w_len) * w.
 
-One kernel of libomnifusion_hip.so (csrc/omni_freeview.hip); float32 on the GPU only, no backward (NotImplementedError if the views
-require grad), no CPU path.  `equi_pers.views_to_erp` merges the views onto ONE panorama without writing the N intermediates.
+One kernel of libomnifusion_hip.so (csrc/omni_freeview.hip); float32 on the GPU only, no CPU path.  This plain mirror has no backward
+(NotImplementedError if the views require grad): the differentiable operators are equi_pers.differentiable.  `equi_pers.views_to_erp` merges the views onto ONE panorama without writing the N intermediates.
 """
 import torch
 

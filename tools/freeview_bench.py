@@ -3,6 +3,11 @@ the reference's functions (equi_pers/equi2pers_torch.py:37, pers2equi_torch.py:3
 call + F.grid_sample), both on the same GPU in the same run, by device events over a warm loop.
 
     python tools/freeview_bench.py [--iters 20] [--out profiles/r09a_freeview.json] [--quick]
+    python tools/freeview_bench.py --bwd [--iters 20] [--out profiles/r10a_freeview_bwd.json] [--quick]
+
+--bwd: the backwards of equi_pers.differentiable (csrc/omni_freeview_bwd.hip) against the autograd of the same restatement: for each
+operator forward and forward + backward are timed (the input requires grad, `out.backward(G)`), backward = their difference; the HIP
+backward also with the option fv_bwd_lds = 0 (global atomics only).
 
 Shapes: B = 8, C = 3, 512 x 1024 <-> 6 cube faces of 256^2, and B = 1, C = 3, 2048 x 4096 <-> 6 x 1024^2.  pers2equi has no batch
 dimension (one image per view): the batch rides in its channels (B * C planes per view).  views_to_erp is also timed against
@@ -102,13 +107,79 @@ def timeit(fn, iters):
     return e0.elapsed_time(e1) / iters * 1e-3
 
 
+def main_bwd(a):
+    from omnifusion_amd import _lib
+    from omnifusion_amd.build import source_hash
+    from omnifusion_amd.equi_pers import cubemap_views
+    from omnifusion_amd.equi_pers import differentiable as fv
+    cases = [(8, 3, 512, 1024, 256)] if a.quick else [(8, 3, 512, 1024, 256), (1, 3, 2048, 4096, 1024)]
+    iters = 3 if a.quick else a.iters
+    theta, phi = cubemap_views()
+    theta_d, phi_d = theta.to(DEV), phi.to(DEV)
+    N, fov = 6, 90.0
+    rows = []
+    for B, C, H, W, P in cases:
+        g = torch.Generator(device=DEV).manual_seed(1)
+        erp = torch.rand(B, C, H, W, device=DEV, generator=g)
+        views = torch.rand(B, N, C, P, P, device=DEV, generator=g)
+        folded = views.permute(1, 0, 2, 3, 4).reshape(N, B * C, P, P).contiguous()          # pers2equi's [N, planes, h, w]
+        legs = {
+            "equi2pers": (lambda x: fv.equi2pers_planar(x, fov, fov, theta, phi, P, P),
+                          lambda x: torch_equi2pers(x, fov, fov, theta_d, phi_d, P, P).view(B, C, P, N, P).permute(0, 3, 1, 2, 4), erp),
+            "pers2equi": (lambda x: fv.pers2equi(x, fov, fov, theta, phi, H, W)[0], lambda x: torch_pers2equi(x, fov, fov, theta_d, phi_d, H, W)[0], folded),
+            "views_to_erp": (lambda x: fv.views_to_erp(x, fov, fov, theta, phi, H, W)[0],
+                             lambda x: reduce_views(*torch_pers2equi(x.permute(1, 0, 2, 3, 4).reshape(N, B * C, P, P), fov, fov, theta_d, phi_d, H, W), B, C), views),
+        }
+        for name, (hip, ref, x0) in legs.items():
+            x = x0.clone().requires_grad_(True)
+            with torch.no_grad():
+                G = torch.rand(hip(x0).shape, device=DEV, generator=g) * 2 - 1
+
+            def both(f):
+                x.grad = None
+                f(x).backward(G)
+                return x.grad
+
+            def fwd(f):
+                with torch.no_grad():
+                    return f(x0)
+            gh, gt = both(hip).clone(), both(ref).clone()
+            rel = float((gh - gt).abs().max() / gt.abs().max())
+            t = {}
+            for tag, f, n in (("hip", hip, iters), ("torch", ref, max(2, iters // 4))):
+                t[tag + "_fwd"] = timeit(lambda: fwd(f), n)
+                t[tag + "_both"] = timeit(lambda: both(f), n)
+            _lib.set_option("fv_bwd_lds", 0)
+            try:
+                same = bool(torch.equal(both(hip), gh))
+                t["hip_both_global"] = timeit(lambda: both(hip), iters)
+            finally:
+                _lib.set_option("fv_bwd_lds", 1)
+            us = lambda v: round(v * 1e6, 1)
+            hb, tb = t["hip_both"] - t["hip_fwd"], t["torch_both"] - t["torch_fwd"]
+            row = dict(op=name, B=B, C=C, H=H, W=W, views=N, view_size=P, hip_fwd_us=us(t["hip_fwd"]), hip_fwd_bwd_us=us(t["hip_both"]), hip_bwd_us=us(hb),
+                       hip_bwd_global_atomics_only_us=us(t["hip_both_global"] - t["hip_fwd"]), global_only_same_bits=same,
+                       torch_eager_fwd_us=us(t["torch_fwd"]), torch_eager_fwd_bwd_us=us(t["torch_both"]), torch_eager_bwd_us=us(tb),
+                       speedup_bwd=round(tb / hb, 2), speedup_fwd_bwd=round(t["torch_both"] / t["hip_both"], 2), max_rel_diff_vs_torch=rel)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    res = dict(build=source_hash(), device=torch.cuda.get_device_name(0), iters=iters, rows=rows)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--bwd", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "freeview_bench measures on an MI355X; there is no CPU timing"
+    if a.bwd:
+        return main_bwd(a)
     from omnifusion_amd.build import source_hash
     from omnifusion_amd.equi_pers import _freeview, cubemap_views, views_to_erp
     from omnifusion_amd.equi_pers.equi2pers_torch import equi2pers_planar
