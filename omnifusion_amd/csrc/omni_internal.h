@@ -132,7 +132,7 @@ struct omni_geometry {
     // bilinear taps inside the patch (omni_pers2equi.hip); index 0: 4-byte elements, 1: 2-byte elements (16-byte chunk alignment)
     struct P2ETiles { uint2* ent; int max_chunks; int max_cand; int ok; int sum_chunks; uint2* ord; int nslots; unsigned char* walk; int nslots_walk; } p2e_tiles[4];   // ord: the table in block order (+ tile id), what the kernels read; [2], [3]: the 8-row tile sets of the one-plane walk kernel (walk table only)
     int p2e_tx, p2e_ty;            // tiles per ERP row / column
-    // pers2equi backward by gathers (omni_pers2equi.hip): per (patch, 4 x 32 patch tile) the ERP box of the pixels whose taps touch it
+    // pers2equi backward by gathers (omni_pers2equi_bwd.hip): per (patch, 4 x 32 patch tile) the ERP box of the pixels whose taps touch it
     // (columns relative to the patch's centre column: the box may cross the +-pi seam), and 1 / (L1 norm of the tap weights) per ERP pixel
     int4* p2e_bwd_box; float* p2e_rden; int p2e_btx, p2e_bty, p2e_bwd_ok;
     int* p2e_bwd_ids; int p2e_bwd_nsmall, p2e_bwd_nbig;   // tile ids: [0, nsmall) boxes of <= 2048 pixels (one wave each), then the big ones (1024 threads each)
@@ -148,7 +148,7 @@ struct omni_geometry {
     int e2p_nfb;
     int e2p_ts;                    // equi2pers: tile side (32 or 16 samples) chosen so that the footprints fit the LDS box
     float2* e2p_ixy;               // equi2pers: clamped sampling coordinates (ix, iy) of every patch sample [N][ph][pw]
-    // equi2pers backward by gathers (omni_equi2pers.hip): per (4 x 32 ERP tile, patch) the box of the patch samples whose taps touch the tile
+    // equi2pers backward by gathers (omni_equi2pers_bwd.hip): per (4 x 32 ERP tile, patch) the box of the patch samples whose taps touch the tile
     int4* e2p_bwd_box; int* e2p_bwd_ids; int e2p_bwd_nsmall, e2p_bwd_nbig, e2p_gtx, e2p_gty, e2p_bwd_ok;
     // the backward operators as constant sparse matrices (omni_spgather.h): one row per OUTPUT element, entries (source index, weight)
     OmniSpTable p2e_sp, e2p_sp;
@@ -163,16 +163,16 @@ struct omni_geometry {
 // implemented in omni_geometry.hip
 int omni_geometry_lookup(const omni_geometry** out, int nrows, float fov_h, float fov_w,
                          int ph, int pw, int H, int W, hipStream_t stream);
-// implemented in omni_pers2equi.hip: fills g->cand on `stream`
+// implemented in omni_p2e_tables.hip: fills g->cand on `stream`
 int omni_p2e_build_candidates(omni_geometry* g, hipStream_t stream);
-// implemented in omni_pers2equi.hip: fills g->p2e_tiles (needs g->cand)
+// implemented in omni_p2e_tables.hip: fills g->p2e_tiles (needs g->cand)
 int omni_p2e_build_tiles(omni_geometry* g, hipStream_t stream);
-// implemented in omni_pers2equi.hip: fills g->p2e_bwd_box / p2e_rden (needs g->cand)
+// implemented in omni_pers2equi_bwd.hip: fills g->p2e_bwd_box / p2e_rden (needs g->cand)
 int omni_p2e_build_bwd(omni_geometry* g, hipStream_t stream);
-// implemented in omni_equi2pers.hip: fills g->e2p_ixy, g->e2p_fb_tiles / e2p_nfb, then g->e2p_boxes
+// implemented in omni_e2p_tables.hip: fills g->e2p_ixy, g->e2p_fb_tiles / e2p_nfb, then g->e2p_boxes
 int omni_e2p_build_tileflags(omni_geometry* g, hipStream_t stream);
 int omni_e2p_build_boxes(omni_geometry* g, hipStream_t stream);
-int omni_e2p_build_bwd(omni_geometry* g, hipStream_t stream);        // fills g->e2p_bwd_* (needs g->e2p_ixy)
+int omni_e2p_build_bwd(omni_geometry* g, hipStream_t stream);        // omni_equi2pers_bwd.hip: fills g->e2p_bwd_* (needs g->e2p_ixy)
 
 // ---------------------------------------------------------------- storage types
 template <typename T> struct Store;

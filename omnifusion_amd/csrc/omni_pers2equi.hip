@@ -23,151 +23,12 @@
 // host:  cos(lon-l0) = cos lon cos l0 + sin lon sin l0  etc.  No transcendental in the kernel.
 //
 // HBM-bound: algorithmic bytes B*C*(ph*pw*N + H*W)*sizeof(T); tables read: 8 B per tile.
-#include <stdio.h>
-#include <string.h>
-#include <utility>
-#include <vector>
-#include <algorithm>
-#include "omni_internal.h"
-#include "omni_spgather.h"
+//
+// This unit: the C entry points, the launchers and the blend kernels (direct gathers, p2e_lds_kernel, p2e_walk_kernel).  omni_p2e_common.h: argument
+// block, tap geometry, table layout | omni_p2e_tables.hip: candidate masks and tile tables | omni_pers2equi_bwd.hip: the backward.
+#include "omni_p2e_common.h"
 
 namespace {
-
-struct P2EArgs {
-    const void* pers; const void* pers2;      // pers2: confidence tensor for the fused K11 blend
-    void* erp;
-    const float2* row_trig; const float2* col_trig;
-    const unsigned long long* cand;
-    int B, C, H, W, ph, pw, ntx;
-    long long sB, sC, sN, sY, sX;              // element strides of the patch tensor
-    float kx, ky;                              // 1/(FOVx*PI), 1/(FOVy*PI_2)   (:115-116)
-    float half_h, half_w;                      // 0.5*height, 0.5*width        (:122-123)
-    int store_nt;                              // 1: non-temporal ERP stores (option p2e_store)
-    int dbg;                                   // debug build only (OMNI_P2E_DBG ablation bits): 1 no tap geometry, 2 no LDS tap reads, 4 no DMA, 8 no stores
-    long long* trace;                          // debug build, bit 16: per-block time stamps (omni_debug_set_trace)
-    PatchTab tab;
-};
-
-struct Taps { int x0, x1, y0, y1; float wa, wb, wc, wd; };
-
-
-// pers2equi_v3.py:112-152 + :191 for one (pixel, patch).  Returns the validity mask.
-// Split in two so that the pixels of one ERP column (same lon) share cos/sin(lon - l0); every kernel (candidate masks, tile
-// boxes, gather blend, LDS blend) goes through these SAME two functions, so all of them see the same bits.
-__device__ __forceinline__ void p2e_lon(const P2EArgs& a, int n, float slon, float clon, float& cd, float& sd)
-{
-    const float sl0 = a.tab.slam[n], cl0 = a.tab.clam[n];
-    cd = clon * cl0 + slon * sl0;                                   // cos(lon - l0)
-    sd = slon * cl0 - clon * sl0;                                   // sin(lon - l0)
-}
-// the float part of the taps (everything but the integer conversions): the four weights and the tap coordinates as floats
-struct TapsF { float x0f, x1f, y0f, y1f; float wa, wb, wc, wd; };
-__device__ __forceinline__ bool p2e_taps_f(const P2EArgs& a, float sp, float cp, float slat, float clat, float cd, float sd, TapsF& t)
-{
-    const float cos_c = sp * slat + cp * clat * cd;                 // :112
-    // :113-114 divide twice by cos_c; one reciprocal and two products differ from that by <= 2 ulp of X, Y (a
-    // validity / floor predicate can flip only where the reference's own coordinate is within round-off of the step)
-    float rc = __builtin_amdgcn_rcpf(cos_c);                       // 1 ulp ...
-    rc = fmaf(fmaf(-cos_c, rc, 1.0f), rc, rc);                      // ... + one Newton step: ~0.5 ulp (an IEEE division costs 11 instructions)
-    float nx = (clat * sd) * rc;                                    // :113
-    float ny = (cp * slat - sp * clat * cd) * rc;                   // :114
-    nx = nx * a.kx;                                                 // :115
-    ny = ny * a.ky;                                                 // :116
-    const float X = (nx + 1.0f) * a.half_h;                         // :122 (sic)
-    const float Y = (ny + 1.0f) * a.half_w;                         // :123 (sic)
-    const float fw = (float)a.pw, fh = (float)a.ph;
-    const bool valid = (X < fw) && (X > 0.0f) && (Y < fh) && (Y > 0.0f) && (cos_c > 0.0f);   // :118,126-127
-    const float fx = floorf(X), fy = floorf(Y);                     // :129-132
-    // :134-137 clamp x0, x1, y0, y1 to [0, P-1].  A VALID pixel has 0 < X < P, so floor(X) is already in range and only the +1
-    // taps can leave it (at the far edge); for an invalid pixel every weight is zeroed below and no kernel uses its indices.
-    const float x0f = fx, x1f = fminf(fx + 1.0f, fw - 1.0f);
-    const float y0f = fy, y1f = fminf(fy + 1.0f, fh - 1.0f);
-    // :144-147 multiply by mask: the mask goes onto the two x factors (two selects instead of four; for a valid pixel the products are the
-    // reference's, for an invalid one they are 0, -0 or — where Y is not finite — NaN, and the threshold below turns all three into 0)
-    const float hx1 = valid ? x1f - X : 0.0f, hx0 = valid ? X - x0f : 0.0f;
-    const float wa = hx1 * (y1f - Y);                               // :139  tap (y0,x0)
-    const float wb = hx1 * (Y - y0f);                               // :140  tap (y1,x0)
-    const float wc = hx0 * (y1f - Y);                               // :141  tap (y0,x1)
-    const float wd = hx0 * (Y - y0f);                               // :142  tap (y1,x1)
-    // :191 zero everything <= 1e-5 (a NaN compares false)
-    t.wa = wa > 1e-5f ? wa : 0.0f;
-    t.wb = wb > 1e-5f ? wb : 0.0f;
-    t.wc = wc > 1e-5f ? wc : 0.0f;
-    t.wd = wd > 1e-5f ? wd : 0.0f;
-    // Right patch edge (x1 == x0 == pw-1, X in [pw-1, pw)): the x0 taps carry the factor (x1 - X) <= 0, so wa and wb are already
-    // exactly 0 — except in the corner cell, where y is clamped too and wa = (x1-X)(y1-Y) > 0.  There all four taps are the same
-    // pixel; its weight is moved to the (y1, x1) tap (v*wa + v*wd -> v*(wa + wd): one rounding), so that EVERY kernel may assume
-    // "x1 == x0  =>  wa == wb == 0" and read the tap pair one column to the left without a select.
-    const bool xedge = x1f == x0f;
-    t.wd = xedge ? t.wd + t.wa : t.wd;
-    t.wa = xedge ? 0.0f : t.wa;
-    t.x0f = x0f; t.x1f = x1f; t.y0f = y0f; t.y1f = y1f;
-    return valid;
-}
-__device__ __forceinline__ bool p2e_taps_core(const P2EArgs& a, float sp, float cp, float slat, float clat, float cd, float sd, Taps& t)
-{
-    TapsF f;
-    const bool valid = p2e_taps_f(a, sp, cp, slat, clat, cd, sd, f);
-    t.wa = f.wa; t.wb = f.wb; t.wc = f.wc; t.wd = f.wd;
-    t.x0 = (int)f.x0f; t.x1 = (int)f.x1f; t.y0 = (int)f.y0f; t.y1 = (int)f.y1f;
-    return valid;
-}
-// The taps as the LDS kernels use them: element offsets of the two tap ROW pairs inside a box whose origin is (xa, ymin) and whose rows are `pitch`
-// elements apart — the pair (x1 - 1, x1) of rows y0 and y1 (at the right patch edge, x1 == x0, wa == wb == 0 and the pair's second element is the x1
-// tap: no select) — and the weights; a pixel the patch does not cover (all weights 0) reads the box origin.  Returns the weight sum.
-// (xo = x0 - (xa + 1 - (x1 - x0)) = x1 - xa - 1; y1 - y0 is 0 or 1: one 24-bit multiply-add and one select instead of two 32-bit multiplies.)
-__device__ __forceinline__ float p2e_taps_box(const P2EArgs& a, float sp, float cp, float slat, float clat, float cd, float sd, int xa1, int ymin, int pitch,
-                                              int& r0, int& r1, float& wa, float& wb, float& wc, float& wd)
-{
-    TapsF f;
-    p2e_taps_f(a, sp, cp, slat, clat, cd, sd, f);
-    const float wsum = (f.wa + f.wb) + (f.wc + f.wd);               // all >= 0 after the threshold
-    const bool used = wsum > 0.0f;
-    const int o0 = __mul24((int)f.y0f - ymin, pitch) + ((int)f.x1f - xa1);
-    r0 = used ? o0 : 0;
-    r1 = used ? o0 + (f.y1f != f.y0f ? pitch : 0) : 0;
-    wa = f.wa; wb = f.wb; wc = f.wc; wd = f.wd;
-    return wsum;
-}
-__device__ __forceinline__ bool p2e_taps_cs(const P2EArgs& a, int n, float slat, float clat, float cd, float sd, Taps& t)
-{
-    return p2e_taps_core(a, a.tab.sphi[n], a.tab.cphi[n], slat, clat, cd, sd, t);
-}
-__device__ __forceinline__ bool p2e_taps(const P2EArgs& a, int n, float slat, float clat, float slon, float clon, Taps& t)
-{
-    float cd, sd;
-    p2e_lon(a, n, slon, clon, cd, sd);
-    return p2e_taps_cs(a, n, slat, clat, cd, sd, t);
-}
-
-// One wave per 64-pixel tile: bit n of cand[row][tile] = any lane valid for patch n.
-__global__ __launch_bounds__(256) void p2e_candidates_kernel(P2EArgs a, unsigned long long* cand)
-{
-    const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-    if (wave >= a.H * a.ntx) return;
-    const int i = wave / a.ntx, j = (wave % a.ntx) * 64 + lane;
-    const float2 rt = a.row_trig[i];
-    const float2 ct = a.col_trig[min(j, a.W - 1)];
-    unsigned long long m = 0;
-    for (int n = 0; n < a.tab.N; ++n) {
-        Taps t;
-        const bool v = p2e_taps(a, n, rt.x, rt.y, ct.x, ct.y, t) && (j < a.W);
-        if (__ballot(v) != 0ull) m |= (1ull << n);
-    }
-    if (lane == 0) cand[wave] = m;
-}
-
-template <typename T> struct Pair;
-template <> struct Pair<float> {
-    struct __attribute__((packed, aligned(4))) U { float x, y; };     // 4-byte aligned 8-byte load
-    static __device__ __forceinline__ void ld(const float* p, float& x, float& y)
-    { const U v = *reinterpret_cast<const U*>(p); x = v.x; y = v.y; }
-};
-template <> struct Pair<__half> {
-    static __device__ __forceinline__ void ld(const __half* p, float& x, float& y)
-    { unsigned u; __builtin_memcpy(&u, p, 4); const __half2 h = *reinterpret_cast<const __half2*>(&u);
-      x = __low2float(h); y = __high2float(h); }
-};
 
 // four taps of one plane.  XS1: the patch rows are unit-stride in x (planar layout), so the two
 // x-taps of a row come from ONE 8-byte load of (xb, xb+1), xb = min(x0, pw-2); when x0 == pw-1 the
@@ -292,7 +153,6 @@ __global__ __launch_bounds__(256) void p2e_kernel(P2EArgs a, int tiles_per_row4,
     }
 }
 
-
 // ------------------------------------------------------------------ LDS-staged blend (planar layout)
 // The gather kernel above is bound by the vector L1 (a 64-lane gather of 8-byte pairs costs ~20 tag look-ups for 0.5 KB of
 // useful data, profiles/r01f_resample_pmc.txt), not by HBM.  Here ONE WAVE owns an ERP tile of P2E_TH x P2E_TW pixels (4 per
@@ -303,108 +163,6 @@ __global__ __launch_bounds__(256) void p2e_kernel(P2EArgs a, int tiles_per_row4,
 // block-level synchronisation at all — a wave orders its own DMA -> ds_read hand-off with counted `s_waitcnt vmcnt(N)`, and
 // keeps `nbuf` boxes in flight (ring of equal slots, sized for the largest box of the geometry).  Arithmetic, summation order
 // and therefore every output bit are those of the gather kernel (tests compare the two with torch.equal).
-constexpr int P2E_TH = 4, P2E_TW = 32;          // ERP tile of one wave: NPX = TH/2 pixels per lane (lane -> column lane%32, rows lane/32 + 2k)
-constexpr int P2E_NPX = P2E_TH / 2;
-constexpr int P2E_MAXC = 12;                    // table entries (covering patches) per tile
-// The ORDERED table the kernel reads: per block slot P2E_REC records of 32 bytes — {tile id | -1, covering patches, 0...}, then per covering
-// patch {entry x, entry y, sin l0, cos l0 | sin p1, cos p1, 0, 0} (the patch constants ride with the entry: one scalar load per patch, issued
-// one patch AHEAD, instead of a table entry and then four dependent loads from the argument segment in front of every patch), one spare.
-constexpr int P2E_REC = P2E_MAXC + 2;
-constexpr int P2E_NJMAX = 8;                    // 1-KiB DMA pieces per box at most: boxes up to 8 KiB
-constexpr int P2E_MAX_CHUNKS = 64 * P2E_NJMAX;
-
-// entry: x = n | bw4 << 6 | bh << 16 | (entry 0 only) count << 26 (bw4 = 16-byte chunks per box row, bh = box rows, both <= 512;
-// count = covering patches of the tile), y = xa | ymin << 16
-template <int TH>                                                  // tile height: P2E_TH (every LDS kernel) or 8 (the one-plane walk kernel, round 5)
-__global__ __launch_bounds__(256) void p2e_tiles_kernel(P2EArgs a, uint2* __restrict__ ent, int tiles_x, int ntiles, int epc,
-                                                        int* __restrict__ stats)
-{
-    const int wid = (int)((blockIdx.x * 256 + threadIdx.x) >> 6), lane = threadIdx.x & 63;
-    if (wid >= ntiles) return;
-    const int ti = wid / tiles_x, tj = wid - ti * tiles_x;
-    const int col = lane & 31, rsub = lane >> 5;
-    const int j = tj * P2E_TW + col;
-    const bool jin = j < a.W;
-    const float2 ct = a.col_trig[jin ? j : a.W - 1];
-    int cnt = 0, maxch = 0, sumch = 0;
-    for (int n = 0; n < a.tab.N; ++n) {
-        int xmin = 0x7fffffff, xmax = -1, ymin = 0x7fffffff, ymax = -1;
-#pragma unroll
-        for (int k = 0; k < TH / 2; ++k) {
-            const int i = ti * TH + rsub + 2 * k;
-            const bool iin = i < a.H;
-            const float2 rt = a.row_trig[iin ? i : a.H - 1];
-            Taps t;
-            p2e_taps(a, n, rt.x, rt.y, ct.x, ct.y, t);
-            const float wsum = (t.wa + t.wb) + (t.wc + t.wd);
-            if (jin && iin && wsum > 0.0f) {
-                xmin = min(xmin, t.x0); xmax = max(xmax, t.x1); ymin = min(ymin, t.y0); ymax = max(ymax, t.y1);
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            xmin = min(xmin, __shfl_xor(xmin, o)); xmax = max(xmax, __shfl_xor(xmax, o));
-            ymin = min(ymin, __shfl_xor(ymin, o)); ymax = max(ymax, __shfl_xor(ymax, o));
-        }
-        if (xmax < 0) continue;                                   // wave-uniform: patch n covers no pixel of this tile
-        int xa = xmin / epc * epc;
-        int bw4 = (xmax / epc * epc + epc - xa) / epc;
-        const int bh = ymax - ymin + 1;
-        const bool fits = bw4 < 1024 && bh < 1024 && xa < 65536 && ymin < 65536 && bw4 * bh <= P2E_MAX_CHUNKS;
-        maxch = max(maxch, fits ? bw4 * bh : P2E_MAX_CHUNKS + 1);
-        sumch += fits ? bw4 * bh : (1 << 20);
-        if (lane == 0 && cnt < P2E_MAXC && fits)
-            ent[(size_t)wid * P2E_MAXC + cnt] = make_uint2((unsigned)n | ((unsigned)bw4 << 6) | ((unsigned)bh << 16),
-                                                           (unsigned)xa | ((unsigned)ymin << 16));
-        ++cnt;
-    }
-    if (lane == 0) {
-        for (int c = cnt; c < P2E_MAXC; ++c) ent[(size_t)wid * P2E_MAXC + c] = make_uint2(0u, 0u);
-        if (cnt <= P2E_MAXC) ent[(size_t)wid * P2E_MAXC].x |= (unsigned)cnt << 26;
-        atomicMax(&stats[0], maxch); atomicMax(&stats[1], cnt); atomicMax(&stats[2], sumch);
-    }
-}
-
-// column origin of a tap pair: the box origin, shifted so that an x1 == x0 tap (right patch edge) becomes the pair's second element
-__device__ __forceinline__ int xa_adj(int x0, int x1, int xa) { return xa + 1 - (x1 - x0); }
-
-template <typename T> struct LdsPair;
-template <> struct LdsPair<float> {
-    static __device__ __forceinline__ void ld(const unsigned char* b, int o, float& x, float& y)
-    { const float* p = reinterpret_cast<const float*>(b) + o; x = p[0]; y = p[1]; }              // one ds_read2_b32
-};
-template <> struct LdsPair<__half> {
-    // halfs o, o+1: one ds_read2_b32 of the two 32-bit words around them + a byte-align (no 16-bit LDS reads, which cost a full
-    // LDS instruction each)
-    static __device__ __forceinline__ void ld(const unsigned char* b, int o, float& x, float& y)
-    {
-        const unsigned* p = reinterpret_cast<const unsigned*>(b) + (o >> 1);
-        const unsigned w0 = p[0], w1 = p[1];
-        const unsigned v = (o & 1) ? __builtin_amdgcn_alignbyte(w1, w0, 2u) : w0;
-        const __half2 h = *reinterpret_cast<const __half2*>(&v);
-        x = __low2float(h); y = __high2float(h);
-    }
-};
-
-typedef __amdgpu_buffer_rsrc_t p2e_rsrc_t;
-typedef __attribute__((address_space(3))) void* p2e_lptr_t;
-__device__ __forceinline__ p2e_rsrc_t p2e_make_rsrc(const void* p, unsigned bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
-}
-// one LDS-DMA instruction: lane l's 16 bytes at buffer offset voff + soff (soff wave-uniform) land at lds + 16 l; an offset
-// outside the buffer deposits zeros without touching memory (used for the padding lanes of a box's last piece).
-// (A plain function: the host pass does not accept this builtin inside a kernel template's body.)
-__device__ __forceinline__ void p2e_dma16(p2e_rsrc_t rs, unsigned char* lds, unsigned voff, unsigned soff)
-{
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (p2e_lptr_t)lds, 16, (int)voff, (int)soff, 0, 0);
-}
-template <int N> __device__ __forceinline__ void p2e_wait_vm()
-{
-    static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit counter");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // ONE WAVE (= one 64-thread block) per (ERP tile, group of PL planes); nothing in here synchronises with another wave.  The
 // covering patches of the tile are walked one after the other; per patch: (1) the first NB boxes are put in flight, (2) the tap
 // geometry of my NPX pixels is evaluated while they travel, (3) the PL stages run.  A stage = (patch, plane p): the box of the
@@ -633,10 +391,6 @@ __global__ __launch_bounds__(64, 4) void p2e_lds_kernel(P2EArgs a, const uint2* 
 //     which deposit zeros without touching memory): every s_waitcnt count of the flat stream is a compile-time constant of (NJ, last patch or not);
 //   * the slot record carries the tile's trig (32 column + 4 row pairs, 288 B): header, first patch record and trig leave in parallel, ONE cold
 //     round trip in front of the first DMA.
-constexpr int P2W_NJMAX = 6;                                   // largest box (KiB) the walk kernel is instantiated for
-constexpr int P2W_SLOT = 768;                                  // bytes per block slot: header 32 | 12 patch records x 32 | trig 288 | pad
-constexpr int P2W_OFF_PATCH = 32, P2W_OFF_TRIG = 32 + 32 * P2E_MAXC;
-static_assert(P2W_OFF_TRIG + 8 * (P2E_TW + 8) <= P2W_SLOT, "slot layout (8-row tiles included)");
 constexpr int p2w_nb(int pieces, int pl)
 {
     int nb = P2E_RING_KB / pieces >= 4 ? 4 : P2E_RING_KB / pieces >= 2 ? 2 : 1;
@@ -645,7 +399,6 @@ constexpr int p2w_nb(int pieces, int pl)
 }
 constexpr int p2w_u(int nb, int pl) { return nb == 4 ? 2 : (nb == 2 && pl == 2) ? 2 : 1; }
 
-constexpr int P2W_WPB = 1;                                     // waves per block: independent waves (no barrier, each its own tile and ring) — 4x fewer workgroups to dispatch
 // TH: rows of the ERP tile a wave owns (TH / 2 pixels per lane).  8 for ONE plane per wave (round 5): the per-(wave, patch) set-up — records, box
 // parameters, the stage switch — is paid half as often (cfg 5 fp32 96 -> 88 us, cfg 3 27.3 -> 26.3, fp16 unchanged: profiles/r05f_p2e_tile8.txt).  Same taps, same candidate order, same blend
 // expression per pixel (a patch that does not cover a pixel adds an exact 0): the bits do not depend on the tile.
@@ -866,81 +619,7 @@ __global__ __launch_bounds__(64 * P2W_WPB, TH > P2E_TH ? (CONF ? 4 : 5) : PL == 
 // 15.9 with the balanced block order), 46.9 vs 33.3 us at nrows = 6: its per-block phases (tools/trace_resample.py) were loads 1.3 us, DMA
 // addresses + ring fill 1.4, taps 1.4, the 8 stages 4.8, stores 0.8 for a 2-patch tile and still grew by 2.5 us per patch — a block's time is
 // the WORK per patch (bytes, taps, geometry) divided by a throughput 16 waves per CU share, not the number of dependent pipelines.
-// What the same traces did show: the CU on a patch seam had 56 patch-tiles to the median CU's 34 — see the block order in omni_p2e_build_tiles.
-// ------------------------------------------------------------------ backward
-// g_pers[b,c,y,x,n] = sum over the ERP pixels (i,j) whose tap of patch n is (y,x) of w~ * g_erp[b,c,i,j], w~ the thresholded,
-// L1-normalised weights of the forward (the operator is linear in the patches; the weights do not depend on them).
-// One thread per ERP pixel, two passes over the candidate patches (normaliser, then scatter); fp32 hardware atomics into a
-// zeroed g_pers.
-__global__ __launch_bounds__(256) void p2e_bwd_kernel(P2EArgs a /* erp = g_erp (in), pers = g_pers (out) */, int nblocks)
-{
-    const unsigned lb = omni_xcd_remap(blockIdx.x, nblocks);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int tx = lb % a.ntx;
-    const int i = __builtin_amdgcn_readfirstlane((int)(lb / a.ntx) * 4 + wave);
-    const int j = tx * 64 + lane;
-    if (i >= a.H) return;
-    const bool inside = j < a.W;
-    const float2 rt = a.row_trig[i];
-    const float2 ct = a.col_trig[inside ? j : a.W - 1];
-    const unsigned long long cm_ = a.cand[(size_t)i * a.ntx + tx];
-    const unsigned cm_hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(cm_ >> 32));
-    const unsigned cm_lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(cm_ & 0xffffffffull));
-    const unsigned long long cmask = ((unsigned long long)cm_hi << 32) | (unsigned long long)cm_lo;
-    float l1 = 0.0f;
-    for (unsigned long long m = cmask; m;) {
-        const int n = __builtin_ctzll(m); m &= m - 1;
-        Taps t; p2e_taps(a, n, rt.x, rt.y, ct.x, ct.y, t);
-        l1 += (t.wa + t.wb) + (t.wc + t.wd);
-    }
-    if (!inside) return;
-    const float rden = 1.0f / fmaxf(l1, 1e-12f);
-    const float* gerp = (const float*)a.erp;
-    float* gp = (float*)const_cast<void*>(a.pers);
-    const size_t erp_plane = (size_t)a.H * a.W, pix = (size_t)i * a.W + j;
-    for (unsigned long long m = cmask; m;) {
-        const int n = __builtin_ctzll(m); m &= m - 1;
-        Taps t; p2e_taps(a, n, rt.x, rt.y, ct.x, ct.y, t);
-        if (!((t.wa + t.wb) + (t.wc + t.wd) > 0.0f)) continue;
-        const size_t oa = (size_t)n * a.sN + (size_t)t.y0 * a.sY + (size_t)t.x0 * a.sX, ob = (size_t)n * a.sN + (size_t)t.y1 * a.sY + (size_t)t.x0 * a.sX;
-        const size_t oc = (size_t)n * a.sN + (size_t)t.y0 * a.sY + (size_t)t.x1 * a.sX, od = (size_t)n * a.sN + (size_t)t.y1 * a.sY + (size_t)t.x1 * a.sX;
-        for (int b = 0; b < a.B; ++b)
-            for (int c = 0; c < a.C; ++c) {
-                const float g = gerp[((size_t)b * a.C + c) * erp_plane + pix] * rden;
-                float* q = gp + (size_t)b * a.sB + (size_t)c * a.sC;
-                if (t.wa != 0.0f) atomicAdd(q + oa, g * t.wa);
-                if (t.wb != 0.0f) atomicAdd(q + ob, g * t.wb);
-                if (t.wc != 0.0f) atomicAdd(q + oc, g * t.wc);
-                if (t.wd != 0.0f) atomicAdd(q + od, g * t.wd);
-            }
-    }
-}
-
-int fill_args(P2EArgs& a, const omni_geometry* g, const void* pers, const void* pers2, void* erp,
-              int B, int C, int layout)
-{
-    a.pers = pers; a.pers2 = pers2; a.erp = erp;
-    a.row_trig = g->row_trig; a.col_trig = g->col_trig; a.cand = g->cand;
-    a.B = B; a.C = C; a.H = g->H; a.W = g->W; a.ph = g->ph; a.pw = g->pw; a.ntx = g->ntx;
-    const long long N = g->N, ph = g->ph, pw = g->pw;
-    if (layout == OMNI_LAYOUT_BCHWN)      { a.sX = N; a.sY = pw * N; a.sN = 1; a.sC = ph * pw * N; a.sB = C * a.sC; }
-    else if (layout == OMNI_LAYOUT_BNCHW) { a.sX = 1; a.sY = pw; a.sC = ph * pw; a.sN = C * a.sC; a.sB = N * a.sN; }
-    else if (layout == OMNI_LAYOUT_BNHWC) { a.sC = 1; a.sX = C; a.sY = pw * C; a.sN = ph * a.sY; a.sB = N * a.sN; }
-    else OMNI_FAIL(OMNI_ERR_INVALID, "omni_pers2equi: unknown layout");
-    const float PIf = (float)M_PI, PI2f = (float)(M_PI * 0.5);
-    // the reference divides twice in fp32 (new_x / FOV[0] / PI); a reciprocal product differs by <= 1.5 ulp
-    a.kx = (float)(1.0 / ((double)(g->fov_w / 360.0f) * (double)PIf));
-    a.ky = (float)(1.0 / ((double)(g->fov_h / 180.0f) * (double)PI2f));
-    a.half_h = 0.5f * (float)g->ph; a.half_w = 0.5f * (float)g->pw;
-    a.tab = g->p2e;
-    a.store_nt = omni_options().p2e_store ? 1 : 0;
-    a.dbg = 0; a.trace = nullptr;
-#ifdef OMNI_DEBUG_BUILD
-    a.dbg = omni_debug_bits("OMNI_P2E_DBG");
-    a.trace = omni_debug_trace_buf();
-#endif
-    return OMNI_OK;
-}
+// What the same traces did show: the CU on a patch seam had 56 patch-tiles to the median CU's 34 — see the block order in omni_p2e_build_tiles (omni_p2e_tables.hip).
 
 template <typename T, bool CONF, bool XS1>
 void launch_p2e_pl(const P2EArgs& a, int planes, int rows4, int nblocks, hipStream_t stream)
@@ -1065,159 +744,7 @@ int launch_p2e(const omni_geometry* g, const void* pers, const void* pers2, void
     OMNI_HIP(hipGetLastError());
     return OMNI_OK;
 }
-
-int check_common(const omni_geometry* g, int B, int C, const char* who)
-{
-    if (!g) OMNI_FAIL(OMNI_ERR_INVALID, std::string(who) + ": null geometry");
-    if (B < 0 || C < 0) OMNI_FAIL(OMNI_ERR_INVALID, std::string(who) + ": negative batch/channels");
-    if (g->H < 1 || g->W < 1) OMNI_FAIL(OMNI_ERR_INVALID, std::string(who) + ": empty ERP size");
-    return OMNI_OK;
-}
 }  // namespace
-
-int omni_p2e_build_candidates(omni_geometry* g, hipStream_t stream)
-{
-    P2EArgs a;
-    int rc = fill_args(a, g, nullptr, nullptr, nullptr, 0, 1, OMNI_LAYOUT_BNCHW);
-    if (rc != OMNI_OK) return rc;
-    const int waves = g->H * g->ntx;
-    hipLaunchKernelGGL(p2e_candidates_kernel, dim3((waves + 3) / 4), dim3(256), 0, stream, a, g->cand);
-    OMNI_HIP(hipGetLastError());
-    // one-time setup: make the table visible to every stream that may use this handle later
-    OMNI_HIP(hipStreamSynchronize(stream));
-    return OMNI_OK;
-}
-
-// Per-tile box tables of the LDS path (one per element size: the 16-byte chunk alignment differs).  One-time setup.
-int omni_p2e_build_tiles(omni_geometry* g, hipStream_t stream)
-{
-    P2EArgs a;
-    int rc = fill_args(a, g, nullptr, nullptr, nullptr, 0, 1, OMNI_LAYOUT_BNCHW);
-    if (rc != OMNI_OK) return rc;
-    g->p2e_tx = (g->W + P2E_TW - 1) / P2E_TW; g->p2e_ty = (g->H + P2E_TH - 1) / P2E_TH;
-    if ((long long)g->p2e_tx * g->p2e_ty >= (1ll << 28)) return OMNI_OK;                     // absurd sizes: gather path only
-    int* dstats = nullptr;
-    OMNI_HIP(hipMalloc((void**)&dstats, 3 * sizeof(int)));
-    // sets 0 / 1: P2E_TH-row tiles (4- / 2-byte elements), what every LDS kernel reads; sets 2 / 3: 8-row tiles for the one-plane walk kernel (its slot
-    // table only; built when the 4-row set of the element size exists)
-    for (int e = 0; e < 4; ++e) {
-        auto& tt = g->p2e_tiles[e];
-        const int epc = (e & 1) ? 8 : 4, TH = e < 2 ? P2E_TH : 8;
-        if (e >= 2 && (!g->p2e_tiles[e - 2].ok || !omni_options().p2e_tile8)) continue;
-        const int ty_set = (g->H + TH - 1) / TH;
-        const long long ntiles = (long long)g->p2e_tx * ty_set;
-        if (hipMalloc((void**)&tt.ent, sizeof(uint2) * (size_t)ntiles * P2E_MAXC) != hipSuccess) { (void)hipFree(dstats); OMNI_FAIL(OMNI_ERR_HIP, "omni_p2e_build_tiles: out of memory"); }
-        if (hipMemsetAsync(dstats, 0, 3 * sizeof(int), stream) != hipSuccess) { (void)hipFree(dstats); OMNI_FAIL(OMNI_ERR_HIP, "omni_p2e_build_tiles: memset"); }
-        if (TH == 8) hipLaunchKernelGGL(p2e_tiles_kernel<8>, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, stream, a, tt.ent, g->p2e_tx, (int)ntiles, epc, dstats);
-        else         hipLaunchKernelGGL(p2e_tiles_kernel<P2E_TH>, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, stream, a, tt.ent, g->p2e_tx, (int)ntiles, epc, dstats);
-        int hs[3] = {0, 0, 0};
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hs, dstats, sizeof(hs), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipStreamSynchronize(stream) != hipSuccess) { (void)hipFree(dstats); OMNI_FAIL(OMNI_ERR_HIP, "omni_p2e_build_tiles: kernel failed"); }
-        tt.max_chunks = hs[0]; tt.max_cand = hs[1];
-        tt.ok = (hs[0] <= P2E_MAX_CHUNKS && hs[1] <= P2E_MAXC && g->pw % epc == 0) ? 1 : 0;
-        tt.sum_chunks = hs[2];
-        if (tt.ok) {
-            // ---- block order.  A block's duration grows with the number of covering patches of its tile (3.3 us + 2.9 us per patch at
-            // cfg 1, tools/trace_resample.py), all blocks of a BASELINE-size launch are resident at once, and the dispatcher deals an XCD's
-            // blocks to its 32 CUs round-robin (block b -> XCD b % 8, CU (b / 8) % 32 of it: tools/trace_cu.py) — with 32 tiles per ERP
-            // row every CU got ONE column strip of the image and the CU on a patch seam 56 patch-tiles where the median CU has 34; the
-            // launch ended when that CU did (17.4 us for blocks of 9.8 us on average).  So: whole bands of tile rows per XCD as before
-            // (vertical neighbours share their boxes in one L2), bands dealt to the XCDs by cost (heaviest with lightest), and inside an
-            // XCD the tiles sorted by cost and dealt to the 32 round-robin positions in snake order.  Pure speed: any order is correct.
-            std::vector<uint2> he((size_t)ntiles * P2E_MAXC);
-            if (hipMemcpy(he.data(), tt.ent, sizeof(uint2) * he.size(), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipFree(dstats); OMNI_FAIL(OMNI_ERR_HIP, "omni_p2e_build_tiles: copy"); }
-            const int tx = g->p2e_tx, ty = ty_set, band = omni_options().p2e_band > 0 ? omni_options().p2e_band : std::max(1, ty / 8), nbands = (ty + band - 1) / band;   // (one contiguous range of tile rows per XCD: 15.8 us, FETCH 52 MB; 8-row bands 16.0, 4-row 17.2 / 61 MB, 2-row 19.6 / 85 MB)
-            auto cost = [&](int wid) { return 2 + (int)(he[(size_t)wid * P2E_MAXC].x >> 26); };
-            std::vector<std::pair<long long, int>> bc(nbands);
-            for (int b = 0; b < nbands; ++b) {
-                long long c = 0;
-                for (int r = b * band; r < std::min(ty, (b + 1) * band); ++r) for (int x = 0; x < tx; ++x) c += cost(r * tx + x);
-                bc[b] = {-c, b};
-            }
-            std::sort(bc.begin(), bc.end());
-            std::vector<std::vector<int>> per(8);
-            for (int k = 0; k < nbands; ++k) {
-                const int r = k / 8, i = k % 8, xcd = (r & 1) ? 7 - i : i, b = bc[k].second;
-                for (int row = b * band; row < std::min(ty, (b + 1) * band); ++row) for (int x = 0; x < tx; ++x) per[xcd].push_back(row * tx + x);
-            }
-            size_t mx = 0;
-            for (auto& v : per) {
-                std::stable_sort(v.begin(), v.end(), [&](int p, int q) { return cost(p) > cost(q); });
-                mx = std::max(mx, v.size());
-            }
-            const size_t rounds = (mx + 31) / 32;
-            tt.nslots = (int)(rounds * 32 * 8);
-            std::vector<uint2> ord((size_t)tt.nslots * 4 * P2E_REC, make_uint2(0u, 0u));       // (a 32-byte record = 4 uint2)
-            for (int s2 = 0; s2 < tt.nslots; ++s2) ord[(size_t)s2 * 4 * P2E_REC].x = 0xffffffffu;
-            auto fbits = [](float f) { unsigned u; memcpy(&u, &f, 4); return u; };
-            for (int xcd = 0; xcd < 8; ++xcd)
-                for (size_t k = 0; k < per[xcd].size(); ++k) {
-                    const size_t r = k / 32, i = k % 32, pos = r * 32 + ((r & 1) ? 31 - i : i);
-                    const size_t slot = pos * 8 + (size_t)xcd;
-                    const int wid = per[xcd][k];
-                    uint2* rec = ord.data() + slot * 4 * P2E_REC;
-                    const int cnt = (int)(he[(size_t)wid * P2E_MAXC].x >> 26);
-                    rec[0] = make_uint2((unsigned)wid, (unsigned)cnt);
-                    for (int c = 0; c < P2E_MAXC; ++c) {
-                        const uint2 e2 = he[(size_t)wid * P2E_MAXC + c];
-                        const int n = (int)(e2.x & 63u);
-                        rec[4 * (c + 1) + 0] = e2;
-                        rec[4 * (c + 1) + 1] = make_uint2(fbits(g->p2e.slam[n]), fbits(g->p2e.clam[n]));
-                        rec[4 * (c + 1) + 2] = make_uint2(fbits(g->p2e.sphi[n]), fbits(g->p2e.cphi[n]));
-                    }
-                }
-            if (e < 2 && (hipMalloc((void**)&tt.ord, sizeof(uint2) * ord.size()) != hipSuccess ||
-                hipMemcpy(tt.ord, ord.data(), sizeof(uint2) * ord.size(), hipMemcpyHostToDevice) != hipSuccess)) { (void)hipFree(dstats); OMNI_FAIL(OMNI_ERR_HIP, "omni_p2e_build_tiles: order table"); }
-            // ---- the same slots for p2e_walk_kernel: header {tile | -1, covering patches, pieces per stage (tile-uniform)}, the patch records, the tile's trig
-            {
-                std::vector<float2> hrow((size_t)g->H), hcol((size_t)g->W);
-                if (hipMemcpy(hrow.data(), g->row_trig, sizeof(float2) * hrow.size(), hipMemcpyDeviceToHost) != hipSuccess ||
-                    hipMemcpy(hcol.data(), g->col_trig, sizeof(float2) * hcol.size(), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipFree(dstats); OMNI_FAIL(OMNI_ERR_HIP, "omni_p2e_build_tiles: trig copy"); }
-                // block b of the walk kernel = P2W_WPB waves = the slots WPB b .. WPB b + WPB - 1, all on CU (b / 8) % 32 of XCD b % 8: the tile that
-                // the one-wave-per-block order gives to (XCD x, CU c, round r) keeps its CU — slot WPB (((r / WPB) 32 + c) 8 + x) + r % WPB
-                const size_t rounds_w = (rounds + P2W_WPB - 1) / P2W_WPB * P2W_WPB;
-                tt.nslots_walk = (int)(rounds_w * 32 * 8);
-                std::vector<unsigned char> wt((size_t)tt.nslots_walk * P2W_SLOT, 0);
-                for (int s2 = 0; s2 < tt.nslots_walk; ++s2) { const unsigned m1 = 0xffffffffu; memcpy(wt.data() + (size_t)s2 * P2W_SLOT, &m1, 4); }
-                int hist[P2E_NJMAX + 1] = {0};
-                for (int s2 = 0; s2 < tt.nslots; ++s2) {
-                    const uint2* rec = ord.data() + (size_t)s2 * 4 * P2E_REC;
-                    const size_t x8 = (size_t)s2 % 8, pos = (size_t)s2 / 8, rr = pos / 32, cu = pos % 32;
-                    unsigned char* dst = wt.data() + ((((rr / P2W_WPB) * 32 + cu) * 8 + x8) * P2W_WPB + rr % P2W_WPB) * P2W_SLOT;
-                    const int wid = (int)rec[0].x, cnt = (int)rec[0].y;
-                    int njt = 1;
-                    if (wid >= 0)
-                        for (int c = 0; c < cnt && c < P2E_MAXC; ++c) {
-                            const unsigned e0 = rec[4 * (c + 1)].x;
-                            const int nchunk = (int)((e0 >> 6) & 1023) * (int)((e0 >> 16) & 1023);
-                            njt = std::max(njt, (nchunk + 63) / 64);
-                        }
-                    if (wid >= 0) ++hist[std::min(njt, P2E_NJMAX)];
-                    const unsigned hdr[8] = {(unsigned)wid, (unsigned)cnt, (unsigned)njt, 0u, 0u, 0u, 0u, 0u};
-                    memcpy(dst, hdr, 32);
-                    memcpy(dst + P2W_OFF_PATCH, rec + 4, 32 * P2E_MAXC);
-                    if (wid >= 0) {
-                        const int ti = wid / tx, tj = wid - ti * tx;
-                        float2* tg = reinterpret_cast<float2*>(dst + P2W_OFF_TRIG);
-                        for (int cc = 0; cc < P2E_TW; ++cc) tg[cc] = hcol[(size_t)std::min(tj * P2E_TW + cc, g->W - 1)];
-                        for (int r = 0; r < TH; ++r) tg[P2E_TW + r] = hrow[(size_t)std::min(ti * TH + r, g->H - 1)];
-                    }
-                }
-                if (omni_options().e2p_verbose)
-                    fprintf(stderr, "[omni] pers2equi %dx%d <- %dx%d, %d-byte elements: tiles by KiB pieces per stage (largest box of the tile): 1:%d 2:%d 3:%d 4:%d 5:%d 6:%d 7:%d 8:%d\n",
-                            g->H, g->W, g->ph, g->pw, 16 / epc, hist[1], hist[2], hist[3], hist[4], hist[5], hist[6], hist[7], hist[8]);
-                if (hipMalloc((void**)&tt.walk, wt.size()) != hipSuccess ||
-                    hipMemcpy(tt.walk, wt.data(), wt.size(), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(dstats); OMNI_FAIL(OMNI_ERR_HIP, "omni_p2e_build_tiles: walk table"); }
-            }
-        }
-        (void)hipFree(tt.ent); tt.ent = nullptr;                     // the kernels read only the ordered table (tt.ord)
-        if (omni_options().e2p_verbose)
-            fprintf(stderr, "[omni] pers2equi %dx%d <- %d patches %dx%d, %d-byte elements: largest tap box %d chunks, <= %d patches and <= %d chunks per %dx%d tile -> %s\n",
-                    g->H, g->W, g->N, g->ph, g->pw, 16 / epc, hs[0], hs[1], hs[2], TH, P2E_TW, tt.ok ? "LDS path" : "gather path");
-    }
-    (void)hipFree(dstats);
-    return OMNI_OK;
-}
 
 // ------------------------------------------------------------------ reference layout -> planar
 // [B,C,ph,pw,N] (N innermost: the reference's stack(dim=-1) / unfold layout) -> [B,N,C,ph,pw].  A blend over the N-innermost tensor
@@ -1293,303 +820,4 @@ extern "C" int omni_pers2equi_conf(const void* pred_w, const void* conf, float* 
     if (dtype == OMNI_F32) return launch_p2e<float, true>(g, pred_w, conf, out, B, 1, layout, (hipStream_t)stream);
     if (dtype == OMNI_F16) return launch_p2e<__half, true>(g, pred_w, conf, out, B, 1, layout, (hipStream_t)stream);
     OMNI_FAIL(OMNI_ERR_INVALID, "omni_pers2equi_conf: dtype must be OMNI_F32 or OMNI_F16");
-}
-
-// Vector-Jacobian product of pers2equi w.r.t. the patches: grad_erp [B,C,H,W] -> grad_pers in the layout of the forward's
-// input (overwritten).  fp32 only.  Replaces what autograd derives from the advanced-indexing gathers of
-// pers2equi_v3.py:174-196 in the reference's training scripts.
-namespace {
-// ---- backward by gathers (no global atomics, nothing to zero).  The scatter kernel above issues 4 global atomics per (ERP pixel, covering
-// patch, plane): 35 M of them at B = 8, 18 x 256^2 — 1.28 ms, bound by the L2 atomic rate.  Transposed, every PATCH pixel is the sum over the ERP
-// pixels whose bilinear taps touch it, and patch tiles are disjoint: one wave owns a 4 x 32 tile of one patch, walks the ERP box of the
-// pixels that can touch it (a constant of the geometry, built once with the SAME tap function — exact superset), evaluates their taps
-// for this patch, and accumulates the ones that fall into its tile in LDS (ds_add_f32: order within the wave's own instruction stream);
-// then it writes the tile once, coalesced.  An ERP pixel is visited by every tile its taps touch (1-4 per covering patch), so the tap
-// geometry is evaluated ~2.5x as often as in the forward; the L1 normaliser of a pixel (all covering patches) is a table.
-constexpr int P2B_TH = 4, P2B_TW = 32;
-
-__device__ __forceinline__ int p2b_centre_col(const P2EArgs& a, int n)
-{
-    return (int)((a.tab.lam0[n] + 3.14159265358979f) * (0.5f / 3.14159265358979f) * (float)(a.W - 1) + 0.5f);
-}
-__device__ __forceinline__ int p2b_wrap(int dx, int W)              // column difference into [-W/2, W - W/2)
-{
-    const int h = W >> 1;
-    dx = dx >= W - h ? dx - W : dx;
-    return dx < -h ? dx + W : dx;
-}
-
-// one wave per 64 ERP pixels of one row: the L1 normaliser of every pixel and, per (patch, tile), the box of the pixels touching it
-__global__ __launch_bounds__(256) void p2e_bwd_box_kernel(P2EArgs a, int* __restrict__ boxes, float* __restrict__ rden, int btx, int bty)
-{
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int tx = blockIdx.x % a.ntx;
-    const int i = __builtin_amdgcn_readfirstlane((int)(blockIdx.x / a.ntx) * 4 + wave);
-    const int j = tx * 64 + lane;
-    if (i >= a.H) return;
-    const bool inside = j < a.W;
-    const float2 rt = a.row_trig[i];
-    const float2 ct = a.col_trig[inside ? j : a.W - 1];
-    const unsigned long long cm_ = a.cand[(size_t)i * a.ntx + tx];
-    const unsigned cm_hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(cm_ >> 32));
-    const unsigned cm_lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(cm_ & 0xffffffffull));
-    const unsigned long long cmask = ((unsigned long long)cm_hi << 32) | (unsigned long long)cm_lo;
-    float l1 = 0.0f;
-    for (unsigned long long m = cmask; m;) {
-        const int n = __builtin_ctzll(m); m &= m - 1;
-        Taps t; p2e_taps(a, n, rt.x, rt.y, ct.x, ct.y, t);
-        const float wsum = (t.wa + t.wb) + (t.wc + t.wd);
-        l1 += wsum;
-        if (!(inside && wsum > 0.0f)) continue;
-        const int dx = p2b_wrap(j - p2b_centre_col(a, n), a.W);
-        const int xs[2] = {t.x0, t.x1}, ys[2] = {t.y0, t.y1};
-        const float w[4] = {t.wa, t.wb, t.wc, t.wd};               // (y0,x0) (y1,x0) (y0,x1) (y1,x1)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (w[k] == 0.0f) continue;
-            const int id = (n * bty + ys[k & 1] / P2B_TH) * btx + xs[k >> 1] / P2B_TW;
-            atomicMin(boxes + 4 * id + 0, dx); atomicMax(boxes + 4 * id + 1, dx);
-            atomicMin(boxes + 4 * id + 2, i);  atomicMax(boxes + 4 * id + 3, i);
-        }
-    }
-    if (inside) rden[(size_t)i * a.W + j] = 1.0f / fmaxf(l1, 1e-12f);
-}
-
-// planar [planes][N][pp] -> the reference's [planes][pp][N] (N innermost), 64 samples of all N patches per block through LDS: coalesced
-// reads (N runs of 256 bytes) and one contiguous run of 64 N floats out.  (Writing N-innermost straight from the gather kernel puts 4 bytes
-// into every 4 N: 260 MB of write traffic for 38 MB at 18 x 256^2.)
-__global__ __launch_bounds__(256) void p2e_nlast_kernel(const float* __restrict__ src, float* __restrict__ dst, int N, int pp, int C)
-{
-    extern __shared__ float nl_tile[];                            // [64][N | 1]
-    const int NP = N | 1, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int p = blockIdx.y, b = p / C, c = p - b * C, s0 = blockIdx.x * 64, ns = min(64, pp - s0);
-    const float* sp = src + ((size_t)b * N * C + c) * pp + s0;    // + n * C * pp
-    for (int n = wave; n < N; n += 4)
-        if (lane < ns) nl_tile[lane * NP + n] = sp[(size_t)n * C * pp + lane];
-    __syncthreads();
-    float* dp = dst + ((size_t)p * pp + s0) * N;
-    for (int i = t; i < ns * N; i += 256) { const int px = i / N, n = i - px * N; dp[i] = nl_tile[px * NP + n]; }
-}
-
-// The transpose as a sparse matrix (omni_spgather.h): every (ERP pixel, covering patch, tap with a non-zero weight) is one entry
-// (source = the pixel, weight = w_tap / l1) of the row of the patch pixel the tap reads.  Same traversal and tap function as above.
-__global__ __launch_bounds__(256) void p2e_sp_walk_kernel(P2EArgs a, const float* __restrict__ rden, SpEmit b)
-{
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int tx = blockIdx.x % a.ntx;
-    const int i = __builtin_amdgcn_readfirstlane((int)(blockIdx.x / a.ntx) * 4 + wave);
-    const int j = tx * 64 + lane;
-    if (i >= a.H || j >= a.W) return;
-    const float2 rt = a.row_trig[i], ct = a.col_trig[j];
-    const size_t pix = (size_t)i * a.W + j;
-    const float r = rden[pix];
-    const unsigned long long cm_ = a.cand[(size_t)i * a.ntx + tx];
-    const unsigned cm_hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(cm_ >> 32));
-    const unsigned cm_lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(cm_ & 0xffffffffull));
-    for (unsigned long long m = ((unsigned long long)cm_hi << 32) | (unsigned long long)cm_lo; m;) {
-        const int n = __builtin_ctzll(m); m &= m - 1;
-        Taps t; p2e_taps(a, n, rt.x, rt.y, ct.x, ct.y, t);
-        const int xs[2] = {t.x0, t.x1}, ys[2] = {t.y0, t.y1};
-        const float w[4] = {t.wa, t.wb, t.wc, t.wd};               // (y0,x0) (y1,x0) (y0,x1) (y1,x1)
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (w[k] != 0.0f) sp_emit(b, (n * a.ph + ys[k & 1]) * a.pw + xs[k >> 1], (unsigned)pix, w[k] * r);
-    }
-}
-
-// NT threads per tile: 64 for the ordinary tiles, 1024 for the few polar ones whose box is whole ERP rows (tens of thousands of pixels)
-template <int PL, int NT>
-__global__ __launch_bounds__(NT) void p2e_bwd_gather_kernel(P2EArgs a /* erp = g_erp (in), pers = g_pers (out) */, const int4* __restrict__ boxes,
-                                                            const float* __restrict__ rden, const int* __restrict__ ids, int btx, int bty, int planes)
-{
-    __shared__ float acc[PL][P2B_TH * P2B_TW];
-    const int lane = threadIdx.x;
-    const int id = ids[blockIdx.x], p0 = blockIdx.y * PL;
-    const int n = id / (btx * bty), tt = id - n * (btx * bty);
-    const int ty0 = (tt / btx) * P2B_TH, tx0 = (tt % btx) * P2B_TW;
-#pragma unroll
-    for (int p = 0; p < PL; ++p)
-        for (int e = lane; e < P2B_TH * P2B_TW; e += NT) acc[p][e] = 0.0f;
-    if (NT > 64) __syncthreads();
-    const int4 box = boxes[id];                                    // dx min, dx max, row min, row max
-    const float* gerp = (const float*)a.erp;
-    const size_t erp_plane = (size_t)a.H * a.W;
-    if (box.x <= box.y) {
-        const int bw = box.y - box.x + 1, npx = bw * (box.w - box.z + 1);
-        const int xc = p2b_centre_col(a, n);
-        const float rbw = 1.0f / (float)bw;
-        for (int base = 0; base < npx; base += NT) {
-            const int idx = base + lane;
-            const bool in = idx < npx;
-            int dy = (int)(((float)idx + 0.5f) * rbw);               // idx / bw (exact for the sizes here, fixed up below)
-            int dxi = idx - dy * bw;
-            if (dxi < 0) { --dy; dxi += bw; } else if (dxi >= bw) { ++dy; dxi -= bw; }
-            const int i = in ? box.z + dy : box.z;
-            int j = xc + box.x + (in ? dxi : 0);
-            j = j < 0 ? j + a.W : (j >= a.W ? j - a.W : j);
-            const float2 rt = a.row_trig[i], ct = a.col_trig[j];
-            Taps t; p2e_taps(a, n, rt.x, rt.y, ct.x, ct.y, t);
-            const size_t pix = (size_t)i * a.W + j;
-            const float r = in ? rden[pix] : 0.0f;
-            // tile-relative tap positions; a tap outside my tile belongs to a neighbouring wave
-            const int ya = t.y0 - ty0, yb = t.y1 - ty0, xa = t.x0 - tx0, xb = t.x1 - tx0;
-            const bool ya_in = (unsigned)ya < (unsigned)P2B_TH, yb_in = (unsigned)yb < (unsigned)P2B_TH;
-            const bool xa_in = (unsigned)xa < (unsigned)P2B_TW, xb_in = (unsigned)xb < (unsigned)P2B_TW;
-            const float wa = (ya_in && xa_in) ? t.wa * r : 0.0f, wb = (yb_in && xa_in) ? t.wb * r : 0.0f;
-            const float wc = (ya_in && xb_in) ? t.wc * r : 0.0f, wd = (yb_in && xb_in) ? t.wd * r : 0.0f;
-            if (wa == 0.0f && wb == 0.0f && wc == 0.0f && wd == 0.0f) continue;
-#pragma unroll
-            for (int p = 0; p < PL; ++p) {
-                if (p0 + p >= planes) break;
-                const float g = gerp[(size_t)(p0 + p) * erp_plane + pix];
-                if (wa != 0.0f) atomicAdd(&acc[p][ya * P2B_TW + xa], g * wa);
-                if (wb != 0.0f) atomicAdd(&acc[p][yb * P2B_TW + xa], g * wb);
-                if (wc != 0.0f) atomicAdd(&acc[p][ya * P2B_TW + xb], g * wc);
-                if (wd != 0.0f) atomicAdd(&acc[p][yb * P2B_TW + xb], g * wd);
-            }
-        }
-    }
-    __syncthreads();                                               // the LDS adds of every wave are done
-    float* gp = (float*)const_cast<void*>(a.pers);
-#pragma unroll
-    for (int p = 0; p < PL; ++p) {
-        if (p0 + p >= planes) break;
-        const size_t pb = (size_t)((p0 + p) / a.C) * a.sB + (size_t)((p0 + p) % a.C) * a.sC + (size_t)n * a.sN;
-        for (int e = lane; e < P2B_TH * P2B_TW; e += NT) {
-            const int y = ty0 + e / P2B_TW, x = tx0 + e % P2B_TW;
-            if (y < a.ph && x < a.pw) gp[pb + (size_t)y * a.sY + (size_t)x * a.sX] = acc[p][e];
-        }
-    }
-}
-}  // namespace
-
-int omni_p2e_build_bwd(omni_geometry* g, hipStream_t stream)
-{
-    P2EArgs a;
-    int rc = fill_args(a, g, nullptr, nullptr, nullptr, 1, 1, OMNI_LAYOUT_BNCHW);
-    if (rc != OMNI_OK) return rc;
-    g->p2e_btx = (g->pw + P2B_TW - 1) / P2B_TW; g->p2e_bty = (g->ph + P2B_TH - 1) / P2B_TH;
-    const size_t ntiles = (size_t)g->N * g->p2e_btx * g->p2e_bty;
-    if (ntiles == 0 || ntiles >= (1u << 30)) return OMNI_OK;       // no table: the scatter kernel serves this geometry
-    OMNI_HIP(hipMalloc((void**)&g->p2e_bwd_box, sizeof(int4) * ntiles));
-    OMNI_HIP(hipMalloc((void**)&g->p2e_rden, sizeof(float) * (size_t)g->H * g->W));
-    std::vector<int4> init(ntiles, make_int4(0x7fffffff, -0x7fffffff, 0x7fffffff, -0x7fffffff));
-    OMNI_HIP(hipMemcpy(g->p2e_bwd_box, init.data(), sizeof(int4) * ntiles, hipMemcpyHostToDevice));
-    const int rows4 = (g->H + 3) / 4;
-    hipLaunchKernelGGL(p2e_bwd_box_kernel, dim3(rows4 * g->ntx), dim3(256), 0, stream, a, (int*)g->p2e_bwd_box, g->p2e_rden, g->p2e_btx, g->p2e_bty);
-    OMNI_HIP(hipGetLastError());
-    OMNI_HIP(hipStreamSynchronize(stream));
-    std::vector<int4> hb(ntiles);
-    OMNI_HIP(hipMemcpy(hb.data(), g->p2e_bwd_box, sizeof(int4) * ntiles, hipMemcpyDeviceToHost));
-    std::vector<int> small, big;
-    for (size_t t = 0; t < ntiles; ++t) {
-        const long long npx = hb[t].x <= hb[t].y ? (long long)(hb[t].y - hb[t].x + 1) * (hb[t].w - hb[t].z + 1) : 0;
-        (npx <= 2048 ? small : big).push_back((int)t);
-    }
-    g->p2e_bwd_nsmall = (int)small.size(); g->p2e_bwd_nbig = (int)big.size();
-    if (omni_options().e2p_verbose) {
-        long long ps = 0, pb = 0, mx = 0;
-        for (size_t t = 0; t < ntiles; ++t) {
-            const long long npx = hb[t].x <= hb[t].y ? (long long)(hb[t].y - hb[t].x + 1) * (hb[t].w - hb[t].z + 1) : 0;
-            (npx <= 2048 ? ps : pb) += npx; mx = npx > mx ? npx : mx;
-        }
-        fprintf(stderr, "[omni] pers2equi backward boxes (%dx%d ERP, %dx%d patches): %zu tiles, %d big; box pixels small %lld big %lld, largest %lld\n",
-                g->H, g->W, g->ph, g->pw, ntiles, g->p2e_bwd_nbig, ps, pb, mx);
-    }
-    small.insert(small.end(), big.begin(), big.end());
-    OMNI_HIP(hipMalloc((void**)&g->p2e_bwd_ids, sizeof(int) * ntiles));
-    OMNI_HIP(hipMemcpy(g->p2e_bwd_ids, small.data(), sizeof(int) * ntiles, hipMemcpyHostToDevice));
-    g->p2e_bwd_ok = 1;
-    // the sparse-matrix form (the default): rows = patch pixels.  (ERP pixel indices must fit the 24-bit source field.)
-    const long long nrows = (long long)g->N * g->ph * g->pw;
-    if (nrows < (1ll << 31) && (long long)g->H * g->W <= (1ll << 24)) {
-        SpBuilder sb;
-        rc = sb.begin(&g->p2e_sp, (int)nrows, stream);
-        if (rc != OMNI_OK) return rc;
-        hipLaunchKernelGGL(p2e_sp_walk_kernel, dim3(rows4 * g->ntx), dim3(256), 0, stream, a, (const float*)g->p2e_rden, sb.emit(0));
-        OMNI_HIP(hipGetLastError());
-        OMNI_HIP(hipStreamSynchronize(stream));
-        bool fits = false;
-        rc = sb.layout((size_t)omni_options().bwd_table_mb << 20, &fits, stream);
-        if (rc != OMNI_OK) return rc;
-        if (fits) {
-            hipLaunchKernelGGL(p2e_sp_walk_kernel, dim3(rows4 * g->ntx), dim3(256), 0, stream, a, (const float*)g->p2e_rden, sb.emit(1));
-            OMNI_HIP(hipGetLastError());
-            OMNI_HIP(hipStreamSynchronize(stream));
-            rc = sb.finish(stream);
-            if (rc != OMNI_OK) return rc;
-        } else omni_sp_free(g->p2e_sp);
-        if (omni_options().e2p_verbose)
-            fprintf(stderr, "[omni] pers2equi backward as a sparse matrix: %d rows, %lld entries (%lld with padding) + %d long rows with %lld entries%s\n",
-                    g->p2e_sp.nrows, g->p2e_sp.nent, g->p2e_sp.npadded, g->p2e_sp.nlong, g->p2e_sp.nlong_ent, fits ? "" : " -> over the table budget, not kept");
-    }
-    return OMNI_OK;
-}
-
-extern "C" int omni_pers2equi_bwd(const void* grad_erp, void* grad_pers, int dtype, int B, int C, int ph, int pw,
-                                  int H, int W, int nrows, float fov_h, float fov_w, int layout, omni_stream_t stream)
-{
-    if (dtype != OMNI_F32) OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_pers2equi_bwd: fp32 only");
-    const omni_geometry* g = nullptr;
-    int rc = omni_geometry_lookup(&g, nrows, fov_h, fov_w, ph, pw, H, W, (hipStream_t)stream);
-    if (rc != OMNI_OK) return rc;
-    rc = check_common(g, B, C, "omni_pers2equi_bwd");
-    if (rc != OMNI_OK) return rc;
-    if (B == 0 || C == 0) return OMNI_OK;
-    if (!grad_erp || !grad_pers) OMNI_FAIL(OMNI_ERR_INVALID, "omni_pers2equi_bwd: null device pointer");
-    P2EArgs a;
-    rc = fill_args(a, g, grad_pers, nullptr, const_cast<void*>(grad_erp), B, C, layout);
-    if (rc != OMNI_OK) return rc;
-    {   // first backward of this geometry: build its tables (synchronises the stream once)
-        omni_geometry* gm = const_cast<omni_geometry*>(g);
-        std::lock_guard<std::mutex> lk(gm->bwd_mu);
-        if (!gm->p2e_bwd_tried) {
-            gm->p2e_bwd_tried = 1;
-            rc = omni_p2e_build_bwd(gm, (hipStream_t)stream);
-            if (rc != OMNI_OK) return rc;
-        }
-    }
-    if (g->p2e_sp.ok && omni_options().p2e_bwd_simple == 0 && a.sY == (long long)pw * a.sX) {
-        SpApply s;
-        s.src = (const float*)grad_erp; s.dst = (float*)grad_pers; s.C = C; s.planes = B * C;
-        s.s_sB = (long long)C * H * W; s.s_sC = (long long)H * W; s.s_hi = 0; s.s_lo = 1;
-        s.d_sB = a.sB; s.d_sC = a.sC; s.rdiv = ph * pw; s.d_hi = a.sN; s.d_lo = (int)a.sX;
-        s.PT = (B * C + 3) / 4 * 4; s.nhi = 1; s.nlo = H * W; s.hi_fastest = 0; s.chunk = 16;
-        float* ws = nullptr;
-        if (omni_options().bwd_wide) {
-            // reference layout: the gathers write the planar form into the scratch, p2e_nlast_kernel turns it N-innermost
-            const size_t n1 = (size_t)H * W * s.PT, n2 = layout == OMNI_LAYOUT_BCHWN ? (size_t)B * C * g->N * ph * pw : 0;
-            rc = omni_bwd_workspace(const_cast<omni_geometry*>(g), (hipStream_t)stream, (n1 + n2) * sizeof(float), &ws);
-            if (rc != OMNI_OK) return rc;
-            if (n2) {
-                const long long pp = (long long)ph * pw;
-                s.dst = ws + n1; s.d_sB = (long long)g->N * C * pp; s.d_sC = pp; s.d_hi = C * pp; s.d_lo = 1;
-                rc = sp_apply(g->p2e_sp, s, (hipStream_t)stream, ws);
-                if (rc != OMNI_OK) return rc;
-                hipLaunchKernelGGL(p2e_nlast_kernel, dim3((unsigned)((pp + 63) / 64), (unsigned)(B * C)), dim3(256), sizeof(float) * 64 * (g->N | 1), (hipStream_t)stream,
-                                   (const float*)(ws + n1), (float*)grad_pers, g->N, (int)pp, C);
-                OMNI_HIP(hipGetLastError());
-                return OMNI_OK;
-            }
-        }
-        return sp_apply(g->p2e_sp, s, (hipStream_t)stream, ws);
-    }
-    if (g->p2e_bwd_ok && omni_options().p2e_bwd_simple != 1) {
-        constexpr int PL = 4;
-        const int groups = (B * C + PL - 1) / PL;
-        if (g->p2e_bwd_nbig)                                      // first: they are the long ones
-            hipLaunchKernelGGL((p2e_bwd_gather_kernel<PL, 1024>), dim3(g->p2e_bwd_nbig, groups), dim3(1024), 0, (hipStream_t)stream, a,
-                               (const int4*)g->p2e_bwd_box, (const float*)g->p2e_rden, (const int*)g->p2e_bwd_ids + g->p2e_bwd_nsmall,
-                               g->p2e_btx, g->p2e_bty, B * C);
-        if (g->p2e_bwd_nsmall)
-            hipLaunchKernelGGL((p2e_bwd_gather_kernel<PL, 64>), dim3(g->p2e_bwd_nsmall, groups), dim3(64), 0, (hipStream_t)stream, a,
-                               (const int4*)g->p2e_bwd_box, (const float*)g->p2e_rden, (const int*)g->p2e_bwd_ids, g->p2e_btx, g->p2e_bty, B * C);
-        OMNI_HIP(hipGetLastError());
-        return OMNI_OK;
-    }
-    OMNI_HIP(hipMemsetAsync(grad_pers, 0, (size_t)B * C * g->N * ph * pw * sizeof(float), (hipStream_t)stream));
-    const int rows4 = (g->H + 3) / 4, nblocks = rows4 * g->ntx;
-    hipLaunchKernelGGL(p2e_bwd_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, a, nblocks);
-    OMNI_HIP(hipGetLastError());
-    return OMNI_OK;
 }

@@ -11,7 +11,7 @@
 // sliced-ELL layout puts entry k of 64 consecutive rows side by side), one gather per entry and plane from a source that sits in L2, one
 // coalesced store per output element — no atomics anywhere, and the summation order is a constant of the geometry (entries sorted by source).
 //
-// Included by omni_pers2equi.hip and omni_equi2pers.hip (each walks its own taps to emit the entries; everything else is shared).
+// Included by omni_pers2equi_bwd.hip and omni_equi2pers_bwd.hip (each walks its own taps to emit the entries; everything else is shared).
 #pragma once
 #include <algorithm>
 #include <vector>

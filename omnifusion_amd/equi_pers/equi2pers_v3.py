@@ -11,9 +11,9 @@ Same name, arguments, return tuple, layouts and dtypes as the reference:
     returns   pers[B,C,h,w,N] (N innermost, contiguous), xyz[N,3,h,w], uv[N,2,h,w] on
               erp_img.device and center_p[N,2] on the CPU      (reference :82,118,122)
 
-All arithmetic runs in libomnifusion_hip.so (csrc/omni_equi2pers.hip) on the caller's
+All arithmetic runs in libomnifusion_hip.so (csrc/omni_equi2pers.hip; this layout's kernels: csrc/omni_e2p_ref.hip) on the caller's
 current stream.  Like the reference's (which autograd differentiates through F.grid_sample, :111), `pers` is
-differentiable w.r.t. `erp_img` (float32): the backward is the HIP scatter kernel `omni_equi2pers_bwd`.
+differentiable w.r.t. `erp_img` (float32): the backward is the HIP scatter kernel `omni_equi2pers_bwd` (csrc/omni_equi2pers_bwd.hip).
 Errors: ValueError for bad nrows/shape/dtype/device (the reference raises
 UnboundLocalError for an unsupported nrows), RuntimeError for HIP failures.
 """

@@ -8,8 +8,8 @@
                ./grid/<layer_name>.pth table cache (:24-29); nothing is written to disk here.
     returns    Tensor[B,C,H,W] on pers_img.device
 
-All arithmetic runs in libomnifusion_hip.so (csrc/omni_pers2equi.hip).  Differentiable w.r.t. `pers_img` (float32) like
-the reference's indexing gathers (:174-196): the backward is the HIP scatter kernel `omni_pers2equi_bwd`.
+All arithmetic runs in libomnifusion_hip.so (csrc/omni_pers2equi.hip; tables: csrc/omni_p2e_tables.hip).  Differentiable w.r.t. `pers_img` (float32) like
+the reference's indexing gathers (:174-196): the backward is the HIP scatter kernel `omni_pers2equi_bwd` (csrc/omni_pers2equi_bwd.hip).
 """
 import ctypes
 

@@ -1,6 +1,8 @@
 #!/bin/bash
 # Investigation build (never the product): the library with packed fp32 arithmetic ALLOWED in the files named on the command line
-# (default omni_pers2equi.hip), every other object as the product has it.  -> tools/pk/libomnifusion_pk.so
+# (default omni_pers2equi.hip: the pers2equi blend kernels — their table builders and backward are omni_p2e_tables.hip and omni_pers2equi_bwd.hip, the
+# equi2pers kernels omni_equi2pers.hip, omni_e2p_ref.hip, omni_e2p_tables.hip, omni_equi2pers_bwd.hip), every other object as the product has it.
+# -> tools/pk/libomnifusion_pk.so
 # extra hipcc flags for the packed files: PKFLAGS
 cd "$(dirname "$0")/.."; C=omnifusion_amd/csrc; O=tools/pk; mkdir -p $O
 PK=${@:-omni_pers2equi.hip}

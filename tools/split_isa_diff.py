@@ -1,12 +1,17 @@
 """Same machine code after a source split: compares the gfx950 device code of two builds kernel by kernel (no GPU needed).
 
-    python tools/split_isa_diff.py PARENT_CSRC [CHILD_CSRC] [-q]
+    python tools/split_isa_diff.py PARENT_CSRC [CHILD_CSRC] [-q] [--parent-obj NAME.o ...]
 
 PARENT_CSRC / CHILD_CSRC: directories holding the objects of a finished build (`python -m omnifusion_amd.build`), the child's default being
-this tree's omnifusion_amd/csrc.  The kernels compared are those of the parent's omni_conv_sh.o; on the child side they may live in any object.
+this tree's omnifusion_amd/csrc.  The kernels compared are those of the parent objects named with --parent-obj (repeatable; default
+omni_conv_sh.o, the split of the convolution units; the resampling split: --parent-obj omni_equi2pers.o --parent-obj omni_pers2equi.o; the
+debug build: the .dbg.o names); on the child side they may live in any object of the same build.
 
 Checked, per kernel: the name exists on both sides, in exactly ONE child object; the instruction sequence is identical (address / encoding
-comments stripped, as tests/test_precision_f16x1.py does); the register, LDS and scratch figures of isa.kernel_meta are equal.
+comments stripped, as tests/test_precision_f16x1.py does); the register, LDS and scratch figures of isa.kernel_meta are equal.  The child
+units — every object that holds one of these kernels — together hold NO kernel the parent objects together do not.  A kernel that several parent
+objects hold (the anonymous-namespace kernels of omni_spgather.h, compiled once per operator) must be in as many child objects, and every parent
+copy is matched with a child copy of its own.
 
 ONE difference is tolerated and printed site by site (-q: a count per kernel): the literal of a pc-relative address formation
     s_getpc_b64 s[n:n+1]; s_add_u32 sn, sn, LIT; s_addc_u32 sn+1, sn+1, LIT
@@ -14,6 +19,7 @@ whose target lies OUTSIDE the kernel on both sides — the distance to a symbol 
 sh_overflow_flag), which moves when the kernels around it do.  A formation that lands INSIDE the kernel (a long branch) must match exactly.
 Exit status 1 on any other difference.
 """
+import argparse
 import collections
 import glob
 import os
@@ -71,66 +77,84 @@ def external_sites(start, end, body):
     return sites
 
 
+def compare(short, pk, pm, ck, cm):
+    """([difference], [normalised literal]) between one parent copy and one child copy of a kernel: (start, end, body) and its isa.kernel_meta entry"""
+    (ps, pe, pb), (cs, ce, cb) = pk, ck
+    bad, notes = [], []
+    for key in META:
+        if pm.get(key, 0) != cm.get(key, 0):
+            bad.append(f"{short}: {key} {pm.get(key, 0)} -> {cm.get(key, 0)}")
+    if len(pb) != len(cb):
+        return bad + [f"{short}: {len(pb)} instructions -> {len(cb)}"], notes
+    psites, csites = external_sites(ps, pe, pb), external_sites(cs, ce, cb)
+    both = set(psites) & set(csites)
+    for i, ((_, pi), (_, ci)) in enumerate(zip(pb, cb)):
+        if pi == ci:
+            continue
+        site = i if i in both else i - 1 if i - 1 in both else None      # the s_add_u32 of a formation, or the s_addc_u32 behind it
+        if site is not None and pi.rsplit(",", 1)[0] == ci.rsplit(",", 1)[0]:
+            notes.append(f"  normalised {short}+{pb[i][0] - ps:#x}: `{pi}` -> `{ci}` (targets {psites[site] - ps:+#x} / {csites[site] - cs:+#x} from the kernel's start: outside it)")
+            continue
+        bad.append(f"{short}+{pb[i][0] - ps:#x}: `{pi}` -> `{ci}`")
+        break
+    return bad, notes
+
+
+def copies(objs):
+    """{kernel name: [(object's base name, (start, end, body), meta)]} over the given objects"""
+    out = collections.OrderedDict()
+    for obj in objs:
+        meta = {k["name"]: k for k in isa.kernel_meta(obj)}
+        for n, k in kernels(obj).items():
+            out.setdefault(n, []).append((os.path.basename(obj), k, meta[n]))
+    return out
+
+
 def main():
-    args = [a for a in sys.argv[1:] if not a.startswith("-")]
-    quiet = "-q" in sys.argv
-    if not args:
-        sys.exit(__doc__)
-    parent_dir = args[0]
-    child_dir = args[1] if len(args) > 1 else os.path.join(ROOT, "omnifusion_amd", "csrc")
-    pobj = os.path.join(parent_dir, "omni_conv_sh.o")
-    parent = kernels(pobj)
-    pmeta = {k["name"]: k for k in isa.kernel_meta(pobj)}
-    child, cmeta, where = {}, {}, collections.defaultdict(list)
-    for obj in sorted(glob.glob(os.path.join(child_dir, "*.o"))):
-        if obj.endswith(".dbg.o") or os.path.basename(obj) == "omni_debug.o":
-            continue
-        ks = kernels(obj)
-        for n in ks:
-            where[n].append(os.path.basename(obj))
-        child.update(ks)
-        cmeta.update({k["name"]: k for k in isa.kernel_meta(obj)})
+    ap = argparse.ArgumentParser(usage=__doc__)
+    ap.add_argument("parent_dir")
+    ap.add_argument("child_dir", nargs="?", default=os.path.join(ROOT, "omnifusion_amd", "csrc"))
+    ap.add_argument("-q", dest="quiet", action="store_true")
+    ap.add_argument("--parent-obj", action="append")
+    opt = ap.parse_args()
+    pobjs = opt.parent_obj or ["omni_conv_sh.o"]
+    label = " + ".join(pobjs)
+    debug = pobjs[0].endswith(".dbg.o")                              # like with like: the debug build's objects, or the product's
+    parent = copies([os.path.join(opt.parent_dir, o) for o in pobjs])
+    child = copies([o for o in sorted(glob.glob(os.path.join(opt.child_dir, "*.o")))
+                    if o.endswith(".dbg.o") == debug and not os.path.basename(o).startswith("omni_debug.")])
+    where = {n: [u for u, _, _ in c] for n, c in child.items()}
     bad = []
-    for n in parent:
-        if len(where[n]) != 1:
-            bad.append(f"{n}: in {len(where[n])} child objects {where[n]}")
-    units = sorted({w for n in parent for w in where[n]})
-    extra = [n for u in units for n, w in where.items() if u in w and n not in parent]
-    for n in extra:
-        bad.append(f"{n}: in the child's conv units but not in the parent's omni_conv_sh.o")
-    total = nsites = 0
+    units = sorted({u for n in parent for u in where.get(n, [])})
+    for u in units:
+        for n, w in where.items():
+            if u in w and n not in parent:
+                bad.append(f"{n}: in the child's units ({', '.join(units)}) but not in the parent's {label}")
+    total = nsites = nkernels = 0
     per_unit = collections.Counter()
-    for n, (ps, pe, pb) in parent.items():
-        if len(where[n]) != 1:
+    for n, pcopies in parent.items():
+        # ONE child object per parent object that holds the kernel: exactly one, but for the kernels of a header that several parent objects
+        # compile (omni_spgather.h: once per operator), which must be in as many child objects — and every parent copy gets a child copy of its own
+        if len(where.get(n, [])) != len(pcopies):
+            bad.append(f"{n}: in {len(pcopies)} parent object(s) but {len(where.get(n, []))} child objects {where.get(n, [])}")
             continue
-        cs, ce, cb = child[n]
-        per_unit[where[n][0]] += 1
-        total += len(pb)
         short = re.sub(r"^_ZN12_GLOBAL__N_1\d+", "", n)
-        for key in META:
-            if pmeta[n].get(key, 0) != cmeta[n].get(key, 0):
-                bad.append(f"{short}: {key} {pmeta[n].get(key, 0)} -> {cmeta[n].get(key, 0)}")
-        if len(pb) != len(cb):
-            bad.append(f"{short}: {len(pb)} instructions -> {len(cb)}")
-            continue
-        psites, csites = external_sites(ps, pe, pb), external_sites(cs, ce, cb)
-        both = set(psites) & set(csites)
-        count = 0
-        for i, ((_, pi), (_, ci)) in enumerate(zip(pb, cb)):
-            if pi == ci:
-                continue
-            site = i if i in both else i - 1 if i - 1 in both else None      # the s_add_u32 of a formation, or the s_addc_u32 behind it
-            if site is not None and pi.rsplit(",", 1)[0] == ci.rsplit(",", 1)[0]:
-                count += 1
-                if not quiet:
-                    print(f"  normalised {short}+{pb[i][0] - ps:#x}: `{pi}` -> `{ci}` (targets {psites[site] - ps:+#x} / {csites[site] - cs:+#x} from the kernel's start: outside it)")
-                continue
-            bad.append(f"{short}+{pb[i][0] - ps:#x}: `{pi}` -> `{ci}`")
-            break
-        nsites += count
-        if quiet and count:
-            print(f"  normalised {count:3d} external pc-relative literals in {short}")
-    print(f"{len(parent)} kernels, {total} instructions in the parent's omni_conv_sh.o; child: " + ", ".join(f"{u} {c}" for u, c in sorted(per_unit.items())))
+        left = list(child[n])
+        for pname, pk, pm in pcopies:
+            results = [compare(short, pk, pm, ck, cm) for _, ck, cm in left]
+            pick = next((i for i, r in enumerate(results) if not r[0]), 0)
+            diffs, notes = results[pick]
+            unit = left.pop(pick)[0]
+            nkernels += 1
+            per_unit[unit] += 1
+            total += len(pk[2])
+            nsites += len(notes)
+            bad += [f"{d} ({pname} -> {unit})" for d in diffs]
+            if opt.quiet and notes:
+                print(f"  normalised {len(notes):3d} external pc-relative literals in {short}")
+            elif notes:
+                print("\n".join(notes))
+    print(f"{nkernels} kernels, {total} instructions in the parent's {label}; child: " + ", ".join(f"{u} {c}" for u, c in sorted(per_unit.items())))
     print(f"{nsites} literals normalised (pc-relative addresses of symbols outside the kernel), nothing else")
     for b in bad:
         print("DIFFERENT:", b)
