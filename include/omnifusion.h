@@ -313,6 +313,28 @@ int omni_masked_median_f32(const float* x, const float* mask, size_t n, unsigned
 int omni_depth_metrics_f32(float* pred, const float* gt, const float* mask, const float* scale_num, const float* scale_den,
                            size_t n, double* ws, float* out, omni_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Semantic segmentation (csrc/omni_semantic.hip): the supervision and scoring of train_erp_sem.py:203-210, 261-278 and
+ * iou.py:21-24 in one pass over the logits.  logits: float32 [B, C, HW] (contiguous NCHW), 2 <= C <= 64; target: int64 [B, HW].
+ * Pixel rules: target == ignore_index is outside the loss; a negative label is outside the matrix; a label
+ * that is neither ignored nor a class index is dropped from both and counted in n_bad.  Nothing synchronises the host.
+ * ---------------------------------------------------------------------------------------------- */
+/* bytes of the workspace that carries the valid count, n_bad and the per-pixel log-sum-exp from the step to the gradient:
+ * int64 count at offset 0, int64 n_bad at offset 8 (both written by every call) */
+size_t omni_semantic_workspace_bytes(size_t npix);
+/* *loss = mean over the valid pixels of lse(logits) - logits[target] (F.cross_entropy; NaN when no pixel is valid);
+ * pred [B, HW] int64 = argmax over C (first index of the maximum, a NaN counts as the maximum), NULL = not written;
+ * confusion [K, K] int64 += count of (pred, target) pairs (rows = predictions), NULL = not counted.  K = 0 means C; C <= K <= 64. */
+int omni_semantic_step_f32(const float* logits, const int64_t* target, int B, int C, size_t HW, int64_t ignore_index, int K,
+                           void* workspace, float* loss, int64_t* pred, int64_t* confusion, omni_stream_t stream);
+/* grad_logits = (softmax - onehot) * (*grad_out) / count on the valid pixels, 0 elsewhere; `workspace` as the step left it. */
+int omni_semantic_grad_f32(const float* logits, const int64_t* target, int B, int C, size_t HW, int64_t ignore_index,
+                           const void* workspace, const float* grad_out, float* grad_logits, omni_stream_t stream);
+/* confusion [K, K] int64 += count of (pred, gt) pairs of two int64 label maps of n pixels, 1 <= K <= 64 (iou.py:21-24); gt < 0 is
+ * skipped, a pair with gt >= K or pred outside [0, K) is dropped and counted in *n_bad (device int64, accumulated; NULL = not counted). */
+int omni_confusion_matrix_i64(const int64_t* pred, const int64_t* gt, size_t n, int K, int64_t* confusion, int64_t* n_bad,
+                              omni_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Host-facing ends of the hot path, csrc/omni_io.hip.
  *

@@ -45,6 +45,7 @@ EXPORTS = [
     "omni_photometric_grad_f32",
     "omni_freeview_rotations", "omni_freeview_equi2pers_f32", "omni_freeview_pers2equi_f32", "omni_freeview_merge_f32",
     "omni_freeview_bwd_workspace_bytes", "omni_freeview_equi2pers_bwd_f32", "omni_freeview_pers2equi_bwd_f32", "omni_freeview_merge_bwd_f32",
+    "omni_semantic_workspace_bytes", "omni_semantic_step_f32", "omni_semantic_grad_f32", "omni_confusion_matrix_i64",
 ]
 
 
@@ -89,6 +90,12 @@ def load():
     lib.omni_freeview_equi2pers_bwd_f32.argtypes = [vp] * 3 + [ci] * 7 + [cf, cf, ci, vp, vp]
     lib.omni_freeview_pers2equi_bwd_f32.argtypes = [vp] * 3 + [ci] * 6 + [cf, cf, vp, vp]
     lib.omni_freeview_merge_bwd_f32.argtypes = [vp] * 3 + [ci] * 7 + [cf, cf, vp, vp]
+    sz, i64 = ctypes.c_size_t, ctypes.c_int64
+    lib.omni_semantic_workspace_bytes.restype = sz
+    lib.omni_semantic_workspace_bytes.argtypes = [sz]
+    lib.omni_semantic_step_f32.argtypes = [vp, vp, ci, ci, sz, i64, ci] + [vp] * 5
+    lib.omni_semantic_grad_f32.argtypes = [vp, vp, ci, ci, sz, i64] + [vp] * 4
+    lib.omni_confusion_matrix_i64.argtypes = [vp, vp, sz, ci] + [vp] * 3
     for name in EXPORTS:
         getattr(lib, name)          # AttributeError here = header/library mismatch
     _lib = lib

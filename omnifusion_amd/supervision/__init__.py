@@ -1,4 +1,5 @@
-"""Host-side mirror of the reference's supervision/ (the losses of the depth training scripts and of view synthesis)."""
-from . import direct, photometric, splatting, ssim  # noqa: F401
+"""Host-side mirror of the reference's supervision/ (the losses of the depth and segmentation training scripts and of view synthesis)."""
+from . import direct, photometric, semantic, splatting, ssim  # noqa: F401
 from .photometric import PhotometricLossParameters, calculate_loss  # noqa: F401
+from .semantic import cross_entropy, segmentation_step  # noqa: F401
 from .ssim import ssim_loss  # noqa: F401
