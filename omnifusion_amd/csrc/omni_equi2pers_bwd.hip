@@ -1,5 +1,5 @@
-// omni_equi2pers_bwd.hip — backward of equi2pers (omni_equi2pers.hip): the scatter kernel e2p_bwd_kernel, the transposed LDS-box kernel
-// (e2p_lds_kernel<TS, true>, omni_e2p_common.h), the backward by gathers and the sparse-matrix form (omni_spgather.h), their tables and omni_equi2pers_bwd.
+// omni_equi2pers_bwd.hip — backward of equi2pers (omni_equi2pers.hip): the scatter kernel e2p_bwd_kernel, the transposed LDS-box kernel (e2p_lds_kernel<TS, true>,
+// omni_e2p_common.h), the backward by gathers, the walk kernel that emits the entries of the sparse-matrix form (applied by omni_spgather.hip), their tables and omni_equi2pers_bwd.
 #include "omni_e2p_common.h"
 #include "omni_spgather.h"
 
@@ -169,54 +169,21 @@ int omni_e2p_build_bwd(omni_geometry* g, hipStream_t stream)
     const size_t ntiles = (size_t)g->e2p_gtx * g->e2p_gty, nbox = ntiles * g->N;
     const long long total = (long long)g->N * g->ph * g->pw;
     if (ntiles == 0 || nbox >= (1u << 28) || total >= (1ll << 31)) return OMNI_OK;
-    OMNI_HIP(hipMalloc((void**)&g->e2p_bwd_box, sizeof(int4) * nbox));
-    std::vector<int4> hb(nbox, make_int4(0x7fffffff, -0x7fffffff, 0x7fffffff, -0x7fffffff));
-    OMNI_HIP(hipMemcpy(g->e2p_bwd_box, hb.data(), sizeof(int4) * nbox, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(e2p_bwd_box_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a, (int*)g->e2p_bwd_box, g->e2p_gtx, (int)total);
-    OMNI_HIP(hipGetLastError());
-    OMNI_HIP(hipStreamSynchronize(stream));
-    OMNI_HIP(hipMemcpy(hb.data(), g->e2p_bwd_box, sizeof(int4) * nbox, hipMemcpyDeviceToHost));
-    std::vector<int> small, big;
-    long long ps = 0, pb = 0, mx = 0;
-    for (size_t t = 0; t < ntiles; ++t) {
-        long long npx = 0;
-        for (int n = 0; n < g->N; ++n) {
-            const int4 b = hb[t * g->N + n];
-            if (b.x <= b.y) npx += (long long)(b.y - b.x + 1) * (b.w - b.z + 1);
-        }
-        (npx <= 4096 ? small : big).push_back((int)t);
-        (npx <= 4096 ? ps : pb) += npx; mx = npx > mx ? npx : mx;
-    }
+    BwdBoxes bx;
+    int rc = omni_bwd_boxes(&g->e2p_bwd_box, &g->e2p_bwd_ids, ntiles, g->N, 4096, stream, &bx, [&](int4* boxes) {
+        hipLaunchKernelGGL(e2p_bwd_box_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a, (int*)boxes, g->e2p_gtx, (int)total);
+        return OMNI_OK;
+    });
+    if (rc != OMNI_OK) return rc;
     if (omni_options().e2p_verbose)
         fprintf(stderr, "[omni] equi2pers backward boxes (%dx%d ERP, %d patches %dx%d): %zu tiles, %zu big; box samples small %lld big %lld, largest %lld\n",
-                g->H, g->W, g->N, g->ph, g->pw, ntiles, big.size(), ps, pb, mx);
-    g->e2p_bwd_nsmall = (int)small.size(); g->e2p_bwd_nbig = (int)big.size();
-    small.insert(small.end(), big.begin(), big.end());
-    OMNI_HIP(hipMalloc((void**)&g->e2p_bwd_ids, sizeof(int) * ntiles));
-    OMNI_HIP(hipMemcpy(g->e2p_bwd_ids, small.data(), sizeof(int) * ntiles, hipMemcpyHostToDevice));
-    g->e2p_bwd_ok = 1;
+                g->H, g->W, g->N, g->ph, g->pw, ntiles, (size_t)bx.nbig, bx.ps, bx.pb, bx.mx);
+    g->e2p_bwd_nsmall = bx.nsmall; g->e2p_bwd_nbig = bx.nbig; g->e2p_bwd_ok = 1;
     // the sparse-matrix form (the default): rows = ERP pixels, sources = patch samples (patch in the high 8 bits, sample in the low 24)
-    if ((long long)g->H * g->W < (1ll << 31) && (long long)g->ph * g->pw <= (1ll << 24) && g->N < 256) {
-        SpBuilder sb;
-        int rc = sb.begin(&g->e2p_sp, g->H * g->W, stream);
-        if (rc != OMNI_OK) return rc;
-        hipLaunchKernelGGL(e2p_sp_walk_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a, (int)total, sb.emit(0));
-        OMNI_HIP(hipGetLastError());
-        OMNI_HIP(hipStreamSynchronize(stream));
-        bool fits = false;
-        rc = sb.layout((size_t)omni_options().bwd_table_mb << 20, &fits, stream);
-        if (rc != OMNI_OK) return rc;
-        if (fits) {
-            hipLaunchKernelGGL(e2p_sp_walk_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a, (int)total, sb.emit(1));
-            OMNI_HIP(hipGetLastError());
-            OMNI_HIP(hipStreamSynchronize(stream));
-            rc = sb.finish(stream);
-            if (rc != OMNI_OK) return rc;
-        } else omni_sp_free(g->e2p_sp);
-        if (omni_options().e2p_verbose)
-            fprintf(stderr, "[omni] equi2pers backward as a sparse matrix: %d rows, %lld entries (%lld with padding) + %d long rows with %lld entries%s\n",
-                    g->e2p_sp.nrows, g->e2p_sp.nent, g->e2p_sp.npadded, g->e2p_sp.nlong, g->e2p_sp.nlong_ent, fits ? "" : " -> over the table budget, not kept");
-    }
+    if ((long long)g->H * g->W < (1ll << 31) && (long long)g->ph * g->pw <= (1ll << 24) && g->N < 256)
+        return omni_sp_build(&g->e2p_sp, g->H * g->W, (size_t)omni_options().bwd_table_mb << 20, stream, "equi2pers", [&](SpEmit e) {
+            hipLaunchKernelGGL(e2p_sp_walk_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a, (int)total, e);
+        });
     return OMNI_OK;
 }
 
@@ -232,15 +199,8 @@ extern "C" int omni_equi2pers_bwd(const void* grad_pers, void* grad_erp, int dty
     if (B == 0 || C == 0) return OMNI_OK;
     if (!grad_pers || !grad_erp) OMNI_FAIL(OMNI_ERR_INVALID, "omni_equi2pers_bwd: null device pointer");
     E2PArgs a; fill_args(a, g, grad_erp, const_cast<void*>(grad_pers), B, C);
-    {   // first backward of this geometry: build its tables (synchronises the stream once)
-        omni_geometry* gm = const_cast<omni_geometry*>(g);
-        std::lock_guard<std::mutex> lk(gm->bwd_mu);
-        if (!gm->e2p_bwd_tried) {
-            gm->e2p_bwd_tried = 1;
-            rc = omni_e2p_build_bwd(gm, (hipStream_t)stream);
-            if (rc != OMNI_OK) return rc;
-        }
-    }
+    rc = omni_bwd_build_once(g, &omni_geometry::e2p_bwd_tried, omni_e2p_build_bwd, (hipStream_t)stream);   // first backward of this geometry: its tables
+    if (rc != OMNI_OK) return rc;
     const int mode = omni_options().e2p_bwd_simple;
     if (g->e2p_sp.ok && (mode == 0 || mode == 4)) {               // the sparse-matrix gather: no atomics, nothing to zero
         SpApply s;
@@ -256,7 +216,7 @@ extern "C" int omni_equi2pers_bwd(const void* grad_pers, void* grad_erp, int dty
                 rc = omni_bwd_workspace(const_cast<omni_geometry*>(g), (hipStream_t)stream, (size_t)g->N * pp * s.PT * sizeof(float), &ws);
                 if (rc != OMNI_OK) return rc;
             }
-            return sp_apply(g->e2p_sp, s, (hipStream_t)stream, ws);
+            return omni_sp_apply(g->e2p_sp, s, (hipStream_t)stream, ws);
         }
     }
     // without the table, mode 0: whichever is faster for the layout — measured at B = 8, cfg 1: planar 0.74 ms (LDS boxes + coalesced global atomics) vs

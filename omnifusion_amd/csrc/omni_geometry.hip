@@ -266,17 +266,6 @@ int omni_bwd_workspace(omni_geometry* g, hipStream_t stream, size_t bytes, float
     return OMNI_OK;
 }
 
-void omni_sp_free(OmniSpTable& t)
-{
-    if (t.ent) (void)hipFree(t.ent);
-    if (t.slice_off) (void)hipFree(t.slice_off);
-    if (t.cnt) (void)hipFree(t.cnt);
-    if (t.long_ent) (void)hipFree(t.long_ent);
-    if (t.long_off) (void)hipFree(t.long_off);
-    if (t.long_row) (void)hipFree(t.long_row);
-    t = OmniSpTable();
-}
-
 extern "C" void omni_geometry_destroy(omni_geometry_t* g)
 {
     if (!g) return;

@@ -45,7 +45,7 @@ struct OmniOptions {
     int e2p_gather;       // OMNI_E2P_GATHER     1: equi2pers always takes the direct-gather kernel (no LDS staging)
     int e2p_notab;        // OMNI_E2P_NOTAB      1: no per-geometry sampling-coordinate table
     int e2p_verbose;      // OMNI_E2P_VERBOSE    1: print tile statistics when a geometry handle is built
-    int e2p_bwd_simple;   // OMNI_E2P_BWD_SIMPLE 0 (default) | 4: the sparse-matrix gather (omni_spgather.h; no atomics, fixed summation order) | 1: plain scatter | 2: LDS boxes + global atomics | 3: ERP-tile gathers with LDS atomics
+    int e2p_bwd_simple;   // OMNI_E2P_BWD_SIMPLE 0 (default) | 4: the sparse-matrix gather (omni_spgather.hip; no atomics, fixed summation order) | 1: plain scatter | 2: LDS boxes + global atomics | 3: ERP-tile gathers with LDS atomics
     int p2e_bwd_simple;   // OMNI_P2E_BWD_SIMPLE 0 (default): the sparse-matrix gather | 1: global atomics (the round-1 kernel) | 2: patch-tile gathers with LDS atomics
     int p2e_gather;       // OMNI_P2E_GATHER     1: pers2equi always takes the direct-gather kernel (no LDS staging) | 2: never (not even for ONE plane of a large ERP)
     int e2p_nbuf;         // OMNI_E2P_NBUF       LDS ring slots (boxes in flight) per wave of the equi2pers LDS kernel: 0 auto | 1 | 2 | 4
@@ -99,7 +99,7 @@ struct PatchTab {
     float cphi[OMNI_MAX_PATCH];
 };
 
-// A linear operator of the geometry as a sparse matrix in sliced-ELL form (omni_spgather.h): rows in slices of 64 (one per lane of a wave), slice s
+// A linear operator of the geometry as a sparse matrix in sliced-ELL form (built, applied and freed by omni_spgather.hip): rows in slices of 64 (one per lane of a wave), slice s
 // holds K_s = slice_off[s+1] - slice_off[s] entries per row, entry k of row r at ent[(slice_off[s] * 64) + k * 64 + (r & 63)]; cnt[r] of them are
 // real.  Rows with more than OMNI_SP_LMAX entries (patch pixels at a pole: a whole ERP row maps onto them) live in a CSR side list instead
 // (cnt[r] = -1) and get a wave each.  Entries of a row are sorted by source index: the summation order is a constant of the geometry.
@@ -110,7 +110,7 @@ struct OmniSpTable {
     int nrows = 0, nslices = 0, nlong = 0, ok = 0;
     long long nent = 0, npadded = 0, nlong_ent = 0;
 };
-void omni_sp_free(OmniSpTable& t);
+void omni_sp_free(OmniSpTable& t);                                                           // omni_spgather.hip
 struct omni_geometry;
 int omni_bwd_workspace(omni_geometry* g, hipStream_t stream, size_t bytes, float** out);    // omni_geometry.hip
 
@@ -150,7 +150,7 @@ struct omni_geometry {
     float2* e2p_ixy;               // equi2pers: clamped sampling coordinates (ix, iy) of every patch sample [N][ph][pw]
     // equi2pers backward by gathers (omni_equi2pers_bwd.hip): per (4 x 32 ERP tile, patch) the box of the patch samples whose taps touch the tile
     int4* e2p_bwd_box; int* e2p_bwd_ids; int e2p_bwd_nsmall, e2p_bwd_nbig, e2p_gtx, e2p_gty, e2p_bwd_ok;
-    // the backward operators as constant sparse matrices (omni_spgather.h): one row per OUTPUT element, entries (source index, weight)
+    // the backward operators as constant sparse matrices (omni_spgather.hip): one row per OUTPUT element, entries (source index, weight)
     OmniSpTable p2e_sp, e2p_sp;
     // scratch of the backward calls (the plane-interleaved copy of the gradient they gather from): one buffer per stream that has called,
     // grown on demand (never under capture), freed with the handle

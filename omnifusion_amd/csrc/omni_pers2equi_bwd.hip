@@ -1,5 +1,5 @@
-// omni_pers2equi_bwd.hip — backward of pers2equi (omni_pers2equi.hip): the scatter kernel p2e_bwd_kernel, the backward by gathers and the sparse-matrix
-// form (omni_spgather.h), their tables and omni_pers2equi_bwd.
+// omni_pers2equi_bwd.hip — backward of pers2equi (omni_pers2equi.hip): the scatter kernel p2e_bwd_kernel, the backward by gathers, the walk kernel that
+// emits the entries of the sparse-matrix form (applied by omni_spgather.hip), their tables and omni_pers2equi_bwd.
 #include "omni_p2e_common.h"
 #include "omni_spgather.h"
 
@@ -231,58 +231,24 @@ int omni_p2e_build_bwd(omni_geometry* g, hipStream_t stream)
     g->p2e_btx = (g->pw + P2B_TW - 1) / P2B_TW; g->p2e_bty = (g->ph + P2B_TH - 1) / P2B_TH;
     const size_t ntiles = (size_t)g->N * g->p2e_btx * g->p2e_bty;
     if (ntiles == 0 || ntiles >= (1u << 30)) return OMNI_OK;       // no table: the scatter kernel serves this geometry
-    OMNI_HIP(hipMalloc((void**)&g->p2e_bwd_box, sizeof(int4) * ntiles));
-    OMNI_HIP(hipMalloc((void**)&g->p2e_rden, sizeof(float) * (size_t)g->H * g->W));
-    std::vector<int4> init(ntiles, make_int4(0x7fffffff, -0x7fffffff, 0x7fffffff, -0x7fffffff));
-    OMNI_HIP(hipMemcpy(g->p2e_bwd_box, init.data(), sizeof(int4) * ntiles, hipMemcpyHostToDevice));
     const int rows4 = (g->H + 3) / 4;
-    hipLaunchKernelGGL(p2e_bwd_box_kernel, dim3(rows4 * g->ntx), dim3(256), 0, stream, a, (int*)g->p2e_bwd_box, g->p2e_rden, g->p2e_btx, g->p2e_bty);
-    OMNI_HIP(hipGetLastError());
-    OMNI_HIP(hipStreamSynchronize(stream));
-    std::vector<int4> hb(ntiles);
-    OMNI_HIP(hipMemcpy(hb.data(), g->p2e_bwd_box, sizeof(int4) * ntiles, hipMemcpyDeviceToHost));
-    std::vector<int> small, big;
-    for (size_t t = 0; t < ntiles; ++t) {
-        const long long npx = hb[t].x <= hb[t].y ? (long long)(hb[t].y - hb[t].x + 1) * (hb[t].w - hb[t].z + 1) : 0;
-        (npx <= 2048 ? small : big).push_back((int)t);
-    }
-    g->p2e_bwd_nsmall = (int)small.size(); g->p2e_bwd_nbig = (int)big.size();
-    if (omni_options().e2p_verbose) {
-        long long ps = 0, pb = 0, mx = 0;
-        for (size_t t = 0; t < ntiles; ++t) {
-            const long long npx = hb[t].x <= hb[t].y ? (long long)(hb[t].y - hb[t].x + 1) * (hb[t].w - hb[t].z + 1) : 0;
-            (npx <= 2048 ? ps : pb) += npx; mx = npx > mx ? npx : mx;
-        }
+    BwdBoxes bx;
+    rc = omni_bwd_boxes(&g->p2e_bwd_box, &g->p2e_bwd_ids, ntiles, 1, 2048, stream, &bx, [&](int4* boxes) {
+        OMNI_HIP(hipMalloc((void**)&g->p2e_rden, sizeof(float) * (size_t)g->H * g->W));     // (the kernel's other output: 1 / L1 norm per ERP pixel)
+        hipLaunchKernelGGL(p2e_bwd_box_kernel, dim3(rows4 * g->ntx), dim3(256), 0, stream, a, (int*)boxes, g->p2e_rden, g->p2e_btx, g->p2e_bty);
+        return OMNI_OK;
+    });
+    if (rc != OMNI_OK) return rc;
+    g->p2e_bwd_nsmall = bx.nsmall; g->p2e_bwd_nbig = bx.nbig; g->p2e_bwd_ok = 1;
+    if (omni_options().e2p_verbose)
         fprintf(stderr, "[omni] pers2equi backward boxes (%dx%d ERP, %dx%d patches): %zu tiles, %d big; box pixels small %lld big %lld, largest %lld\n",
-                g->H, g->W, g->ph, g->pw, ntiles, g->p2e_bwd_nbig, ps, pb, mx);
-    }
-    small.insert(small.end(), big.begin(), big.end());
-    OMNI_HIP(hipMalloc((void**)&g->p2e_bwd_ids, sizeof(int) * ntiles));
-    OMNI_HIP(hipMemcpy(g->p2e_bwd_ids, small.data(), sizeof(int) * ntiles, hipMemcpyHostToDevice));
-    g->p2e_bwd_ok = 1;
+                g->H, g->W, g->ph, g->pw, ntiles, g->p2e_bwd_nbig, bx.ps, bx.pb, bx.mx);
     // the sparse-matrix form (the default): rows = patch pixels.  (ERP pixel indices must fit the 24-bit source field.)
     const long long nrows = (long long)g->N * g->ph * g->pw;
-    if (nrows < (1ll << 31) && (long long)g->H * g->W <= (1ll << 24)) {
-        SpBuilder sb;
-        rc = sb.begin(&g->p2e_sp, (int)nrows, stream);
-        if (rc != OMNI_OK) return rc;
-        hipLaunchKernelGGL(p2e_sp_walk_kernel, dim3(rows4 * g->ntx), dim3(256), 0, stream, a, (const float*)g->p2e_rden, sb.emit(0));
-        OMNI_HIP(hipGetLastError());
-        OMNI_HIP(hipStreamSynchronize(stream));
-        bool fits = false;
-        rc = sb.layout((size_t)omni_options().bwd_table_mb << 20, &fits, stream);
-        if (rc != OMNI_OK) return rc;
-        if (fits) {
-            hipLaunchKernelGGL(p2e_sp_walk_kernel, dim3(rows4 * g->ntx), dim3(256), 0, stream, a, (const float*)g->p2e_rden, sb.emit(1));
-            OMNI_HIP(hipGetLastError());
-            OMNI_HIP(hipStreamSynchronize(stream));
-            rc = sb.finish(stream);
-            if (rc != OMNI_OK) return rc;
-        } else omni_sp_free(g->p2e_sp);
-        if (omni_options().e2p_verbose)
-            fprintf(stderr, "[omni] pers2equi backward as a sparse matrix: %d rows, %lld entries (%lld with padding) + %d long rows with %lld entries%s\n",
-                    g->p2e_sp.nrows, g->p2e_sp.nent, g->p2e_sp.npadded, g->p2e_sp.nlong, g->p2e_sp.nlong_ent, fits ? "" : " -> over the table budget, not kept");
-    }
+    if (nrows < (1ll << 31) && (long long)g->H * g->W <= (1ll << 24))
+        return omni_sp_build(&g->p2e_sp, (int)nrows, (size_t)omni_options().bwd_table_mb << 20, stream, "pers2equi", [&](SpEmit e) {
+            hipLaunchKernelGGL(p2e_sp_walk_kernel, dim3(rows4 * g->ntx), dim3(256), 0, stream, a, (const float*)g->p2e_rden, e);
+        });
     return OMNI_OK;
 }
 
@@ -300,15 +266,8 @@ extern "C" int omni_pers2equi_bwd(const void* grad_erp, void* grad_pers, int dty
     P2EArgs a;
     rc = fill_args(a, g, grad_pers, nullptr, const_cast<void*>(grad_erp), B, C, layout);
     if (rc != OMNI_OK) return rc;
-    {   // first backward of this geometry: build its tables (synchronises the stream once)
-        omni_geometry* gm = const_cast<omni_geometry*>(g);
-        std::lock_guard<std::mutex> lk(gm->bwd_mu);
-        if (!gm->p2e_bwd_tried) {
-            gm->p2e_bwd_tried = 1;
-            rc = omni_p2e_build_bwd(gm, (hipStream_t)stream);
-            if (rc != OMNI_OK) return rc;
-        }
-    }
+    rc = omni_bwd_build_once(g, &omni_geometry::p2e_bwd_tried, omni_p2e_build_bwd, (hipStream_t)stream);   // first backward of this geometry: its tables
+    if (rc != OMNI_OK) return rc;
     if (g->p2e_sp.ok && omni_options().p2e_bwd_simple == 0 && a.sY == (long long)pw * a.sX) {
         SpApply s;
         s.src = (const float*)grad_erp; s.dst = (float*)grad_pers; s.C = C; s.planes = B * C;
@@ -324,7 +283,7 @@ extern "C" int omni_pers2equi_bwd(const void* grad_erp, void* grad_pers, int dty
             if (n2) {
                 const long long pp = (long long)ph * pw;
                 s.dst = ws + n1; s.d_sB = (long long)g->N * C * pp; s.d_sC = pp; s.d_hi = C * pp; s.d_lo = 1;
-                rc = sp_apply(g->p2e_sp, s, (hipStream_t)stream, ws);
+                rc = omni_sp_apply(g->p2e_sp, s, (hipStream_t)stream, ws);
                 if (rc != OMNI_OK) return rc;
                 hipLaunchKernelGGL(p2e_nlast_kernel, dim3((unsigned)((pp + 63) / 64), (unsigned)(B * C)), dim3(256), sizeof(float) * 64 * (g->N | 1), (hipStream_t)stream,
                                    (const float*)(ws + n1), (float*)grad_pers, g->N, (int)pp, C);
@@ -332,7 +291,7 @@ extern "C" int omni_pers2equi_bwd(const void* grad_erp, void* grad_pers, int dty
                 return OMNI_OK;
             }
         }
-        return sp_apply(g->p2e_sp, s, (hipStream_t)stream, ws);
+        return omni_sp_apply(g->p2e_sp, s, (hipStream_t)stream, ws);
     }
     if (g->p2e_bwd_ok && omni_options().p2e_bwd_simple != 1) {
         constexpr int PL = 4;

@@ -327,3 +327,52 @@ def test_backward_without_tables_falls_back():
         assert bool(torch.isfinite(res[1][k]).all())
         d = (res[0][k] - res[1][k]).abs().max().item()
         assert d <= 2e-5 * max(1.0, res[0][k].abs().max().item()), (k, d)
+
+
+def test_backward_operators_keep_their_tables_apart():
+    """both operators reach their sparse tables and the stream's scratch through one unit (omni_spgather.hip): the table and the scratch of one are
+    untouched by the other.  On a fresh geometry handle, e2p, p2e, e2p, p2e on one stream: the second result of each equals the first bit for
+    bit, and both equal the same call on a handle whose OTHER operator never built its tables (a new handle of the SAME geometry: the cache is
+    cleared; a handle of another fov computes another operator, so it cannot give the bits to compare with).  A second geometry that differs only
+    in fov — another handle, its own tables and scratch on the same stream — is used in between the four calls and must not disturb them either.
+    64 x 128 ERP, 18 patches of 32 x 32, B * C = 3, planar layout."""
+    _, _, _, L = _ops()
+    import ctypes
+    lib = L.load()
+    P_ = lambda t: ctypes.c_void_p(t.data_ptr())
+    B, C, nrows, P, H, W, N = 1, 3, 4, 32, 64, 128, 18
+    f80, f81 = ctypes.c_float(80), ctypes.c_float(81)
+    gp = torch.rand((B, N, C, P, P), device=DEV); ge = torch.rand((B, C, H, W), device=DEV)
+    s = torch.cuda.Stream()
+    sp = ctypes.c_void_p(s.cuda_stream)
+    torch.cuda.synchronize()
+
+    def e2p(fov=f80):
+        out = torch.full((B, C, H, W), float("nan"), device=DEV)
+        assert lib.omni_equi2pers_bwd(P_(gp), P_(out), 0, B, C, H, W, P, P, nrows, fov, fov, L.LAYOUT_BNCHW, sp) == 0, lib.omni_last_error()
+        return out
+
+    def p2e(fov=f80):
+        out = torch.full((B, N, C, P, P), float("nan"), device=DEV)
+        assert lib.omni_pers2equi_bwd(P_(ge), P_(out), 0, B, C, P, P, H, W, nrows, fov, fov, L.LAYOUT_BNCHW, sp) == 0, lib.omni_last_error()
+        return out
+
+    try:
+        with torch.cuda.stream(s):
+            lib.omni_geometry_cache_clear()
+            e_alone = e2p()                                            # this handle never builds the pers2equi tables
+            s.synchronize()
+            lib.omni_geometry_cache_clear()
+            p_alone = p2e()                                            # ... and this one never the equi2pers tables
+            s.synchronize()
+            lib.omni_geometry_cache_clear()
+            e1, p1 = e2p(), p2e()
+            other = (p2e(f81), e2p(f81))                               # the second geometry, in between
+            e2, p2 = e2p(), p2e()
+        s.synchronize()
+    finally:
+        lib.omni_geometry_cache_clear()
+    assert all(bool(torch.isfinite(t).all()) for t in (e1, p1) + other)
+    assert not torch.equal(other[1], e1) and not torch.equal(other[0], p1)      # (it IS another operator)
+    assert torch.equal(e1, e2) and torch.equal(p1, p2)
+    assert torch.equal(e1, e_alone) and torch.equal(p1, p_alone)

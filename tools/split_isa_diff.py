@@ -1,6 +1,6 @@
 """Same machine code after a source split: compares the gfx950 device code of two builds kernel by kernel (no GPU needed).
 
-    python tools/split_isa_diff.py PARENT_CSRC [CHILD_CSRC] [-q] [--parent-obj NAME.o ...]
+    python tools/split_isa_diff.py PARENT_CSRC [CHILD_CSRC] [-q] [--parent-obj NAME.o ...] [--merged-copies]
 
 PARENT_CSRC / CHILD_CSRC: directories holding the objects of a finished build (`python -m omnifusion_amd.build`), the child's default being
 this tree's omnifusion_amd/csrc.  The kernels compared are those of the parent objects named with --parent-obj (repeatable; default
@@ -10,8 +10,15 @@ debug build: the .dbg.o names); on the child side they may live in any object of
 Checked, per kernel: the name exists on both sides, in exactly ONE child object; the instruction sequence is identical (address / encoding
 comments stripped, as tests/test_precision_f16x1.py does); the register, LDS and scratch figures of isa.kernel_meta are equal.  The child
 units — every object that holds one of these kernels — together hold NO kernel the parent objects together do not.  A kernel that several parent
-objects hold (the anonymous-namespace kernels of omni_spgather.h, compiled once per operator) must be in as many child objects, and every parent
+objects hold (anonymous-namespace kernels of a header that more than one unit compiles) must be in as many child objects, and every parent
 copy is matched with a child copy of its own.
+
+--merged-copies (off by default: the rule above is the strict one) is for the change that gives such a header a unit of its own (the
+sparse-gather kernels: --parent-obj omni_equi2pers_bwd.o --parent-obj omni_pers2equi_bwd.o, child omni_spgather.o): a kernel that several
+parent objects hold may then be in ONE child object, if every parent copy is identical to that copy and to the other parent copies.  Kernels
+are then paired by names in which an argument type of the kernel's own anonymous namespace (`NS_7SpApplyE`) reads like a global one (`7SpApply`):
+a type that leaves the anonymous namespace because it now crosses units (SpApply, the argument block of those kernels) changes the mangled name
+of every kernel that takes it, not its code.  A name that does not pair this way fails the comparison like any missing kernel.
 
 ONE difference is tolerated and printed site by site (-q: a count per kernel): the literal of a pc-relative address formation
     s_getpc_b64 s[n:n+1]; s_add_u32 sn, sn, LIT; s_addc_u32 sn+1, sn+1, LIT
@@ -100,13 +107,26 @@ def compare(short, pk, pm, ck, cm):
     return bad, notes
 
 
-def copies(objs):
-    """{kernel name: [(object's base name, (start, end, body), meta)]} over the given objects"""
+def global_types(name):
+    """the mangled kernel name with every `NS_<length><identifier>E` (a type of the kernel's own anonymous namespace) as `<length><identifier>`"""
+    out, i = "", 0
+    for m in re.finditer(r"NS_(\d+)", name):
+        end = m.end() + int(m.group(1))
+        if m.start() >= i and name[end:end + 1] == "E":
+            out += name[i:m.start()] + name[m.start() + 3:end]
+            i = end + 1
+    return out + name[i:]
+
+
+def copies(objs, merged=False):
+    """{kernel name: [(object's base name, (start, end, body), meta)]} over the given objects; merged: the names of --merged-copies"""
     out = collections.OrderedDict()
     for obj in objs:
         meta = {k["name"]: k for k in isa.kernel_meta(obj)}
-        for n, k in kernels(obj).items():
-            out.setdefault(n, []).append((os.path.basename(obj), k, meta[n]))
+        ks = kernels(obj)
+        keys = [global_types(n) if merged else n for n in ks]
+        for key, (n, k) in zip(keys, ks.items()):
+            out.setdefault(key, []).append((os.path.basename(obj), k, meta[n]))
     return out
 
 
@@ -116,13 +136,14 @@ def main():
     ap.add_argument("child_dir", nargs="?", default=os.path.join(ROOT, "omnifusion_amd", "csrc"))
     ap.add_argument("-q", dest="quiet", action="store_true")
     ap.add_argument("--parent-obj", action="append")
+    ap.add_argument("--merged-copies", action="store_true")
     opt = ap.parse_args()
     pobjs = opt.parent_obj or ["omni_conv_sh.o"]
     label = " + ".join(pobjs)
     debug = pobjs[0].endswith(".dbg.o")                              # like with like: the debug build's objects, or the product's
-    parent = copies([os.path.join(opt.parent_dir, o) for o in pobjs])
+    parent = copies([os.path.join(opt.parent_dir, o) for o in pobjs], opt.merged_copies)
     child = copies([o for o in sorted(glob.glob(os.path.join(opt.child_dir, "*.o")))
-                    if o.endswith(".dbg.o") == debug and not os.path.basename(o).startswith("omni_debug.")])
+                    if o.endswith(".dbg.o") == debug and not os.path.basename(o).startswith("omni_debug.")], opt.merged_copies)
     where = {n: [u for u, _, _ in c] for n, c in child.items()}
     bad = []
     units = sorted({u for n in parent for u in where.get(n, [])})
@@ -135,11 +156,16 @@ def main():
     for n, pcopies in parent.items():
         # ONE child object per parent object that holds the kernel: exactly one, but for the kernels of a header that several parent objects
         # compile (omni_spgather.h: once per operator), which must be in as many child objects — and every parent copy gets a child copy of its own
-        if len(where.get(n, [])) != len(pcopies):
+        # (--merged-copies: or in ONE child object that every parent copy equals)
+        merged = opt.merged_copies and len(pcopies) > 1 and len(where.get(n, [])) == 1
+        if len(where.get(n, [])) != len(pcopies) and not merged:
             bad.append(f"{n}: in {len(pcopies)} parent object(s) but {len(where.get(n, []))} child objects {where.get(n, [])}")
             continue
         short = re.sub(r"^_ZN12_GLOBAL__N_1\d+", "", n)
-        left = list(child[n])
+        left = list(child[n]) * (len(pcopies) if merged else 1)        # merged: every parent copy against the ONE child copy,
+        if merged:                                                     # and the parent copies against each other
+            for pname, pk, pm in pcopies[1:]:
+                bad += [f"{d} ({pcopies[0][0]} / {pname}: the parent's own copies)" for d in compare(short, pcopies[0][1], pcopies[0][2], pk, pm)[0]]
         for pname, pk, pm in pcopies:
             results = [compare(short, pk, pm, ck, cm) for _, ck, cm in left]
             pick = next((i for i, r in enumerate(results) if not r[0]), 0)
