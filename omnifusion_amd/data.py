@@ -99,6 +99,9 @@ class DeviceFeeder:
                         "ready": torch.cuda.Event(), "free": None} for _ in range(self.depth)]
         self._outs = [torch.empty((B, 3, H, W), dtype=torch.float32, device=self.device) for _ in range(self._nout)]
         self._done = [None] * self._nout
+        # the frames come from the CURRENT stream's allocator pool and are written on the side stream: a block that work still queued on the
+        # current stream writes to (a forward's freed intermediates: the host runs a whole forward ahead) must not take the first copy early
+        self.side.wait_stream(torch.cuda.current_stream(self.device))
 
     def _stage(self, slot, frames):
         s = self._slots[slot]

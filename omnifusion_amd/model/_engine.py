@@ -361,6 +361,56 @@ class Engine:
             return out
         return self._conv(self._up(x, M, H, Wd, C, Ho, Wo), key, M, Ho, Wo, C, Cout, 3, 1, 1, act, out_f32=out_f32, out=out)
 
+    def transformer(self, d, bs):
+        """The transformer over the N tokens of each panorama (:263-268): position embedding, six blocks, encoder_norm.
+        d: fp32 [bs*N, P/32, P/32, 32] (the `down` projection of layer4).  Returns the fp32 token matrix [bs*N, 512]."""
+        lib = _lib.load()
+        dev = d.device
+        self._s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        self._bs = bs
+        N, P32 = self.npatches, self.patch_size[0] // 32
+        M = bs * N
+        sh = self.sh
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+        tok = new(M, 512)
+        _lib.check(lib.omni_token_pack_f32(_p(d), _p(self.w["pos"]), _p(tok), M, N, P32 * P32, 32, self._s), "token_pack")
+        normed = None                                                # LayerNorm(tok) for the NEXT consumer, when fc2's second pass has already made it
+        pending = None                                               # a lone panorama: fc2's K slices (parts, slices, bias key, residual) — the next consumer adds them up
+        for i in range(6):
+            t = f"t{i}."
+            if sh:                                                   # LN / attention emit SH, the GEMMs run f16x3 from it
+                if pending is not None:
+                    tok, qkv = self._ln_gemm_parts(pending, t + "norm1.weight", t + "norm1.bias", 1e-5, t + "attn.qkv.w16", M, 1536)
+                    pending = None
+                elif normed is not None:
+                    qkv = self._gemm_sh(normed, t + "attn.qkv.w16", None, M, 512, 1536)
+                else:
+                    qkv = self._ln_gemm_sh(tok, t + "norm1.weight", t + "norm1.bias", 1e-5, t + "attn.qkv.w16", None, M, 1536)
+                att = new(M, 512)
+                _lib.check(lib.omni_attention_qkv_sh(_p(qkv), _p(att), bs, N, self._s), "attention")
+                tok = self._gemm_sh(att, t + "attn.proj.w16", t + "attn.proj.bias", M, 512, 512, res=tok)
+                h = self._ln_gemm_sh(tok, t + "norm2.weight", t + "norm2.bias", 1e-5, t + "mlp.fc1.w16", t + "mlp.fc1.bias", M, 2048, act=ACT_GELU, out_sh=True)
+                nxt = (f"t{i + 1}.norm1.weight", f"t{i + 1}.norm1.bias", 1e-5, True) if i < 5 else ("enc_norm.w", "enc_norm.b", 1e-6, False)
+                tok, normed, pending = self._fc2_ln(h, t + "mlp.fc2.w16", t + "mlp.fc2.bias", M, tok, nxt)
+                continue
+            y = self._ln(tok, t + "norm1.weight", t + "norm1.bias", M, 1e-5)
+            q = self._gemm(y, t + "attn.q.weight", None, M, 512, 512)
+            kv = self._gemm(y, t + "attn.kv.weight", None, M, 512, 1024)
+            att = new(M, 512)
+            _lib.check(lib.omni_attention_f32(_p(q), _p(kv), _p(att), bs, N, self._s), "attention")
+            tok = self._gemm(att, t + "attn.proj.weight", t + "attn.proj.bias", M, 512, 512, res=tok)
+            y = self._ln(tok, t + "norm2.weight", t + "norm2.bias", M, 1e-5)
+            h = self._gemm(y, t + "mlp.fc1.weight", t + "mlp.fc1.bias", M, 512, 2048, act=ACT_GELU)
+            tok = self._gemm(h, t + "mlp.fc2.weight", t + "mlp.fc2.bias", M, 2048, 512, res=tok)
+        if sh and pending is not None:                                 # the last fc2's K slices: sum + bias + residual + encoder_norm in one kernel
+            parts, S, bkey, res_tok = pending
+            tok_sum, tok = new(M, 512), new(M, 512)
+            _lib.check(lib.omni_splitk_reduce_ln512(_p(parts), S, _p(self.w[bkey]), _p(res_tok), _p(tok_sum), _p(self.w["enc_norm.w"]), _p(self.w["enc_norm.b"]),
+                                                    ctypes.c_float(1e-6), _p(tok), 0, M, self._s), "reduce+ln")
+        else:
+            tok = normed if (sh and normed is not None) else self._ln(tok, "enc_norm.w", "enc_norm.b", M, 1e-6)
+        return tok
+
     # ------------------------------------------------------------------ network over the patch batch
     def network(self, patches, point_feat, bs, confidence, out=None):
         """patches: planar [bs, N, 3, P, P]; point_feat: NHWC [N or bs*N, P/4, P/4, 64].
@@ -412,43 +462,7 @@ class Engine:
             raise RuntimeError(f"patch size {P}: token dim {32 * P32 * P32} != 512 — the reference network only exists at "
                                "patch size 128 (SURVEY.md finding 0.1)")
         d = self._conv(layer4, "down", M, P32, P32, 512, 32, 1, 1, 0, ACT_NONE, out_f32=True)
-        tok = new(M, 512)
-        _lib.check(lib.omni_token_pack_f32(_p(d), _p(self.w["pos"]), _p(tok), M, N, P32 * P32, 32, self._s), "token_pack")
-        normed = None                                                # LayerNorm(tok) for the NEXT consumer, when fc2's second pass has already made it
-        pending = None                                               # a lone panorama: fc2's K slices (parts, slices, bias key, residual) — the next consumer adds them up
-        for i in range(6):
-            t = f"t{i}."
-            if sh:                                                   # LN / attention emit SH, the GEMMs run f16x3 from it
-                if pending is not None:
-                    tok, qkv = self._ln_gemm_parts(pending, t + "norm1.weight", t + "norm1.bias", 1e-5, t + "attn.qkv.w16", M, 1536)
-                    pending = None
-                elif normed is not None:
-                    qkv = self._gemm_sh(normed, t + "attn.qkv.w16", None, M, 512, 1536)
-                else:
-                    qkv = self._ln_gemm_sh(tok, t + "norm1.weight", t + "norm1.bias", 1e-5, t + "attn.qkv.w16", None, M, 1536)
-                att = new(M, 512)
-                _lib.check(lib.omni_attention_qkv_sh(_p(qkv), _p(att), bs, N, self._s), "attention")
-                tok = self._gemm_sh(att, t + "attn.proj.w16", t + "attn.proj.bias", M, 512, 512, res=tok)
-                h = self._ln_gemm_sh(tok, t + "norm2.weight", t + "norm2.bias", 1e-5, t + "mlp.fc1.w16", t + "mlp.fc1.bias", M, 2048, act=ACT_GELU, out_sh=True)
-                nxt = (f"t{i + 1}.norm1.weight", f"t{i + 1}.norm1.bias", 1e-5, True) if i < 5 else ("enc_norm.w", "enc_norm.b", 1e-6, False)
-                tok, normed, pending = self._fc2_ln(h, t + "mlp.fc2.w16", t + "mlp.fc2.bias", M, tok, nxt)
-                continue
-            y = self._ln(tok, t + "norm1.weight", t + "norm1.bias", M, 1e-5)
-            q = self._gemm(y, t + "attn.q.weight", None, M, 512, 512)
-            kv = self._gemm(y, t + "attn.kv.weight", None, M, 512, 1024)
-            att = new(M, 512)
-            _lib.check(lib.omni_attention_f32(_p(q), _p(kv), _p(att), bs, N, self._s), "attention")
-            tok = self._gemm(att, t + "attn.proj.weight", t + "attn.proj.bias", M, 512, 512, res=tok)
-            y = self._ln(tok, t + "norm2.weight", t + "norm2.bias", M, 1e-5)
-            h = self._gemm(y, t + "mlp.fc1.weight", t + "mlp.fc1.bias", M, 512, 2048, act=ACT_GELU)
-            tok = self._gemm(h, t + "mlp.fc2.weight", t + "mlp.fc2.bias", M, 2048, 512, res=tok)
-        if sh and pending is not None:                                 # the last fc2's K slices: sum + bias + residual + encoder_norm in one kernel
-            parts, S, bkey, res_tok = pending
-            tok_sum, tok = new(M, 512), new(M, 512)
-            _lib.check(lib.omni_splitk_reduce_ln512(_p(parts), S, _p(self.w[bkey]), _p(res_tok), _p(tok_sum), _p(self.w["enc_norm.w"]), _p(self.w["enc_norm.b"]),
-                                                    ctypes.c_float(1e-6), _p(tok), 0, M, self._s), "reduce+ln")
-        else:
-            tok = normed if (sh and normed is not None) else self._ln(tok, "enc_norm.w", "enc_norm.b", M, 1e-6)
+        tok = self.transformer(d, bs)
         _lib.check((lib.omni_add_hw_sh if sh else lib.omni_add_hw_f32)(_p(layer4), _p(tok), M, P32 * P32, 512, self._s), "token bias")
         # ---- decoder (:270-302); torch.cat is the two-source form of the conv
         up = self._up(layer4, M, P32, P32, 512, P16, P16)
