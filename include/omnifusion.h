@@ -265,6 +265,16 @@ int omni_stem_sh_f16x3(const float* src, const void* wt16, const float* bias, vo
 int omni_stem_sh_f16x1(const float* src, const void* wt16, const float* bias, void* dst, int M, int P, omni_stream_t stream);
 int omni_maxpool3x3s2_sh(const void* src, void* dst, int M, int H, int W, int C, omni_stream_t stream);
 int omni_upsample_bilinear_sh(const void* src, void* dst, int M, int H, int W, int C, int Ho, int Wo, omni_stream_t stream);
+/* conv3x3(F.interpolate(x, scale_factor 2, bilinear, align_corners=False), pad 1) from the nine 1x1 TAP PRODUCTS on the low-resolution map
+ * (both operators are linear): y fp32 [M][Hl][Wl][9][Cout], y[..., t, co] = sum_ci W[co][t][ci] * x[..., ci] with t = ky*3 + kx — the result of
+ * omni_conv2d_sh_f16x3_ws (1x1, 9*Cout outputs, no bias, fp32) on weights repacked tap-major, row t*Cout + co.  The kernel forms
+ *   dst[q] = act(bias + sum_t [q + t - 1 inside the 2Hl x 2Wl map] * up2(y_t)[q + t - 1]),   dst SH [M][2Hl][2Wl][Cout],
+ * reading y once (one image x 32 channels per block, staged in LDS), with the source index arithmetic of omni_upsample_bilinear_* and a fixed
+ * summation order: deterministic, and an image's bits do not depend on M.  Values are saturated to the SH range (omni_sh_overflow reports it).
+ * bias fp32 [Cout] or NULL; act OMNI_ACT_NONE or OMNI_ACT_RELU; tensors 16-byte aligned.
+ * Cout % 32 != 0, Hl * Wl > 64 or another activation: OMNI_ERR_UNSUPPORTED (omni_upsample_bilinear_sh + omni_conv2d_sh_f16x3_ws compute the
+ * same convolution); null tensors or an empty shape: OMNI_ERR_INVALID. */
+int omni_up2_tapsum_sh(const float* y, const float* bias, void* dst, int M, int Hl, int Wl, int Cout, int act, omni_stream_t stream);
 int omni_add_hw_sh(void* x, const float* y, int M, int HW, int C, omni_stream_t stream);
 int omni_add_period_sh(void* x, const float* y, size_t total, size_t period, omni_stream_t stream);
 /* nn.LayerNorm(512) with an SH result, and the attention core on a fused q|k|v projection [B*N, 1536] (q at column 0,

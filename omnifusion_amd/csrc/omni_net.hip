@@ -9,6 +9,7 @@
 //   attention       softmax(q k^T * 128^-1/2) v over the N tokens     model/blocks.py:50-62
 //   heads           pred (ReLU) / weight_pred (sigmoid) 3x3 32->1     :223-224,304-307
 //   mlp_points      1x1 conv 3->16->64 (+BN+ReLU) of xyz (* depth)    spherical_model_iterative.py:290-305,319,387-393
+#include <algorithm>
 #include "omni_internal.h"
 #include "omni_sh.h"
 
@@ -162,6 +163,67 @@ __global__ __launch_bounds__(256) void upsample_sh8_kernel(const unsigned char* 
     }
     unsigned char* d = dst + (((size_t)m * Ho + oy) * Wo + ox) * pp + coff;
     *reinterpret_cast<omni_h8v*>(d) = oh; *reinterpret_cast<omni_h8v*>(d + 64) = ol;
+}
+
+// ------------------------------------------------------------------ tap sum: conv3x3(upsample2x(x)) from nine 1x1 products on the LOW-RES map
+// y [M][Hl*Wl][9][Cout] fp32 holds Y_t = W_t . x per tap t = ky*3 + kx; both operators are linear, so
+//   out[q] = bias + sum_t [q + t - 1 inside the up-sampled map] * up2(Y_t)[q + t - 1]
+// Block = one image x one slab of 32 channels: its 9 * Hl*Wl rows of 128 bytes are staged in LDS once (pixel pitch 1152 bytes = 128 mod 256:
+// two neighbouring source pixels lie in opposite halves of the bank row), then thread = (output pixel, 4 channels) takes 9 taps x 4 bilinear
+// neighbours as 16-byte reads.  ds_read_b128 is served in the lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31} (+32): the lane -> pixel map
+// below gives every group TWO horizontally adjacent output pixels x 8 channel quads, whose source columns are equal (same addresses: broadcast)
+// or neighbours (other half of the bank row) — conflict-free.  Source index arithmetic of upsample_kernel; fixed summation order.
+constexpr int TS_SLAB = 32, TS_PITCH = 9 * TS_SLAB, TS_MAX_HW = 64;
+__global__ __launch_bounds__(256) void up2_tapsum_sh_kernel(const float* __restrict__ y, const float* __restrict__ bias, void* __restrict__ dst,
+                                                            int Hl, int Wl, int Cout, int act)
+{
+    extern __shared__ __attribute__((aligned(16))) float ts_img[];           // [Hl*Wl][9][32], the ONLY LDS object of this kernel
+    const int m = blockIdx.x, c0 = blockIdx.y * TS_SLAB, HW = Hl * Wl;
+    const float* src = y + (size_t)m * HW * 9 * Cout + c0;
+    const int nq = HW * 9 * (TS_SLAB / 4);                                   // 16-byte pieces: eight per (pixel, tap) row
+#pragma unroll 4
+    for (int i = threadIdx.x; i < nq; i += 256)
+        *reinterpret_cast<f4v*>(ts_img + i * 4) = *reinterpret_cast<const f4v*>(src + (size_t)(i >> 3) * Cout + (i & 7) * 4);
+    __syncthreads();
+    const int Ho = 2 * Hl, Wo = 2 * Wl, NP = Ho * Wo;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pi = ((lane >> 5) << 2) | ((0x31130220u >> (((lane >> 2) & 7) * 4)) & 3);      // pixel of the wave's eight; 4-lane chunks 0,3 | 5,6 | 1,2 | 4,7 share one
+    const int q = (lane & 7) * 4;
+    f4v bv = (f4v)(0.0f);
+    if (bias) bv = *reinterpret_cast<const f4v*>(bias + c0 + q);
+    for (int p = wave * 8 + pi; p < NP; p += 32) {                           // (Wo is even: pixels 2k and 2k+1 are in one row)
+        const int oy = p / Wo, ox = p - oy * Wo;
+        int yo0[3], yo1[3], xo0[3], xo1[3];
+        float ly[3], lx[3];
+        bool vy[3], vx[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int py = oy + k - 1, px = ox + k - 1;
+            vy[k] = (unsigned)py < (unsigned)Ho; vx[k] = (unsigned)px < (unsigned)Wo;
+            const float fy = fmaxf(0.5f * ((float)py + 0.5f) - 0.5f, 0.0f), fx = fmaxf(0.5f * ((float)px + 0.5f) - 0.5f, 0.0f);
+            const int y0 = (int)fy, x0 = (int)fx;                            // <= Hl - 1, Wl - 1 also one pixel outside the map (fy <= Hl - 0.25)
+            ly[k] = fy - (float)y0; lx[k] = fx - (float)x0;
+            yo0[k] = y0 * Wl * TS_PITCH; yo1[k] = (y0 + (y0 < Hl - 1 ? 1 : 0)) * Wl * TS_PITCH;
+            xo0[k] = x0 * TS_PITCH;      xo1[k] = (x0 + (x0 < Wl - 1 ? 1 : 0)) * TS_PITCH;
+        }
+        f4v acc = (f4v)(0.0f);
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                if (!(vy[ky] && vx[kx])) continue;
+                const float* b = ts_img + (ky * 3 + kx) * TS_SLAB + q;
+                const f4v v00 = *reinterpret_cast<const f4v*>(b + yo0[ky] + xo0[kx]), v01 = *reinterpret_cast<const f4v*>(b + yo0[ky] + xo1[kx]);
+                const f4v v10 = *reinterpret_cast<const f4v*>(b + yo1[ky] + xo0[kx]), v11 = *reinterpret_cast<const f4v*>(b + yo1[ky] + xo1[kx]);
+                const float hy = 1.0f - ly[ky], hx = 1.0f - lx[kx];
+                const float w00 = hy * hx, w01 = hy * lx[kx], w10 = ly[ky] * hx, w11 = ly[ky] * lx[kx];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[e] = fmaf(w11, v11[e], fmaf(w10, v10[e], fmaf(w01, v01[e], fmaf(w00, v00[e], acc[e]))));
+            }
+        f4v o = acc + bv;
+        if (act == OMNI_ACT_RELU) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
+        act_store4<true>(dst, (((size_t)m * Ho + oy) * Wo + ox) * Cout + c0 + q, o);
+    }
 }
 
 // x[m][hw][c] += y[m][c]            (token bias on layer4)
@@ -446,6 +508,27 @@ int omni_upsample_bilinear_sh(const void* src, void* dst, int M, int H, int W, i
     if (C % 32) OMNI_FAIL(OMNI_ERR_INVALID, "SH tensors need C % 32 == 0");
     hipLaunchKernelGGL(upsample_sh8_kernel, dim3(nblk((size_t)M * Ho * Wo * C / 8)), dim3(256), 0, S_, (const unsigned char*)src,
                        (unsigned char*)dst, M, H, W, C, Ho, Wo, (float)H / (float)Ho, (float)W / (float)Wo);
+    OMNI_HIP(hipGetLastError()); return OMNI_OK;
+}
+int omni_up2_tapsum_sh(const float* y, const float* bias, void* dst, int M, int Hl, int Wl, int Cout, int act, omni_stream_t stream)
+{
+    if (!y || !dst || M < 1 || Hl < 1 || Wl < 1 || Cout < 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_up2_tapsum_sh: null tensor or empty shape");
+    if ((uintptr_t)y % 16 || (uintptr_t)bias % 16 || (uintptr_t)dst % 16) OMNI_FAIL(OMNI_ERR_INVALID, "omni_up2_tapsum_sh: tensors must be 16-byte aligned");
+    if (Cout % TS_SLAB || Cout / TS_SLAB > 65535 || (long long)Hl * Wl > TS_MAX_HW || (act != OMNI_ACT_NONE && act != OMNI_ACT_RELU))
+        OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_up2_tapsum_sh: Cout % 32 == 0, Hl * Wl <= 64, no activation or ReLU");
+    const size_t lds = (size_t)Hl * Wl * TS_PITCH * sizeof(float);
+    if (lds > 64 * 1024) {                                                   // (more than 64 KiB of dynamic LDS must be asked for, once per device)
+        static std::mutex mu;
+        static std::vector<int> done;
+        int dev = 0;
+        OMNI_HIP(hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lk(mu);
+        if (std::find(done.begin(), done.end(), dev) == done.end()) {
+            OMNI_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(up2_tapsum_sh_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, TS_MAX_HW * TS_PITCH * (int)sizeof(float)));
+            done.push_back(dev);
+        }
+    }
+    hipLaunchKernelGGL(up2_tapsum_sh_kernel, dim3((unsigned)M, (unsigned)(Cout / TS_SLAB)), dim3(256), lds, S_, y, bias, dst, Hl, Wl, Cout, act);
     OMNI_HIP(hipGetLastError()); return OMNI_OK;
 }
 int omni_add_hw_sh(void* x, const float* y, int M, int HW, int C, omni_stream_t stream)

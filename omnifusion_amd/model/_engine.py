@@ -124,6 +124,9 @@ class Engine:
         for name in ("de_conv0_0", "de_conv0_1", "de_conv1_0", "de_conv1_1", "de_conv2_0", "de_conv2_1",
                      "de_conv3_0", "de_conv3_1", "de_conv4_0"):
             convbn(name, name + ".conv", name + ".bn")
+        for name in ("de_conv0_0", "de_conv1_0"):               # the same folded weights tap-major, [9*Cout][Cin] with row t*Cout + co = W[co][t][:]: the
+            w, _ = self._fold(sd, name + ".conv", name + ".bn")   # operand of the nine 1x1 tap products on the low-resolution map (_up_conv_taps)
+            W[name + ".taps.w16"] = split_weights_f16x3(w.permute(2, 3, 0, 1).reshape(9 * w.shape[0], w.shape[1]).to(torch.float32)).to(dev)
         down = "down1" if self.iterative else "down"
         W["down.w"] = f(sd[down + ".weight"].reshape(32, 512)); W["down.b"] = f(sd[down + ".bias"])
         W["down.w16"] = split_weights_f16x3(sd[down + ".weight"].reshape(32, 512)).to(dev)
@@ -361,6 +364,24 @@ class Engine:
             return out
         return self._conv(self._up(x, M, H, Wd, C, Ho, Wo), key, M, Ho, Wo, C, Cout, 3, 1, 1, act, out_f32=out_f32, out=out)
 
+    # Decoder stages that multiply BEFORE up-sampling: conv3x3(up2(x)) = tap sum of up2(W_t . x), nine 1x1 products on a quarter of the pixels
+    # (a quarter of the stage's matrix instructions; the up-sampled tensor never exists).  The set of layer keys that take this path; the
+    # operands exist for de_conv0_0 (K = 512) and de_conv1_0 (K = 128).  tools/taps_ab.py, three forwards of 8 panoramas in flight:
+    # de_conv0_0 3980 -> 4050 panoramas/s, every round above every round without; de_conv1_0 3980 -> 3975, its 42 MB of fp32 tap products
+    # cost what the matrix work saves, so it stays on the up-sampling path (profiles/EXPERIMENTS.md, r13a).  f16x3 only (the other modes'
+    # pinned accuracy figures stay); never a function of the batch size.  Results equal the two-kernel form to rounding (< 1e-5 m of depth).
+    taps_first = frozenset(("de_conv0_0",))
+
+    def _up_conv_taps(self, x, key, M, H, Wd, C, Cout, act):
+        """conv3x3(upsample2x(x)) for the stages in `taps_first`: tap GEMM on the low-resolution map + omni_up2_tapsum_sh; every other
+        case (mode, shape the tap-sum kernel does not serve) is the up-sampling kernel followed by the convolution."""
+        if key in self.taps_first and self.sh and self.terms == 3 and Cout % 32 == 0 and H * Wd <= 64:
+            y = self._conv(x, key + ".taps", M, H, Wd, C, 9 * Cout, 1, 1, 0, ACT_NONE, bias=False, out_f32=True)
+            out = torch.empty((M, 2 * H, 2 * Wd, Cout), dtype=torch.float32, device=x.device)
+            _lib.check(_lib.load().omni_up2_tapsum_sh(_p(y), _p(self.w[key + ".b"]), _p(out), M, H, Wd, Cout, act, self._s), "tap sum " + key)
+            return out
+        return self._conv(self._up(x, M, H, Wd, C, 2 * H, 2 * Wd), key, M, 2 * H, 2 * Wd, C, Cout, 3, 1, 1, act)
+
     def transformer(self, d, bs):
         """The transformer over the N tokens of each panorama (:263-268): position embedding, six blocks, encoder_norm.
         d: fp32 [bs*N, P/32, P/32, 32] (the `down` projection of layer4).  Returns the fp32 token matrix [bs*N, 512]."""
@@ -465,11 +486,9 @@ class Engine:
         tok = self.transformer(d, bs)
         _lib.check((lib.omni_add_hw_sh if sh else lib.omni_add_hw_f32)(_p(layer4), _p(tok), M, P32 * P32, 512, self._s), "token bias")
         # ---- decoder (:270-302); torch.cat is the two-source form of the conv
-        up = self._up(layer4, M, P32, P32, 512, P16, P16)
-        x = self._conv(up, "de_conv0_0", M, P16, P16, 512, 256, 3, 1, 1, ACT_RELU)
+        x = self._up_conv_taps(layer4, "de_conv0_0", M, P32, P32, 512, 256, ACT_RELU)
         x = self._conv(x, "de_conv0_1", M, P16, P16, 256, 128, 3, 1, 1, ACT_RELU, x2=layer3, C2=256)
-        up = self._up(x, M, P16, P16, 128, P8, P8)
-        x = self._conv(up, "de_conv1_0", M, P8, P8, 128, 128, 3, 1, 1, ACT_RELU)
+        x = self._up_conv_taps(x, "de_conv1_0", M, P16, P16, 128, 128, ACT_RELU)
         x = self._conv(x, "de_conv1_1", M, P8, P8, 128, 64, 3, 1, 1, ACT_RELU, x2=layer2, C2=128)
         x = self._up_conv(x, "de_conv2_0", M, P8, P8, 64, 64, ACT_RELU)
         x = self._conv(x, "de_conv2_1", M, P4, P4, 64, 64, 3, 1, 1, ACT_RELU, x2=layer1, C2=64)
