@@ -485,6 +485,37 @@ int omni_freeview_pers2equi_bwd_f32(const float* grad_erp, float* grad_pers, con
 int omni_freeview_merge_bwd_f32(const float* grad_erp, float* grad_pers, const float* rot_inv_dev, int B, int N, int C, int h, int w,
                                 int H, int W, float hfov_deg, float wfov_deg, void* ws, omni_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * The geometry terms of depth training (csrc/omni_normals.hip; train_erp_depth.py:267-275).  float32, H, W >= 2
+ * (smaller: OMNI_ERR_UNSUPPORTED).  `ray_tables`: a device array of 2 H + 2 W floats, [sin lat: H][cos lat: H][sin lon: W][cos lon: W]
+ * of coords2uv / uv2xyz (util.py:159-174), built by the caller once per image size.  Nothing is allocated, nothing synchronises.
+ * omni_depth_normals_f32: util.py:332-382 depth2normal_gpu, depth [B,1,H,W] -> normals [B,3,H,W]; the cross products always run over the
+ * channel axis (the reference: over the batch axis when B == 3).
+ * omni_sobel_f32: util.py:426-446 imgrad, img [B,C,H,W] -> the Sobel maps of its channel mean, grad_y and grad_x [B,1,H,W].
+ * omni_l1_loss_f32 / omni_l1_grad_f32: supervision/direct.py:20-26 calculate_l1_loss over pred / gt [B,C,hw] and mask [B,mask_c,hw],
+ * mask_c = 1 or C; count = the sum of the mask as stored.  `workspace` (omni_l1_workspace_bytes(B) bytes) carries the counts to the gradient,
+ * which writes dloss/dpred * (*grad_out).
+ * omni_geometry_terms_f32: losses[0] = normal_loss = 1 - mean_b(sum_b(normals(pred) normals(gt) mask) / sum(mask)) (terms & 1),
+ * losses[1] = grad_loss = calculate_l1_loss(imgrad_yx(pred), imgrad_yx(gt), mask) (terms & 2) from one pass over pred, gt, mask [B,1,H,W];
+ * a term that is not asked for is not computed and its slot is 0.  erode_mask: the mask is mask * [all eight neighbours non-zero]
+ * (outside the image counts as non-zero).  `workspace`: omni_geometry_terms_workspace_bytes(B, H, W) bytes (0 for invalid arguments), any
+ * content, 16-byte aligned; it carries the mask sums to omni_geometry_terms_grad_f32, which writes
+ * (*grad_normal) d normal_loss / d pred + (*grad_grad) d grad_loss / d pred; a NULL upstream pointer leaves that term out (not both).
+ * An item (grad_loss) or batch (normal_loss) whose mask sum is 0: NaN, as omni_berhu_loss_f32. */
+int omni_depth_normals_f32(const float* depth, const float* ray_tables, int B, int H, int W, float* normals, omni_stream_t stream);
+int omni_sobel_f32(const float* img, int B, int C, int H, int W, float* grad_y, float* grad_x, omni_stream_t stream);
+size_t omni_l1_workspace_bytes(int B);
+int omni_l1_loss_f32(const float* pred, const float* gt, const float* mask, int B, int C, size_t hw, int mask_c, void* workspace,
+                     float* loss, omni_stream_t stream);
+int omni_l1_grad_f32(const float* pred, const float* gt, const float* mask, int B, int C, size_t hw, int mask_c, const void* workspace,
+                     const float* grad_out, float* grad_pred, omni_stream_t stream);
+size_t omni_geometry_terms_workspace_bytes(int B, int H, int W);
+int omni_geometry_terms_f32(const float* pred, const float* gt, const float* mask, const float* ray_tables, int B, int H, int W, int terms,
+                            int erode_mask, void* workspace, float* losses, omni_stream_t stream);
+int omni_geometry_terms_grad_f32(const float* pred, const float* gt, const float* mask, const float* ray_tables, int B, int H, int W,
+                                 int erode_mask, const void* workspace, const float* grad_normal, const float* grad_grad, float* grad_pred,
+                                 omni_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

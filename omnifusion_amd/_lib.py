@@ -46,6 +46,8 @@ EXPORTS = [
     "omni_freeview_rotations", "omni_freeview_equi2pers_f32", "omni_freeview_pers2equi_f32", "omni_freeview_merge_f32",
     "omni_freeview_bwd_workspace_bytes", "omni_freeview_equi2pers_bwd_f32", "omni_freeview_pers2equi_bwd_f32", "omni_freeview_merge_bwd_f32",
     "omni_semantic_workspace_bytes", "omni_semantic_step_f32", "omni_semantic_grad_f32", "omni_confusion_matrix_i64",
+    "omni_depth_normals_f32", "omni_sobel_f32", "omni_l1_workspace_bytes", "omni_l1_loss_f32", "omni_l1_grad_f32",
+    "omni_geometry_terms_workspace_bytes", "omni_geometry_terms_f32", "omni_geometry_terms_grad_f32",
 ]
 
 
@@ -96,6 +98,16 @@ def load():
     lib.omni_semantic_step_f32.argtypes = [vp, vp, ci, ci, sz, i64, ci] + [vp] * 5
     lib.omni_semantic_grad_f32.argtypes = [vp, vp, ci, ci, sz, i64] + [vp] * 4
     lib.omni_confusion_matrix_i64.argtypes = [vp, vp, sz, ci] + [vp] * 3
+    lib.omni_depth_normals_f32.argtypes = [vp, vp, ci, ci, ci, vp, vp]
+    lib.omni_sobel_f32.argtypes = [vp] + [ci] * 4 + [vp] * 3
+    lib.omni_l1_workspace_bytes.restype = sz
+    lib.omni_l1_workspace_bytes.argtypes = [ci]
+    lib.omni_l1_loss_f32.argtypes = [vp] * 3 + [ci, ci, sz, ci] + [vp] * 3
+    lib.omni_l1_grad_f32.argtypes = [vp] * 3 + [ci, ci, sz, ci] + [vp] * 4
+    lib.omni_geometry_terms_workspace_bytes.restype = sz
+    lib.omni_geometry_terms_workspace_bytes.argtypes = [ci] * 3
+    lib.omni_geometry_terms_f32.argtypes = [vp] * 4 + [ci] * 5 + [vp] * 3
+    lib.omni_geometry_terms_grad_f32.argtypes = [vp] * 4 + [ci] * 4 + [vp] * 5
     for name in EXPORTS:
         getattr(lib, name)          # AttributeError here = header/library mismatch
     _lib = lib

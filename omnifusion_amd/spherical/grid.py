@@ -30,3 +30,26 @@ def create_spherical_grid(width, horizontal_shift=(-numpy.pi - numpy.pi / 2.0), 
     u = u + horizontal_shift                # standard: [-3 pi / 2, pi / 2)
     v = v + vertical_shift                  # standard: [-pi / 2, pi / 2)
     return torch.stack((u, v), dim=1)
+
+
+_RAY_TABLES = {}
+
+
+def ray_table_values(height, width):
+    """The rays of util.py:159-174 (coords2uv of the 1-based pixel coordinates, middle = n / 2 + 0.5, then uv2xyz) are separable:
+    xyz(i, j) = (cos v_i sin u_j, cos v_i cos u_j, sin v_i).  -> float32 numpy [2 H + 2 W] = sin v | cos v | sin u | cos u, evaluated with the
+    reference's own numpy operations: the angle in float64, stored as float32, then float32 sin / cos."""
+    u = ((numpy.arange(width) + 1 - (width / 2 + 0.5)) / width * 2 * numpy.pi).astype(numpy.float32)
+    v = (-(numpy.arange(height) + 1 - (height / 2 + 0.5)) / height * numpy.pi).astype(numpy.float32)
+    return numpy.concatenate([numpy.sin(v), numpy.cos(v), numpy.sin(u), numpy.cos(u)]).astype(numpy.float32)
+
+
+def ray_tables(height, width, device):
+    """The table above on `device`, built once per (H, W, device) and kept: the kernels of csrc/omni_normals.hip read it instead of evaluating
+    any trigonometry.  The first call for a size copies 8 (H + W) bytes to the device (do it outside a graph capture)."""
+    device = torch.device(device)
+    key = (int(height), int(width), device.type, device.index if device.index is not None else torch.cuda.current_device())
+    t = _RAY_TABLES.get(key)
+    if t is None:
+        t = _RAY_TABLES[key] = torch.from_numpy(ray_table_values(height, width)).to(device)
+    return t

@@ -21,6 +21,13 @@ Free-view sampling — mirror of the reference's util.py:40-60:
     equi, mask = transform_pers(pers, THETA, PHI, output_h_pano, output_w_pano, h_fov, v_fov)    # [N,C,H,W], [N,1,1,H,W]
 
 Same names, arguments and shapes; they run equi_pers.equi2pers_torch / pers2equi_torch (csrc/omni_freeview.hip).
+
+Geometry of a depth map — mirror of util.py:332-382 and :426-451 (csrc/omni_normals.hip), forward only:
+
+    normals = depth2normal_gpu(depth)                 # [B,3,H,W]
+    grad_y, grad_x = imgrad(img); yx = imgrad_yx(depth)
+
+The differentiable losses built on them are supervision.geometry.geometry_terms / normal_loss / gradient_loss.
 """
 import ctypes
 
@@ -97,6 +104,58 @@ def dibr_vertical(depth, image, uvgrid, sgrid, baseline):
 
 def dibr_horizontal(depth, image, uvgrid, sgrid, baseline):
     return _dibr(depth, image, uvgrid, sgrid, baseline, HORIZONTAL)[0]
+
+
+def _forward_only_map(t, name, who, hint):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a tensor")
+    if t.requires_grad:
+        raise ValueError(f"{who} is forward only; the differentiable entry is {hint}")
+    if not t.is_cuda:
+        raise ValueError(f"{name} must be a tensor on an MI355X device; there is no CPU path")
+    if t.dim() != 4 or t.numel() == 0:
+        raise ValueError(f"{name} must be a non-empty [B,C,H,W] tensor (got shape {tuple(t.shape)})")
+    if not t.is_floating_point():
+        raise ValueError(f"{name} must be a floating-point tensor (got {t.dtype})")
+    return t.detach().contiguous().to(torch.float32)
+
+
+def depth2normal_gpu(depth):
+    """Mirror of the reference's util.py:332-382: depth [B,1,H,W] -> float32 unit normals [B,3,H,W] of the vertices ray(i, j) * depth, from the
+    four one-sided differences (zero where the neighbour lies outside the image, on all four borders; no wrap across the seam), the four
+    normalised cross products 2x0, 4x2, 6x4, 0x6 and the normalised sum.  The cross products run over the channel axis for every B (the
+    reference's `torch.cross` without `dim` takes the batch axis when B == 3); the result lives on the input's device.
+    The curvature map the reference computes and discards is not computed.  Forward only."""
+    from .spherical.grid import ray_tables
+    x = _forward_only_map(depth, "depth", "depth2normal_gpu", "supervision.geometry.normal_loss")
+    B, C, H, W = x.shape
+    if C != 1:
+        raise ValueError(f"depth must be [B,1,H,W] (got {tuple(depth.shape)})")
+    out = torch.empty(B, 3, H, W, dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        _lib.check(lib.omni_depth_normals_f32(_p(x), _p(ray_tables(H, W, x.device)), B, H, W, _p(out), _lib.stream_of(x)), "depth2normal_gpu")
+    return out
+
+
+def imgrad(img):
+    """Mirror of util.py:426-446: -> (grad_y, grad_x), each [B,1,H,W]: the channel mean of img [B,C,H,W], then the 3x3 Sobel cross-correlations
+    with zero padding, [[1,2,1],[0,0,0],[-1,-2,-1]] for y and [[1,0,-1],[2,0,-2],[1,0,-1]] for x.  Forward only."""
+    x = _forward_only_map(img, "img", "imgrad", "supervision.geometry.gradient_loss")
+    B, C, H, W = x.shape
+    gy = torch.empty(B, 1, H, W, dtype=torch.float32, device=x.device)
+    gx = torch.empty_like(gy)
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        _lib.check(lib.omni_sobel_f32(_p(x), B, C, H, W, _p(gy), _p(gx), _lib.stream_of(x)), "imgrad")
+    return gy, gx
+
+
+def imgrad_yx(img):
+    """Mirror of util.py:448-451: cat(grad_y, grad_x) on dim 1, [B,2,H,W].  C must be 1 (the reference's `.view(N, C, h, w)` fails otherwise)."""
+    if isinstance(img, torch.Tensor) and img.dim() == 4 and img.shape[1] != 1:
+        raise ValueError(f"imgrad_yx needs a single-channel image [B,1,H,W] (got {tuple(img.shape)})")
+    return torch.cat(imgrad(img), dim=1)
 
 
 def transform_equi(equi, THETA, PHI, output_h, output_w, select_pers, h_fov, v_fov):
