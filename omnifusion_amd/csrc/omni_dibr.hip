@@ -21,7 +21,8 @@
 // not finite poisons them for recon only.  The reference propagates inf / NaN through its float sums instead.
 // Sources whose coordinates are not finite are dropped (render only: the DIBR modes clean their coordinates as the reference does).
 #include "omni_internal.h"
-#include "omni_fixedpoint.h"   // finite, dibr_exponent, pow2f, fixq, dibr_zero_kernel, block_reduce
+#include "omni_fixedpoint.h"   // finite, dibr_exponent, pow2f, fixq, dibr_zero_kernel
+#include "omni_reduce.h"       // block_reduce
 
 namespace {
 

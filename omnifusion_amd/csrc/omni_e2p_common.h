@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <utility>
 #include "omni_internal.h"
+#include "omni_reduce.h"
 
 namespace {
 
@@ -165,17 +166,6 @@ __device__ __forceinline__ void e2p_sample_xy(const E2PArgs& a, int n, int h, in
 // (double-buffered LDS, one barrier per plane).  Tiles whose box does not fit (the pole itself lies inside, or
 // the ERP row pitch is not a multiple of 4) fall back to the direct gathers — wave-uniform branch, same taps.
 constexpr int E2P_BOXF = 3968;                    // floats per LDS buffer: 2 buffers + 80 B < 32 KiB -> 5 blocks / CU
-
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-    return v;
-}
 
 // Grid: blocks [0, ntiles) own one (patch, tile) each and run the LDS path; a tile that does not fit returns at once
 // and is covered by blocks [ntiles, ntiles + nfb*B): one block per (listed tile, batch item), direct gathers, so the

@@ -8,6 +8,7 @@
 //                            |p-g|/g, (p-g)^2/g, (p-g)^2, (log p - log g)^2 [own mask p,g > 1e-7], delta < 1.25^{1,2,3}
 // Reductions are two-stage (per-block partials in double, then one block in fixed order): deterministic.
 #include "omni_internal.h"
+#include "omni_reduce.h"
 
 namespace {
 
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(256) void metrics_partial_kernel(float* __restrict_
                                                               const float* __restrict__ mask, const float* __restrict__ scale_num,
                                                               const float* __restrict__ scale_den, size_t n, double* __restrict__ part)
 {
-    __shared__ double red[4][NMET];
+    __shared__ double red[NMET][4];
     const float sc = (scale_num && scale_den) ? (*scale_num / *scale_den) : 1.0f;
     double s[NMET];
 #pragma unroll
@@ -84,16 +85,10 @@ __global__ __launch_bounds__(256) void metrics_partial_kernel(float* __restrict_
             if (p > 1e-7f && g > 1e-7f) { const float l = logf(p) - logf(g); s[3] += (double)(l * l); s[8] += 1.0; }
         }
     }
+    block_sum<NMET>(s, red);
+    if (threadIdx.x == 0)
 #pragma unroll
-    for (int k = 0; k < NMET; ++k)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_xor(s[k], o);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < NMET; ++k) red[wave][k] = s[k];
-    __syncthreads();
-    if (threadIdx.x < NMET) part[(size_t)blockIdx.x * NMET + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+        for (int k = 0; k < NMET; ++k) part[(size_t)blockIdx.x * NMET + k] = s[k];
 }
 __global__ void metrics_final_kernel(const double* __restrict__ part, int nblocks, float* __restrict__ out)
 {

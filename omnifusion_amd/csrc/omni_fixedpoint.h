@@ -29,17 +29,4 @@ __global__ __launch_bounds__(256) void dibr_zero_kernel(uint4* __restrict__ p, s
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) p[i] = make_uint4(0u, 0u, 0u, 0u);
 }
 
-__device__ __forceinline__ int block_reduce(int v, bool is_max, int* red)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(v, o); v = is_max ? max(v, t) : min(v, t); }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = red[0];
-#pragma unroll
-    for (int k = 1; k < 4; ++k) v = is_max ? max(v, red[k]) : min(v, red[k]);
-    return v;
-}
-
 }  // namespace

@@ -25,6 +25,7 @@
 
 #include "omni_internal.h"
 #include "omni_fixedpoint.h"
+#include "omni_reduce.h"
 #include "omni_freeview_taps.h"
 
 namespace {

@@ -1,12 +1,11 @@
-// omni_io.hip — the host-facing ends of the hot path: what sits between the loader / the training and
-// export code of the reference and the equi_pers operators, moved onto the device so that the GPU is never fed or drained by
+// omni_io.hip — the host-facing ends of the hot path: what sits between the loader / the export
+// code of the reference and the equi_pers operators, moved onto the device so that the GPU is never fed or drained by
 // per-pixel host work.  gfx950 only.  All kernels are HBM-bound streaming passes (coalesced 16-byte accesses where the layout allows).
 //
 //   omni_preprocess_rgb_u8     decoded BGR uint8 HWC frame(s) -> cv2.INTER_AREA resize -> /255 -> float32 CHW
 //                              (dataset_loader_stanford.py:54,92-97 `readRGBPano` + `rgb.astype(np.float32)/255` + transpose(2,0,1) :85)
 //   omni_preprocess_depth_u16  16-bit depth frame -> float32 -> INTER_AREA resize -> /65535*128 -> mask (0.1, 8] -> depth *= mask
 //                              (dataset_loader_stanford.py:99-109 `readDepthPano`, :76-80)
-//   omni_berhu_loss_f32        reverse-Huber loss + its gradient w.r.t. the prediction (supervision/direct.py:3-18; train_erp_depth.py:267)
 //   omni_pointcloud_ply_f32    depth map + panorama -> binary PLY vertex records x,y,z,blue,green,red (test.py:210-240, util.py:159-174)
 #include "omni_internal.h"
 
@@ -112,82 +111,6 @@ __global__ __launch_bounds__(256) void prep_depth_kernel(const unsigned short* _
     mask[i] = m ? 1 : 0;
 }
 
-// ------------------------------------------------------------------ BerHu (reverse Huber), supervision/direct.py:3-18
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// pass 1: max |gt - pred| over EVERYTHING (:7 — not only the masked elements), non-negative floats order like their bits
-__global__ __launch_bounds__(256) void berhu_max_kernel(const float* __restrict__ pred, const float* __restrict__ gt, size_t n, unsigned* __restrict__ maxbits)
-{
-    float m = 0.0f;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) m = fmaxf(m, fabsf(gt[i] - pred[i]));
-    m = wave_max_f(m);
-    if ((threadIdx.x & 63) == 0) atomicMax(maxbits, __float_as_uint(m));
-}
-
-// pass 2: per batch item, partial sums of loss*mask*weight and of mask (fixed block -> slot mapping: deterministic)
-__global__ __launch_bounds__(256) void berhu_sum_kernel(const float* __restrict__ pred, const float* __restrict__ gt, const float* __restrict__ mask,
-                                                        const float* __restrict__ wt, size_t per, const unsigned* __restrict__ maxbits,
-                                                        double* __restrict__ part /* [B][gridDim.x][2] */)
-{
-    __shared__ double red[2][4];
-    const int b = blockIdx.y;
-    const float c = __uint_as_float(*maxbits) / 5.0f;                  // :7
-    double s = 0.0, cnt = 0.0;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < per; i += (size_t)gridDim.x * 256) {
-        const size_t j = (size_t)b * per + i;
-        const float d = gt[j] - pred[j], ad = fabsf(d);
-        const float l = (ad <= c) ? ad : (d * d + c * c) / (2.0f * c);             // :8-10
-        s += (double)(l * mask[j] * wt[j]);                                        // :16-17
-        cnt += (double)mask[j];                                                    // :15
-    }
-    s = wave_sum_d(s); cnt = wave_sum_d(cnt);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s; red[1][threadIdx.x >> 6] = cnt; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double* p = part + ((size_t)b * gridDim.x + blockIdx.x) * 2;
-        p[0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        p[1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-    }
-}
-
-// pass 3: loss = mean_b(sum_b / count_b) (:18); counts[b] kept for the gradient
-__global__ void berhu_final_kernel(const double* __restrict__ part, int B, int nblk, float* __restrict__ loss, float* __restrict__ counts)
-{
-    if (threadIdx.x != 0) return;
-    double tot = 0.0;
-    for (int b = 0; b < B; ++b) {
-        double s = 0.0, c = 0.0;
-        for (int k = 0; k < nblk; ++k) { s += part[((size_t)b * nblk + k) * 2]; c += part[((size_t)b * nblk + k) * 2 + 1]; }
-        counts[b] = (float)c;
-        tot += (double)((float)s / (float)c);          // fp32 division like torch (0/0 -> NaN for an empty mask, like the reference)
-    }
-    *loss = (float)(tot / B);
-}
-
-// gradient w.r.t. pred (c is a Python float in the reference — `.item()` — hence a constant):
-// dL/dpred = -(g / B) * mask * weight / count_b * (|d| <= c ? sign(d) : d / c)
-__global__ __launch_bounds__(256) void berhu_grad_kernel(const float* __restrict__ pred, const float* __restrict__ gt, const float* __restrict__ mask,
-                                                         const float* __restrict__ wt, size_t per, size_t n, const unsigned* __restrict__ maxbits,
-                                                         const float* __restrict__ counts, const float* __restrict__ gout, int B, float* __restrict__ grad)
-{
-    const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (j >= n) return;
-    const float c = __uint_as_float(*maxbits) / 5.0f;
-    const int b = (int)(j / per);
-    const float d = gt[j] - pred[j], ad = fabsf(d);
-    const float dl = (ad <= c) ? (d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f)) : d / c;      // d loss / d diff
-    grad[j] = -(*gout / (float)B) * (mask[j] * wt[j] / counts[b]) * dl;
-}
-
 // ------------------------------------------------------------------ point cloud, test.py:210-240
 // vertex i of image b (row-major, x fastest — np.meshgrid(range(w), range(h)) reshaped, :211-213):
 //   coords = (x+1, y+1);  u = (cx - (w/2 + 0.5)) / w * 2 pi,  v = -(cy - (h/2 + 0.5)) / h * pi          util.py:159-165
@@ -249,42 +172,6 @@ extern "C" int omni_preprocess_depth_u16(const unsigned short* src, float* depth
     const size_t n = (size_t)B * H * W;
     hipLaunchKernelGGL(prep_depth_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, depth, mask, B, Hs, Ws, H, W,
                        (float)((double)Hs / H), (float)((double)Ws / W), min_depth, max_depth);
-    OMNI_HIP(hipGetLastError());
-    return OMNI_OK;
-}
-
-extern "C" size_t omni_berhu_workspace_bytes(int B) { return 64 + sizeof(double) * 2 * 256 * (size_t)(B > 0 ? B : 1) + sizeof(float) * (size_t)(B > 0 ? B : 1); }
-
-extern "C" int omni_berhu_loss_f32(const float* pred, const float* gt, const float* mask, const float* weights, int B, size_t per_item,
-                                   void* workspace, float* loss, omni_stream_t stream)
-{
-    if (!pred || !gt || !mask || !weights || !workspace || !loss) OMNI_FAIL(OMNI_ERR_INVALID, "omni_berhu_loss_f32: null device pointer");
-    if (B < 1 || per_item < 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_berhu_loss_f32: empty batch");
-    hipStream_t s = (hipStream_t)stream;
-    unsigned* maxbits = (unsigned*)workspace;
-    double* part = (double*)((char*)workspace + 64);
-    float* counts = (float*)(part + 2 * 256 * (size_t)B);
-    const size_t n = (size_t)B * per_item;
-    OMNI_HIP(hipMemsetAsync(maxbits, 0, sizeof(unsigned), s));
-    const unsigned g1 = (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
-    hipLaunchKernelGGL(berhu_max_kernel, dim3(g1), dim3(256), 0, s, pred, gt, n, maxbits);
-    const unsigned nblk = (unsigned)((per_item + 255) / 256 < 256 ? (per_item + 255) / 256 : 256);
-    hipLaunchKernelGGL(berhu_sum_kernel, dim3(nblk, B), dim3(256), 0, s, pred, gt, mask, weights, per_item, (const unsigned*)maxbits, part);
-    hipLaunchKernelGGL(berhu_final_kernel, dim3(1), dim3(64), 0, s, (const double*)part, B, (int)nblk, loss, counts);
-    OMNI_HIP(hipGetLastError());
-    return OMNI_OK;
-}
-
-extern "C" int omni_berhu_grad_f32(const float* pred, const float* gt, const float* mask, const float* weights, int B, size_t per_item,
-                                   const void* workspace, const float* grad_out, float* grad_pred, omni_stream_t stream)
-{
-    if (!pred || !gt || !mask || !weights || !workspace || !grad_out || !grad_pred) OMNI_FAIL(OMNI_ERR_INVALID, "omni_berhu_grad_f32: null device pointer");
-    if (B < 1 || per_item < 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_berhu_grad_f32: empty batch");
-    const unsigned* maxbits = (const unsigned*)workspace;
-    const float* counts = (const float*)((const char*)workspace + 64 + sizeof(double) * 2 * 256 * (size_t)B);
-    const size_t n = (size_t)B * per_item;
-    hipLaunchKernelGGL(berhu_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pred, gt, mask, weights, per_item, n,
-                       maxbits, counts, grad_out, B, grad_pred);
     OMNI_HIP(hipGetLastError());
     return OMNI_OK;
 }

@@ -3,19 +3,19 @@
 //
 //   omni_depth_normals_f32            util.py:332-382 depth2normal_gpu: depth [B,1,H,W] -> unit normals [B,3,H,W]
 //   omni_sobel_f32                    util.py:426-446 imgrad: channel mean, then the two 3x3 Sobel maps [B,1,H,W]
-//   omni_l1_loss_f32 / _grad_f32      supervision/direct.py:20-26 calculate_l1_loss and its gradient w.r.t. pred
 //   omni_geometry_terms_f32           normal_loss = 1 - mean_b(sum_b(pn gn mask) / sum(mask)) and grad_loss = calculate_l1_loss(imgrad_yx(pred),
 //                                     imgrad_yx(gt), mask) from ONE pass over pred, gt and mask; no normal or Sobel map is written
 //   omni_geometry_terms_grad_f32      d(g_n normal_loss + g_g grad_loss) / d pred, one gather kernel
 //
 // Forward: a block owns a 16 x 64 tile; pred, gt and mask are staged in LDS with a one-pixel halo (16-byte loads of the interior where the
 // rows are aligned, scalar loads of the halo columns), a thread owns four pixels.  Sums go wave -> block -> one double partial per (item,
-// tile); a final block adds them in a fixed order (the BerHu scheme of omni_io.hip).  No atomics: the bits do not change from run to run.
+// tile); a final block adds them in a fixed order (the BerHu scheme of omni_losses.hip).  No atomics: the bits do not change from run to run.
 // Backward: the same tile with a two-pixel halo.  Phase A recomputes, for the tile and a one-pixel ring around it, what each pixel q sends
 // to the five depths its normal read and the two Sobel adjoints, into LDS; phase B: a thread per output pixel gathers from its own entry
 // and its neighbours'.  Nothing is scattered, nothing is stored by the forward but the mask sums.
 // Per-pixel arithmetic: omni_normals.h, shared with the two mirrors.  Rays come from four host-built tables (no trigonometry here).
 #include "omni_normals.h"
+#include "omni_reduce.h"
 
 namespace {
 
@@ -23,27 +23,6 @@ using geo::V3;
 
 constexpr int GT_W = 64, GT_H = 16, G_THREADS = 256, G_ROWS = G_THREADS / GT_W, G_PX = GT_H / G_ROWS;
 constexpr int TERM_NORMAL = 1, TERM_GRAD = 2;
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// sums `n` doubles of the block's threads into thread 0 (fixed tree); red: [n][G_THREADS / 64]
-template <int N>
-__device__ __forceinline__ void block_sum(double (&v)[N], double (*red)[G_THREADS / 64])
-{
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        v[k] = wave_sum(v[k]);
-        if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-}
 
 // Rows y0 - HALO .. y0 + GT_H + HALO, columns x0 - HALO .. x0 + GT_W + HALO of one H x W plane into lds[(GT_H + 2 HALO)][(GT_W + 2 HALO)];
 // `fill` outside the image.  vec: W % 4 == 0 and the plane is 16-byte aligned, so every aligned group of four columns is inside or outside.
@@ -129,7 +108,7 @@ __global__ __launch_bounds__(G_THREADS) void geometry_terms_kernel(const float* 
 
 // One block.  Per item: thread t adds partials t, t + 256, ... in that order, then the fixed tree.  head[0] = sum(mask) of the batch,
 // head[1 + b] = sum(mask) of item b (float32, as `count` in the reference); losses[0] = normal_loss, losses[1] = grad_loss.
-// An empty mask divides 0 by 0: NaN, as berhu_final_kernel.
+// An empty mask divides 0 by 0: NaN, as masked_mean_final_kernel.
 __global__ __launch_bounds__(G_THREADS) void geometry_final_kernel(const double* __restrict__ part, int B, int ntiles, float* __restrict__ head,
                                                                    float* __restrict__ losses)
 {
@@ -280,54 +259,6 @@ __global__ __launch_bounds__(G_THREADS) void sobel_kernel(const float* __restric
     grad_y[p] = gy; grad_x[p] = gx;
 }
 
-// ------------------------------------------------------------------ calculate_l1_loss
-constexpr int L1_MAX_BLOCKS = 256;
-
-// part: [B][gridDim.x][2] = sum(|gt - pred| * mask), sum(mask) — the mask summed as it is stored ([B,1,...] once, [B,C,...] C planes)
-__global__ __launch_bounds__(G_THREADS) void l1_sum_kernel(const float* __restrict__ pred, const float* __restrict__ gt, const float* __restrict__ mask,
-                                                           int C, size_t hw, int mask_c, double* __restrict__ part)
-{
-    __shared__ double red[2][G_THREADS / 64];
-    const int b = blockIdx.y;
-    const size_t per = (size_t)C * hw;
-    double s[2] = {0.0, 0.0};
-    for (size_t e = (size_t)blockIdx.x * G_THREADS + threadIdx.x; e < per; e += (size_t)gridDim.x * G_THREADS) {
-        const size_t c = e / hw, o = e - c * hw;
-        const float m = mask[(size_t)b * mask_c * hw + (mask_c == 1 ? o : e)];
-        s[0] += (double)(fabsf(gt[b * per + e] - pred[b * per + e]) * m);
-        if (mask_c != 1 || c == 0) s[1] += (double)m;
-    }
-    block_sum<2>(s, red);
-    if (threadIdx.x == 0) {
-        double* p = part + ((size_t)b * gridDim.x + blockIdx.x) * 2;
-        p[0] = s[0]; p[1] = s[1];
-    }
-}
-
-__global__ void l1_final_kernel(const double* __restrict__ part, int B, int nblk, float* __restrict__ loss, float* __restrict__ counts)
-{
-    if (threadIdx.x != 0) return;
-    double tot = 0.0;
-    for (int b = 0; b < B; ++b) {
-        double s = 0.0, c = 0.0;
-        for (int k = 0; k < nblk; ++k) { s += part[((size_t)b * nblk + k) * 2]; c += part[((size_t)b * nblk + k) * 2 + 1]; }
-        counts[b] = (float)c;
-        tot += (double)((float)s / (float)c);                                // 0 / 0 -> NaN for an empty mask, as berhu_final_kernel
-    }
-    *loss = (float)(tot / B);
-}
-
-__global__ __launch_bounds__(G_THREADS) void l1_grad_kernel(const float* __restrict__ pred, const float* __restrict__ gt, const float* __restrict__ mask,
-                                                            int B, int C, size_t hw, int mask_c, size_t n, const float* __restrict__ counts,
-                                                            const float* __restrict__ gout, float* __restrict__ grad)
-{
-    const size_t p = (size_t)blockIdx.x * G_THREADS + threadIdx.x;
-    if (p >= n) return;
-    const size_t per = (size_t)C * hw, b = p / per, e = p - b * per;
-    const float m = mask[b * mask_c * hw + (mask_c == 1 ? e % hw : e)];
-    grad[p] = -(*gout / (float)B) * (m / counts[b]) * geo::sign0(gt[p] - pred[p]);
-}
-
 // ------------------------------------------------------------------ host side
 constexpr int GEO_MAX_B = 65535;                                             // gridDim.y
 
@@ -365,47 +296,6 @@ extern "C" int omni_sobel_f32(const float* img, int B, int C, int H, int W, floa
     if (const int rc = geo_check("omni_sobel_f32", B, H, W)) return rc;
     const size_t n = (size_t)B * H * W;
     hipLaunchKernelGGL(sobel_kernel, dim3((unsigned)((n + G_THREADS - 1) / G_THREADS)), dim3(G_THREADS), 0, (hipStream_t)stream, img, n, C, H, W, grad_y, grad_x);
-    OMNI_HIP(hipGetLastError());
-    return OMNI_OK;
-}
-
-extern "C" size_t omni_l1_workspace_bytes(int B) { const size_t b = B > 0 ? B : 1; return sizeof(double) * 2 * L1_MAX_BLOCKS * b + sizeof(float) * b; }
-
-namespace {
-int l1_check(const char* who, int B, int C, size_t hw, int mask_c)
-{
-    if (B < 1 || C < 1 || hw < 1) OMNI_FAIL(OMNI_ERR_INVALID, std::string(who) + ": empty batch");
-    if (mask_c != 1 && mask_c != C) OMNI_FAIL(OMNI_ERR_INVALID, std::string(who) + ": the mask has 1 or C channels");
-    if (B > GEO_MAX_B) OMNI_FAIL(OMNI_ERR_UNSUPPORTED, std::string(who) + ": more than 65535 items");
-    return OMNI_OK;
-}
-}  // namespace
-
-extern "C" int omni_l1_loss_f32(const float* pred, const float* gt, const float* mask, int B, int C, size_t hw, int mask_c, void* workspace,
-                                float* loss, omni_stream_t stream)
-{
-    if (!pred || !gt || !mask || !workspace || !loss) OMNI_FAIL(OMNI_ERR_INVALID, "omni_l1_loss_f32: null device pointer");
-    if (const int rc = l1_check("omni_l1_loss_f32", B, C, hw, mask_c)) return rc;
-    double* part = (double*)workspace;
-    float* counts = (float*)(part + 2 * L1_MAX_BLOCKS * (size_t)B);
-    const size_t per = (size_t)C * hw, want = (per + G_THREADS - 1) / G_THREADS;
-    const unsigned nblk = (unsigned)(want < (size_t)L1_MAX_BLOCKS ? want : (size_t)L1_MAX_BLOCKS);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(l1_sum_kernel, dim3(nblk, B), dim3(G_THREADS), 0, s, pred, gt, mask, C, hw, mask_c, part);
-    hipLaunchKernelGGL(l1_final_kernel, dim3(1), dim3(64), 0, s, (const double*)part, B, (int)nblk, loss, counts);
-    OMNI_HIP(hipGetLastError());
-    return OMNI_OK;
-}
-
-extern "C" int omni_l1_grad_f32(const float* pred, const float* gt, const float* mask, int B, int C, size_t hw, int mask_c, const void* workspace,
-                                const float* grad_out, float* grad_pred, omni_stream_t stream)
-{
-    if (!pred || !gt || !mask || !workspace || !grad_out || !grad_pred) OMNI_FAIL(OMNI_ERR_INVALID, "omni_l1_grad_f32: null device pointer");
-    if (const int rc = l1_check("omni_l1_grad_f32", B, C, hw, mask_c)) return rc;
-    const float* counts = (const float*)((const double*)workspace + 2 * L1_MAX_BLOCKS * (size_t)B);
-    const size_t n = (size_t)B * C * hw;
-    hipLaunchKernelGGL(l1_grad_kernel, dim3((unsigned)((n + G_THREADS - 1) / G_THREADS)), dim3(G_THREADS), 0, (hipStream_t)stream, pred, gt, mask, B, C, hw,
-                       mask_c, n, counts, grad_out, grad_pred);
     OMNI_HIP(hipGetLastError());
     return OMNI_OK;
 }

@@ -10,7 +10,7 @@
 // (zeros beyond the image: the reference's zero padding), runs the window separably — rows, then columns — over the five moments
 // x, y, x^2, y^2, xy, and forms SSIM, d_ssim, L1 and the weighted loss in registers.  No map is written (omni_ssim_f32 apart).
 // The window sums and SSIM run in fp64: sigma^2 = E[x^2] - mu^2 cancels against C2 = 9e-4, where fp32 sums leave ~1e-4 relative.
-// The per-item sum is two-stage with a fixed block -> slot mapping (the BerHu scheme of omni_io.hip): deterministic, no atomics, the
+// The per-item sum is two-stage with a fixed block -> slot mapping (the BerHu scheme of omni_losses.hip): deterministic, no atomics, the
 // scalar stays on the device.
 //
 // Backward w.r.t. pred: the window is symmetric and the padding zero, so the adjoint of a window sum is the same window sum.
@@ -19,6 +19,7 @@
 //   pass 2 windows the three planes and combines  mask * (win P1 + 2 x win P2 + y win P3) + the L1 term.
 // 'box': P is zero on the border ring (the map there is the constant 0), which is all the valid-only adjoint needs.
 #include "omni_internal.h"
+#include "omni_reduce.h"
 
 namespace {
 
@@ -31,13 +32,6 @@ struct PhotoArgs {
     float win[2 * PR_MAX + 1];                                      // the 1-D window (fp32 values, as the reference builds it)
     double alpha;
 };
-
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __device__ __forceinline__ float mask_at(const PhotoArgs& a, int b, int c, size_t HW, size_t p)
 {
@@ -132,7 +126,7 @@ __global__ __launch_bounds__(256) void photo_kernel(PhotoArgs a, int tiles_x, do
     rows_xy(a, wd, xs, ys, hm);
     __syncthreads();
     const int SW = PT_W + 2 * a.r;
-    double lsum = 0.0, csum = 0.0;
+    double sum[2] = {0.0, 0.0};                                     // loss, mask
     for (int e = threadIdx.x; e < PT_H * PT_W; e += 256) {
         const int row = e / PT_W, col = e - row * PT_W, y = y0 + row, x = x0 + col;
         if (y >= a.H || x >= a.W) continue;
@@ -150,8 +144,8 @@ __global__ __launch_bounds__(256) void photo_kernel(PhotoArgs a, int tiles_x, do
             if (part) {
                 const double dss = h < 0.0 ? 0.0 : (h > 1.0 ? 1.0 : h);             // NaN stays NaN, like torch.clamp
                 const double l1 = (double)fabsf(ys[(row + a.r) * SW + col + a.r] - xs[(row + a.r) * SW + col + a.r]);
-                lsum += ((a.alpha * dss + (1.0 - a.alpha) * l1) * (double)m) * (double)wt;
-                if (a.mask_c != 1 || c == 0) csum += (double)m;
+                sum[0] += ((a.alpha * dss + (1.0 - a.alpha) * l1) * (double)m) * (double)wt;
+                if (a.mask_c != 1 || c == 0) sum[1] += (double)m;
             }
         } else {
             // d loss / d ssim at this pixel: (gout / B) / count_b * weights * mask * alpha * (-1/2) inside the clamp, 0 outside
@@ -163,13 +157,10 @@ __global__ __launch_bounds__(256) void photo_kernel(PhotoArgs a, int tiles_x, do
         }
     }
     if (MODE == 0 && part) {
-        lsum = wave_sum_d(lsum); csum = wave_sum_d(csum);
-        if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = lsum; red[1][threadIdx.x >> 6] = csum; }
-        __syncthreads();
+        block_sum<2>(sum, red);
         if (threadIdx.x == 0) {
             double* o = part + ((size_t)b * (gridDim.x * gridDim.y) + (size_t)c * gridDim.x + blockIdx.x) * 2;
-            o[0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-            o[1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+            o[0] = sum[0]; o[1] = sum[1];
         }
     }
 }

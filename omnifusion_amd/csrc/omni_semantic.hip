@@ -13,6 +13,7 @@
 // label is outside the matrix (iou.py:23), and a label or prediction that is neither is dropped from both and counted in n_bad — nothing is
 // ever read or counted out of range.
 #include "omni_internal.h"
+#include "omni_reduce.h"
 
 namespace {
 
@@ -55,19 +56,6 @@ __device__ __forceinline__ int conf_bin(long long pred, long long gt, int K, boo
     return (int)pred * K + (int)gt;
 }
 
-__device__ __forceinline__ long long wave_sum(long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 template <int PX> struct Vec;
 template <> struct Vec<1> { using F = float; };
 template <> struct Vec<4> { using F = float4; };
@@ -108,8 +96,8 @@ __global__ __launch_bounds__(SEM_THREADS) void semantic_step_kernel(const float*
 {
     using F = typename Vec<PX>::F;
     __shared__ unsigned hist[SEM_MAX_K * SEM_MAX_K];
-    __shared__ double red_sum[SEM_THREADS / 64];
-    __shared__ long long red_cnt[SEM_THREADS / 64], red_bad[SEM_THREADS / 64];
+    __shared__ double red_sum[1][SEM_THREADS / 64];
+    __shared__ long long red_cnt[2][SEM_THREADS / 64];                        // count, bad
     const int KK = K * K;
     if (confusion) {
         for (int i = threadIdx.x; i < KK; i += SEM_THREADS) hist[i] = 0;
@@ -168,17 +156,12 @@ __global__ __launch_bounds__(SEM_THREADS) void semantic_step_kernel(const float*
             if (pred_out) store_px<PX>(pred_out + p, best);
         }
     }
-    sum = wave_sum(sum); count = wave_sum(count); nbad = wave_sum(nbad);
-    if ((threadIdx.x & 63) == 0) { red_sum[threadIdx.x >> 6] = sum; red_cnt[threadIdx.x >> 6] = count; red_bad[threadIdx.x >> 6] = nbad; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        SemPart r;
-        r.sum = (red_sum[0] + red_sum[1]) + (red_sum[2] + red_sum[3]);
-        r.count = red_cnt[0] + red_cnt[1] + red_cnt[2] + red_cnt[3];
-        r.bad = red_bad[0] + red_bad[1] + red_bad[2] + red_bad[3];
-        part[blockIdx.x] = r;
-    }
-    if (confusion) hist_flush(hist, KK, confusion);                          // (the barrier above orders the LDS adds before the reads)
+    double s[1] = {sum};
+    long long n[2] = {count, nbad};
+    block_sum<1>(s, red_sum);
+    block_sum<2>(n, red_cnt);
+    if (threadIdx.x == 0) part[blockIdx.x] = SemPart{s[0], n[0], n[1]};
+    if (confusion) hist_flush(hist, KK, confusion);                          // (block_sum's barrier orders the LDS adds before the reads)
 }
 
 // one block: thread t sums partials t, t + 256, ... in that order, then a fixed tree
@@ -240,11 +223,11 @@ __global__ __launch_bounds__(SEM_THREADS) void confusion_kernel(const long long*
                                                                 long long* __restrict__ confusion, long long* __restrict__ n_bad)
 {
     __shared__ unsigned hist[SEM_MAX_K * SEM_MAX_K];
-    __shared__ long long red_bad[SEM_THREADS / 64];
+    __shared__ long long red_bad[1][SEM_THREADS / 64];
     const int KK = K * K;
     for (int i = threadIdx.x; i < KK; i += SEM_THREADS) hist[i] = 0;
     __syncthreads();
-    long long nbad = 0;
+    long long nbad[1] = {0};
     const size_t step = (size_t)gridDim.x * SEM_THREADS;
     for (size_t base = (size_t)blockIdx.x * SEM_THREADS; base < n; base += step) {                   // block-uniform
         const size_t p = base + threadIdx.x;
@@ -252,18 +235,13 @@ __global__ __launch_bounds__(SEM_THREADS) void confusion_kernel(const long long*
         if (p < n) {
             bool bad = false;
             bin = conf_bin(pred[p], gt[p], K, bad);
-            nbad += bad ? 1 : 0;
+            nbad[0] += bad ? 1 : 0;
         }
         hist_add(hist, bin);
     }
-    nbad = wave_sum(nbad);
-    if ((threadIdx.x & 63) == 0) red_bad[threadIdx.x >> 6] = nbad;
-    __syncthreads();
+    block_sum<1>(nbad, red_bad);                                             // (its barrier also orders the LDS adds before the flush)
     hist_flush(hist, KK, confusion);
-    if (threadIdx.x == 0 && n_bad) {
-        const long long tot = red_bad[0] + red_bad[1] + red_bad[2] + red_bad[3];
-        if (tot) atomicAdd(reinterpret_cast<unsigned long long*>(n_bad), (unsigned long long)tot);
-    }
+    if (threadIdx.x == 0 && n_bad && nbad[0]) atomicAdd(reinterpret_cast<unsigned long long*>(n_bad), (unsigned long long)nbad[0]);
 }
 
 // a block's 32-bit bins cannot overflow below 2^32 pixels per block; far above anything a device holds

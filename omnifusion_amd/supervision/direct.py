@@ -2,12 +2,12 @@
 
     loss = calculate_berhu_loss(pred, gt, mask, weights)      # scalar tensor on pred.device, differentiable w.r.t. pred
 
-Same name, arguments and value as the reference.  Everything numeric runs in libomnifusion_hip.so (csrc/omni_io.hip): a max
+Same name, arguments and value as the reference.  Everything numeric runs in libomnifusion_hip.so (csrc/omni_losses.hip): a max
 pass, a deterministic two-stage masked sum and — for backward — one element-wise gradient pass.  Unlike the reference
 (`torch.max(abs_diff).item()`, a device->host synchronisation per step) the threshold c = max|gt - pred| / 5 stays on the device;
 like there it is a constant of the backward pass.
 
-calculate_l1_loss — mirror of :20-26 (the gradient term of the depth objective, train_erp_depth.py:272-274; csrc/omni_normals.hip):
+calculate_l1_loss — mirror of :20-26 (the gradient term of the depth objective, train_erp_depth.py:272-274; the same unit):
 
     loss = calculate_l1_loss(pred, gt, mask)                  # mean_b(sum_b(|gt - pred| * mask) / sum_b(mask)), differentiable w.r.t. pred
 """
