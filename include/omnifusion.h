@@ -516,6 +516,39 @@ int omni_geometry_terms_grad_f32(const float* pred, const float* gt, const float
                                  int erode_mask, const void* workspace, const float* grad_normal, const float* grad_grad, float* grad_pred,
                                  omni_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * The guided (edge-aware) smoothness term of the self-supervised objective (csrc/omni_smoothness.hip, DESIGN.md §15;
+ * supervision/smoothness.py:3-8, spherical/derivatives.py:7-24,190-214, spherical/cartesian.py:14-50).  float32, B, C, H, W >= 1.
+ * Nothing is allocated, nothing synchronises, nothing is read back.  Differences are t[i,j] - t[i,j+1] (du) and t[i,j] - t[i+1,j] (dv)
+ * with replicate padding: the last column's du and the last row's dv are 0.  A mask element is valid where it is != 0.
+ * omni_image_diff_f32: dI_du (axis 0) / dI_dv (axis 1), img [B,C,H,W] -> out [B,C,H,W].
+ * omni_image_diff_norm_f32: dI_duv, the 2-norm over the 2 C difference channels, img [B,C,H,W] -> out [B,1,H,W].
+ * omni_vertex_diff_norm_f32: dV_dxyz, pcloud [B,3,H,W] -> out [B,1,H,W] = sqrt(du^2 + dv^2), du = |du_x| + |du_y| + |du_z|, dv likewise.
+ * omni_guided_smoothness_f32: *loss = sum(mask ? input_duv exp(-guide_duv) weights : 0) / sum(mask != 0) over n elements each (the mask
+ * selects: nothing at a masked element, the weight included, reaches the sum); omni_guided_smoothness_grad_f32 writes
+ * (*grad_out) dloss / dinput_duv.  `workspace`: omni_guided_smoothness_workspace_bytes(n) bytes.
+ * omni_depth_smoothness_f32: the same loss for input_duv = dV_dxyz of the vertices x = depth cos(phi) (-1) cos(theta), y = depth sin(theta),
+ * z = depth sin(phi) cos(theta) and guide_duv = dI_duv(image), from one pass over depth [B,1,H,W], image [B,C,H,W], mask and weights
+ * [B,1,H,W] (weights may be NULL: 1); no intermediate map is written.  `factors`: a device array [4][H][W] = cos phi | sin phi |
+ * cos theta | sin theta of the spherical grid, built by the caller once per grid.  omni_depth_smoothness_grad_f32 writes
+ * (*grad_out) dloss / ddepth by a gather (no atomics); d|x|/dx = 0 at 0 and the gradient of a 2-norm is 0 where the norm is 0.
+ * `workspace`: omni_depth_smoothness_workspace_bytes(B, H, W) bytes.  Workspaces: 0 for invalid arguments, any content, 16-byte aligned;
+ * the forward leaves the mask sum there for the gradient.  sum(mask != 0) == 0: NaN (0 / 0), as the reference. */
+int omni_image_diff_f32(const float* img, int B, int C, int H, int W, int axis, float* out, omni_stream_t stream);
+int omni_image_diff_norm_f32(const float* img, int B, int C, int H, int W, float* out, omni_stream_t stream);
+int omni_vertex_diff_norm_f32(const float* pcloud, int B, int H, int W, float* out, omni_stream_t stream);
+size_t omni_guided_smoothness_workspace_bytes(size_t n);
+int omni_guided_smoothness_f32(const float* input_duv, const float* guide_duv, const float* mask, const float* weights, size_t n,
+                               void* workspace, float* loss, omni_stream_t stream);
+int omni_guided_smoothness_grad_f32(const float* guide_duv, const float* mask, const float* weights, size_t n, const void* workspace,
+                                    const float* grad_out, float* grad_input, omni_stream_t stream);
+size_t omni_depth_smoothness_workspace_bytes(int B, int H, int W);
+int omni_depth_smoothness_f32(const float* depth, const float* image, const float* mask, const float* weights, const float* factors, int B,
+                              int C, int H, int W, void* workspace, float* loss, omni_stream_t stream);
+int omni_depth_smoothness_grad_f32(const float* depth, const float* image, const float* mask, const float* weights, const float* factors,
+                                   int B, int C, int H, int W, const void* workspace, const float* grad_out, float* grad_depth,
+                                   omni_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

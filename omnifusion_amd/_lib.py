@@ -48,6 +48,9 @@ EXPORTS = [
     "omni_semantic_workspace_bytes", "omni_semantic_step_f32", "omni_semantic_grad_f32", "omni_confusion_matrix_i64",
     "omni_depth_normals_f32", "omni_sobel_f32", "omni_l1_workspace_bytes", "omni_l1_loss_f32", "omni_l1_grad_f32",
     "omni_geometry_terms_workspace_bytes", "omni_geometry_terms_f32", "omni_geometry_terms_grad_f32",
+    "omni_image_diff_f32", "omni_image_diff_norm_f32", "omni_vertex_diff_norm_f32",
+    "omni_guided_smoothness_workspace_bytes", "omni_guided_smoothness_f32", "omni_guided_smoothness_grad_f32",
+    "omni_depth_smoothness_workspace_bytes", "omni_depth_smoothness_f32", "omni_depth_smoothness_grad_f32",
 ]
 
 
@@ -108,6 +111,17 @@ def load():
     lib.omni_geometry_terms_workspace_bytes.argtypes = [ci] * 3
     lib.omni_geometry_terms_f32.argtypes = [vp] * 4 + [ci] * 5 + [vp] * 3
     lib.omni_geometry_terms_grad_f32.argtypes = [vp] * 4 + [ci] * 4 + [vp] * 5
+    lib.omni_image_diff_f32.argtypes = [vp] + [ci] * 5 + [vp] * 2
+    lib.omni_image_diff_norm_f32.argtypes = [vp] + [ci] * 4 + [vp] * 2
+    lib.omni_vertex_diff_norm_f32.argtypes = [vp] + [ci] * 3 + [vp] * 2
+    lib.omni_guided_smoothness_workspace_bytes.restype = sz
+    lib.omni_guided_smoothness_workspace_bytes.argtypes = [sz]
+    lib.omni_guided_smoothness_f32.argtypes = [vp] * 4 + [sz] + [vp] * 3
+    lib.omni_guided_smoothness_grad_f32.argtypes = [vp] * 3 + [sz] + [vp] * 4
+    lib.omni_depth_smoothness_workspace_bytes.restype = sz
+    lib.omni_depth_smoothness_workspace_bytes.argtypes = [ci] * 3
+    lib.omni_depth_smoothness_f32.argtypes = [vp] * 5 + [ci] * 4 + [vp] * 3
+    lib.omni_depth_smoothness_grad_f32.argtypes = [vp] * 5 + [ci] * 4 + [vp] * 4
     for name in EXPORTS:
         getattr(lib, name)          # AttributeError here = header/library mismatch
     _lib = lib
