@@ -549,6 +549,28 @@ int omni_depth_smoothness_grad_f32(const float* depth, const float* image, const
                                    int B, int C, int H, int W, const void* workspace, const float* grad_out, float* grad_depth,
                                    omni_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * The one-directional Chamfer term between two point clouds and its gradient (csrc/omni_chamfer.hip; util.py:201-257,
+ * chamfer_distance_with_batch).  float32, contiguous p1 [B,N,D] and p2 [B,M,D], D = 2 or 3, B, N, M >= 1 (B <= 65535; N x M has no limit).
+ * mask1 [B,N] / mask2 [B,M]: uint8, valid where != 0, either may be NULL (every point valid).  Nothing is allocated, nothing synchronises,
+ * nothing is read back; no floating-point atomics: every output has the same bits on every run.
+ * omni_chamfer_nn_f32: dist [B,N] = min over the valid j of |p1[i] - p2[j]| (squared distances from direct differences, sqrt of the winner),
+ * 0 at a masked query; idx [B,N] int32 = the argmin, the LOWEST index among equal distances, -1 at a masked query and in an item without a
+ * valid target (whose dist is +inf); *loss = sum(dist), added in double in a fixed order and rounded once.  A NaN coordinate of a valid
+ * target makes every dist of its item NaN, one of a valid query its own dist (idx -1), and the loss NaN.
+ * omni_chamfer_grad_f32: with g_i = *grad_loss (NULL: 0) + grad_dist[b,i] (NULL: 0), at least one of them given:
+ * grad_p1 [B,N,D] = g_i (p1[i] - p2[idx_i]) / dist_i, 0 where dist_i == 0, at masked queries and where idx_i < 0; grad_p2 [B,M,D] = the
+ * negated sum of the same vectors over the queries whose idx is j, in 64-bit fixed point (exact, order-independent).  Either gradient
+ * pointer may be NULL (not computed), not both.  idx is the forward's output.
+ * `workspace`: omni_chamfer_workspace_bytes(B, N, M, D) bytes (0 for invalid arguments), any content, 16-byte aligned; the two calls do
+ * not share state through it.  Option "chamfer_split" = 0 keeps the search from cutting the targets into chunks (same bits). */
+size_t omni_chamfer_workspace_bytes(int B, int N, int M, int D);
+int omni_chamfer_nn_f32(const float* p1, const float* p2, const unsigned char* mask1, const unsigned char* mask2, int B, int N, int M, int D,
+                        float* dist, int* idx, float* loss, void* workspace, omni_stream_t stream);
+int omni_chamfer_grad_f32(const float* p1, const float* p2, const unsigned char* mask1, const int* idx, const float* grad_loss,
+                          const float* grad_dist, int B, int N, int M, int D, float* grad_p1, float* grad_p2, void* workspace,
+                          omni_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,7 @@ EXPORTS = [
     "omni_image_diff_f32", "omni_image_diff_norm_f32", "omni_vertex_diff_norm_f32",
     "omni_guided_smoothness_workspace_bytes", "omni_guided_smoothness_f32", "omni_guided_smoothness_grad_f32",
     "omni_depth_smoothness_workspace_bytes", "omni_depth_smoothness_f32", "omni_depth_smoothness_grad_f32",
+    "omni_chamfer_workspace_bytes", "omni_chamfer_nn_f32", "omni_chamfer_grad_f32",
 ]
 
 
@@ -122,6 +123,10 @@ def load():
     lib.omni_depth_smoothness_workspace_bytes.argtypes = [ci] * 3
     lib.omni_depth_smoothness_f32.argtypes = [vp] * 5 + [ci] * 4 + [vp] * 3
     lib.omni_depth_smoothness_grad_f32.argtypes = [vp] * 5 + [ci] * 4 + [vp] * 4
+    lib.omni_chamfer_workspace_bytes.restype = sz
+    lib.omni_chamfer_workspace_bytes.argtypes = [ci] * 4
+    lib.omni_chamfer_nn_f32.argtypes = [vp] * 4 + [ci] * 4 + [vp] * 5
+    lib.omni_chamfer_grad_f32.argtypes = [vp] * 6 + [ci] * 4 + [vp] * 4
     for name in EXPORTS:
         getattr(lib, name)          # AttributeError here = header/library mismatch
     _lib = lib

@@ -70,6 +70,7 @@ const OptName kOpts[] = {
     {"p2e_store", "OMNI_P2E_STORE", &OmniOptions::p2e_store, 1},
     {"fv_bwd_lds", "OMNI_FV_BWD_LDS", &OmniOptions::fv_bwd_lds, 1},
     {"geom_cache_max", "OMNI_GEOM_CACHE_MAX", &OmniOptions::geom_cache_max, 16},
+    {"chamfer_split", "OMNI_CHAMFER_SPLIT", &OmniOptions::chamfer_split, 1},
 };
 }  // namespace
 

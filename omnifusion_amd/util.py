@@ -28,6 +28,12 @@ Geometry of a depth map — mirror of util.py:332-382 and :426-451 (csrc/omni_no
     grad_y, grad_x = imgrad(img); yx = imgrad_yx(depth)
 
 The differentiable losses built on them are supervision.geometry.geometry_terms / normal_loss / gradient_loss.
+
+Chamfer distance — mirror of util.py:201-257 (csrc/omni_chamfer.hip):
+
+    loss = chamfer_distance_with_batch(p1, p2, debug=False)      # [B,N,D], [B,M,D] -> the sum of p1's nearest-neighbour distances, differentiable
+
+supervision.chamfer has the masked, bidirectional and mean forms and the nearest neighbours themselves.
 """
 import ctypes
 
@@ -170,3 +176,11 @@ def transform_pers(pers, THETA, PHI, output_h_pano, output_w_pano, h_fov, v_fov)
     from .equi_pers.pers2equi_torch import pers2equi
     equi, mask = pers2equi(pers, h_fov, v_fov, THETA, PHI, output_h_pano, output_w_pano)
     return equi, mask.unsqueeze(1)
+
+
+def chamfer_distance_with_batch(p1, p2, debug=False):
+    """Mirror of the reference's util.py:201-257: p1 [B,N,D], p2 [B,M,D] -> the sum over batch and points of min_j |p1[b,i] - p2[b,j]|, a 0-d
+    float32 tensor on the device, differentiable w.r.t. both clouds.  The reference repeats both clouds to [B,N,M,D] (12 N M bytes per item);
+    here nothing of that size exists.  `debug` (the reference prints intermediate tensors) is accepted and ignored."""
+    from .supervision.chamfer import chamfer_distance
+    return chamfer_distance(p1, p2, reduction="sum")
