@@ -356,6 +356,26 @@ int omni_confusion_matrix_i64(const int64_t* pred, const int64_t* gt, size_t n, 
 int omni_preprocess_rgb_u8(const unsigned char* src_hwc, float* dst_chw, int B, int Hs, int Ws, int H, int W, omni_stream_t stream);
 int omni_preprocess_depth_u16(const unsigned short* src, float* depth, unsigned char* mask, int B, int Hs, int Ws, int H, int W,
                               float min_depth, float max_depth, omni_stream_t stream);
+/* Training-time augmentation of the reference's loaders folded into the same pass (csrc/omni_augment.hip): random horizontal flip and
+ * yaw roll (dataset_loader_stanford.py:57-67), gamma (dataset_loader_360d.py:67-71), colour permutation (dataset_loader_stanford.py:70-73).
+ * Per item b the kernels read, from DEVICE memory, aug[b][5] = {flip, dx, perm0, perm1, perm2} (int32) and gamma[b] (float32; gamma may be
+ * NULL = no gamma).  flip then roll is one column map, out[y][x] = in[y][s(x)] with r = (x - dx) mod W, s(x) = r without flip and
+ * W-1-r with flip; colour is out[c] = in[perm[c]] ** gamma in the loader's channel order.  dx is reduced modulo W (negative values
+ * included) and perm modulo 3 inside the kernels; nothing is read back on the host, the calls are capturable and a replayed graph reads
+ * the table's current contents.  No atomics, no workspace: bitwise reproducible.
+ * omni_augment_rgb_u8 / omni_augment_depth_u16: the arithmetic of omni_preprocess_rgb_u8 / omni_preprocess_depth_u16 (INTER_AREA and its
+ * uint8 rounding happen BEFORE the map) sampled through s(x); gamma == 1 is bit-identical to no gamma.  Option "augment_lut" = 0 evaluates
+ * powf per value instead of through the 256-entry table a block builds (same bits).
+ * omni_augment_planes: the index map on planes [B,C,H,W] of elem_bytes (1, 2, 4, 8) bytes per element that already live on the device
+ * (label maps, masks, float32 depth or images), copied as bytes.  color = 1 (C == 3) also applies perm and, with gamma != NULL (float32
+ * elements only), powf.  inverse = 1 applies s^-1 instead — x' = x without flip, W-1-x with flip, t(x) = (x' + dx) mod W — and no colour:
+ * it puts a prediction made on an augmented batch back onto the original panorama.  src == dst is OMNI_ERR_INVALID. */
+int omni_augment_rgb_u8(const unsigned char* src_hwc, float* dst_chw, const int* aug, const float* gamma, int B, int Hs, int Ws, int H, int W,
+                        omni_stream_t stream);
+int omni_augment_depth_u16(const unsigned short* src, float* depth, unsigned char* mask, const int* aug, int B, int Hs, int Ws, int H, int W,
+                           float min_depth, float max_depth, omni_stream_t stream);
+int omni_augment_planes(const void* src, void* dst, int elem_bytes, const int* aug, const float* gamma, int B, int C, int H, int W,
+                        int color, int inverse, omni_stream_t stream);
 /* PNG decoding on the host (csrc/omni_png.hip; no GPU involved) — the two decode calls of dataset_loader_stanford.py:
  *   :85 cv2.imread(path)      -> kind 0: uint8 [H,W,3] in B,G,R order (alpha dropped, gray replicated, 16-bit samples >> 8)
  *   :96 cv2.imread(path, -1)  -> kind 1: the file's own samples, single-channel gray only: uint8 or uint16 (host byte order) [H,W]

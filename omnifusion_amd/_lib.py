@@ -52,6 +52,7 @@ EXPORTS = [
     "omni_guided_smoothness_workspace_bytes", "omni_guided_smoothness_f32", "omni_guided_smoothness_grad_f32",
     "omni_depth_smoothness_workspace_bytes", "omni_depth_smoothness_f32", "omni_depth_smoothness_grad_f32",
     "omni_chamfer_workspace_bytes", "omni_chamfer_nn_f32", "omni_chamfer_grad_f32",
+    "omni_augment_rgb_u8", "omni_augment_depth_u16", "omni_augment_planes",
 ]
 
 
@@ -127,6 +128,9 @@ def load():
     lib.omni_chamfer_workspace_bytes.argtypes = [ci] * 4
     lib.omni_chamfer_nn_f32.argtypes = [vp] * 4 + [ci] * 4 + [vp] * 5
     lib.omni_chamfer_grad_f32.argtypes = [vp] * 6 + [ci] * 4 + [vp] * 4
+    lib.omni_augment_rgb_u8.argtypes = [vp] * 4 + [ci] * 5 + [vp]
+    lib.omni_augment_depth_u16.argtypes = [vp] * 4 + [ci] * 5 + [cf, cf, vp]
+    lib.omni_augment_planes.argtypes = [vp, vp, ci, vp, vp] + [ci] * 6 + [vp]
     for name in EXPORTS:
         getattr(lib, name)          # AttributeError here = header/library mismatch
     _lib = lib

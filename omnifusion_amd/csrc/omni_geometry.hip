@@ -71,6 +71,7 @@ const OptName kOpts[] = {
     {"fv_bwd_lds", "OMNI_FV_BWD_LDS", &OmniOptions::fv_bwd_lds, 1},
     {"geom_cache_max", "OMNI_GEOM_CACHE_MAX", &OmniOptions::geom_cache_max, 16},
     {"chamfer_split", "OMNI_CHAMFER_SPLIT", &OmniOptions::chamfer_split, 1},
+    {"augment_lut", "OMNI_AUGMENT_LUT", &OmniOptions::augment_lut, 1},
 };
 }  // namespace
 

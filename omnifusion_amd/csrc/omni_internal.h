@@ -73,6 +73,7 @@ struct OmniOptions {
     int fv_bwd_lds;       // OMNI_FV_BWD_LDS     1 (default): the free-view backward scatters sum a block's target box in LDS where it fits | 0: global atomics only (same bits)
     int geom_cache_max;   // OMNI_GEOM_CACHE_MAX geometry handles kept per process (LRU), default 16
     int chamfer_split;    // OMNI_CHAMFER_SPLIT  1 (default): the nearest-neighbour search cuts the targets into chunks over gridDim.y where the queries alone give fewer than 2048 blocks | 0: never (same bits)
+    int augment_lut;      // OMNI_AUGMENT_LUT    1 (default): gamma of the uint8 augmentation kernels through a 256-entry table built per block in LDS | 0: powf per value (same bits)
 };
 OmniOptions& omni_options();
 int omni_num_cus();                // compute units of the current device (cached per device)
