@@ -536,6 +536,30 @@ int omni_geometry_terms_grad_f32(const float* pred, const float* gt, const float
                                  int erode_mask, const void* workspace, const float* grad_normal, const float* grad_grad, float* grad_pred,
                                  omni_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------------------------
+ * The plane-fit normals of a depth map (csrc/omni_planefit.hip; equi_pers/depth2normal.py).  float32 in and out, any
+ * H, W >= 1; `ray_tables` as above.  Over the 25 vertices p = ray * depth at offsets {-4,-2,0,2,4}^2 of a pixel (zero vectors outside the
+ * image, no wrap across the seam): M = sum p p^T, s = sum p, n = M^-1 s where det M >= 1e-5 and n = s otherwise, normal = n / max(|n|,
+ * 1e-12).  Moments, determinant and solve are float64 (the reference's float32 solve is off by 1e-2 at 512 x 1024); a NaN depth gives NaN
+ * normals at exactly the centres whose windows hold it.  Nothing is allocated, nothing synchronises.
+ * omni_planefit_normals_f32: depth [B,1,H,W] -> normals [B,3,H,W].
+ * omni_planefit_normals_grad_f32: grad_depth [B,1,H,W] = d <grad_normals, normals> / d depth for an upstream [B,3,H,W].
+ * omni_planefit_loss_f32: *loss = 1 - mean_b(sum_b(N(pred) . N(gt) mask) / sum(mask)) (train_erp_depth.py:271 with these normals; the
+ * mask sum is the whole batch's, the mask is multiplied in by value; erode_mask as in omni_geometry_terms_f32) from pred, gt, mask
+ * [B,1,H,W]; neither normal map is written.  A batch whose mask sum is 0: NaN.
+ * omni_planefit_loss_grad_f32: grad_pred = (*grad_out) d loss / d pred; `workspace` is the one omni_planefit_loss_f32 filled for the same
+ * arguments (it carries the mask sum).
+ * `workspace`: omni_planefit_workspace_bytes(B, H, W) bytes (0 for invalid arguments), any content on entry, 16-byte aligned: the sums
+ * of the loss and the [B,6,H,W] float64 map the two backward kernels hand over (the normals' backward uses that part alone). */
+size_t omni_planefit_workspace_bytes(int B, int H, int W);
+int omni_planefit_normals_f32(const float* depth, const float* ray_tables, int B, int H, int W, float* normals, omni_stream_t stream);
+int omni_planefit_normals_grad_f32(const float* depth, const float* ray_tables, const float* grad_normals, int B, int H, int W, void* workspace,
+                                   float* grad_depth, omni_stream_t stream);
+int omni_planefit_loss_f32(const float* pred, const float* gt, const float* mask, const float* ray_tables, int B, int H, int W, int erode_mask,
+                           void* workspace, float* loss, omni_stream_t stream);
+int omni_planefit_loss_grad_f32(const float* pred, const float* gt, const float* mask, const float* ray_tables, int B, int H, int W,
+                                int erode_mask, void* workspace, const float* grad_out, float* grad_pred, omni_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * The guided (edge-aware) smoothness term of the self-supervised objective (csrc/omni_smoothness.hip, DESIGN.md §15;
  * supervision/smoothness.py:3-8, spherical/derivatives.py:7-24,190-214, spherical/cartesian.py:14-50).  float32, B, C, H, W >= 1.

@@ -53,6 +53,8 @@ EXPORTS = [
     "omni_depth_smoothness_workspace_bytes", "omni_depth_smoothness_f32", "omni_depth_smoothness_grad_f32",
     "omni_chamfer_workspace_bytes", "omni_chamfer_nn_f32", "omni_chamfer_grad_f32",
     "omni_augment_rgb_u8", "omni_augment_depth_u16", "omni_augment_planes",
+    "omni_planefit_workspace_bytes", "omni_planefit_normals_f32", "omni_planefit_normals_grad_f32", "omni_planefit_loss_f32",
+    "omni_planefit_loss_grad_f32",
 ]
 
 
@@ -131,6 +133,12 @@ def load():
     lib.omni_augment_rgb_u8.argtypes = [vp] * 4 + [ci] * 5 + [vp]
     lib.omni_augment_depth_u16.argtypes = [vp] * 4 + [ci] * 5 + [cf, cf, vp]
     lib.omni_augment_planes.argtypes = [vp, vp, ci, vp, vp] + [ci] * 6 + [vp]
+    lib.omni_planefit_workspace_bytes.restype = sz
+    lib.omni_planefit_workspace_bytes.argtypes = [ci] * 3
+    lib.omni_planefit_normals_f32.argtypes = [vp, vp, ci, ci, ci, vp, vp]
+    lib.omni_planefit_normals_grad_f32.argtypes = [vp] * 3 + [ci] * 3 + [vp] * 3
+    lib.omni_planefit_loss_f32.argtypes = [vp] * 4 + [ci] * 4 + [vp] * 3
+    lib.omni_planefit_loss_grad_f32.argtypes = [vp] * 4 + [ci] * 4 + [vp] * 4
     for name in EXPORTS:
         getattr(lib, name)          # AttributeError here = header/library mismatch
     _lib = lib

@@ -15,6 +15,9 @@ erode_mask=True replaces the mask by mask * [mask != 0 at all eight neighbours] 
 kernels.  The loaders zero the ground truth where it is invalid; a normal next to such a hole is the normalised sum of four nearly cancelling
 unit vectors — rounding noise — so real, holey data wants erode_mask=True.  The default is the reference's formula.
 
+planefit_normal_loss(pred, gt, mask) is normal_loss's formula over the plane-fit normals of equi_pers.depth2normal (25 vertices per pixel, least squares
+in float64; csrc/omni_planefit.hip): one 0-d float32 tensor, H, W >= 1, the same masks and the same erode_mask.
+
 Masks may be bool, uint8 or float (multiplied in by value); non-contiguous inputs are made contiguous, as calculate_berhu_loss does.  A batch
 whose mask sum is 0 gives a NaN normal_loss, an item whose mask sum is 0 a NaN grad_loss (0 / 0, as calculate_berhu_loss), with NaN gradients
 for the items concerned.
@@ -68,7 +71,35 @@ class _GeometryTerms(torch.autograd.Function):
         return grad, None, None, None, None, None
 
 
-def _run(pred, gt, mask, erode_mask, terms):
+class _PlanefitLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, gt, mask, tab, erode):
+        lib = _lib.load()
+        B, _, H, W = pred.shape
+        ws = torch.empty(lib.omni_planefit_workspace_bytes(B, H, W) // 8 + 1, dtype=torch.float64, device=pred.device)
+        loss = torch.empty((), dtype=torch.float32, device=pred.device)
+        with torch.cuda.device(pred.device):
+            _lib.check(lib.omni_planefit_loss_f32(_p(pred), _p(gt), _p(mask), _p(tab), B, H, W, erode, _p(ws), _p(loss), _lib.stream_of(pred)),
+                       "planefit_normal_loss")
+        ctx.save_for_backward(pred, gt, mask, tab, ws)
+        ctx.erode = erode
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        pred, gt, mask, tab, ws = ctx.saved_tensors
+        lib = _lib.load()
+        B, _, H, W = pred.shape
+        go = grad_out.contiguous().to(torch.float32)
+        grad = torch.empty_like(pred)
+        with torch.cuda.device(pred.device):
+            _lib.check(lib.omni_planefit_loss_grad_f32(_p(pred), _p(gt), _p(mask), _p(tab), B, H, W, ctx.erode, _p(ws), _p(go), _p(grad),
+                                                       _lib.stream_of(pred)), "planefit_normal_loss backward")
+        return grad, None, None, None, None
+
+
+def _checked(pred, gt, mask):
+    """The argument checks of every entry here -> (pred, gt, mask) contiguous float32."""
     for t, name in ((pred, "pred"), (gt, "gt"), (mask, "mask")):
         if not isinstance(t, torch.Tensor):
             raise ValueError(f"{name} must be a tensor")
@@ -86,8 +117,13 @@ def _run(pred, gt, mask, erode_mask, terms):
     if not pred.is_floating_point() or not gt.is_floating_point():
         raise ValueError("pred and gt must be floating-point tensors")
     f = lambda t: t.contiguous().to(torch.float32)
+    return f(pred), f(gt), f(mask)
+
+
+def _run(pred, gt, mask, erode_mask, terms):
+    pred, gt, mask = _checked(pred, gt, mask)
     H, W = pred.shape[2:]
-    return _GeometryTerms.apply(f(pred), f(gt), f(mask), ray_tables(H, W, pred.device), terms, 1 if erode_mask else 0)
+    return _GeometryTerms.apply(pred, gt, mask, ray_tables(H, W, pred.device), terms, 1 if erode_mask else 0)
 
 
 def geometry_terms(pred, gt, mask, erode_mask=False):
@@ -103,3 +139,11 @@ def normal_loss(pred, gt, mask, erode_mask=False):
 def gradient_loss(pred, gt, mask, erode_mask=False):
     """geometry_terms(...)[1], bit for bit, without the normals."""
     return _run(pred, gt, mask, erode_mask, GRADIENT)[1]
+
+
+def planefit_normal_loss(pred, gt, mask, erode_mask=False):
+    """normal_loss's formula over the plane-fit normals of equi_pers.depth2normal (25 vertices per pixel, least squares in float64; csrc/omni_planefit.hip,
+    DESIGN.md §18) instead of the four cross products: the normals one wants on real, noisy depth.  Any H, W >= 1; neither normal map is written."""
+    pred, gt, mask = _checked(pred, gt, mask)
+    H, W = pred.shape[2:]
+    return _PlanefitLoss.apply(pred, gt, mask, ray_tables(H, W, pred.device), 1 if erode_mask else 0)
