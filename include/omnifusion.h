@@ -615,6 +615,36 @@ int omni_chamfer_grad_f32(const float* p1, const float* p2, const unsigned char*
                           const float* grad_dist, int B, int N, int M, int D, float* grad_p1, float* grad_p2, void* workspace,
                           omni_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * The backward of omni_conv2d_nhwc_f16x3_ws (csrc/omni_conv_bwd.hip): out = act(Z), Z = conv(src1 ++ src2, wt) + bias + res.
+ * fp32 NHWC tensors, wt fp32 [Cout][(ky,kx,c)], C1, C2, Cout multiples of 32, KH = KW = 1 or 3, stride 1 or 2, any pad >= 0, act NONE or
+ * RELU (GELU: OMNI_ERR_UNSUPPORTED — the forward does not keep the pre-activation).  rows = M * Ho * Wo.  Products are f16x3 as in the
+ * forward.  Nothing is allocated, nothing synchronises, nothing is read back; no floating-point atomics: the same bits on every run.
+ * omni_conv2d_bwd_epilogue_f32: dz[r][j] = grad_out[r][j] . [out[r][j] > 0] (act NONE: dz = grad_out; dz may then be NULL and the caller
+ * passes grad_out on as dZ); grad_bias[j] = sum_r dZ[r][j] (two fixed-order stages); the residual's gradient is dZ itself.  scale: two
+ * floats in device memory, 2^s and 2^-s, s = 8 - floor(log2 max|dZ|) clamped to [-126, 126]; s = 0 where dZ is all zero or its largest
+ * magnitude is not finite.  The two calls below multiply dZ by 2^s before they split it into halfs and their result by 2^-s (both exact), so
+ * gradients of any magnitude keep the precision of the format and grad_out . 2^n gives every gradient . 2^n bit for bit.
+ * omni_conv2d_bwd_data_f16x3: dx[m,y,x,ci] = sum_{ky,kx,co} dz[m,(y+p-ky)/s,(x+p-kx)/s,co] . wt[co][(ky,kx,ci)] over the taps where both
+ * divisions are exact and the source lies inside the Ho x Wo map; channels [0, C1) go to dx1 [M,H,W,C1], [C1, C1+C2) to dx2 [M,H,W,C2]; either
+ * may be NULL (not computed), not both; every element of a given tensor is written.  A tap that does not apply is not read.
+ * omni_conv2d_bwd_weight_f16x3: dw[co][(ky,kx,ci)] = sum_r dz[r][co] . A[r][(ky,kx,ci)], A the forward's implicit im2col of src1 ++ src2.
+ * The rows are cut into chunks of option "conv_wgrad_rows" rows (a multiple of 32, least 32; 0 = the library's plan), summed in chunk
+ * order: the result is a function of the inputs and the chunk length.
+ * `workspace`: omni_conv2d_bwd_workspace_bytes(...) bytes serve any of the three calls (0 for shapes outside the scope above; it depends on
+ * "conv_wgrad_rows"), any content, 16-byte aligned; the calls share no state through it — scale is the only hand-over.
+ * omni_conv2d_split_weights_f16x3: wt fp32 [Cout][K] -> wt16, the halfs [Cout][K/32][hi32|lo32] the forward reads, on the device. */
+size_t omni_conv2d_bwd_workspace_bytes(int M, int H, int W, int C1, int C2, int Cout, int KH, int KW, int stride, int pad);
+int omni_conv2d_bwd_epilogue_f32(const float* grad_out, const float* out, float* dz, float* grad_bias, float* scale, long long rows,
+                                 int Cout, int act, void* workspace, size_t ws_bytes, omni_stream_t stream);
+int omni_conv2d_bwd_data_f16x3(const float* dz, const float* wt, const float* scale, float* dx1, float* dx2, int M, int H, int W, int C1,
+                               int C2, int Cout, int KH, int KW, int stride, int pad, void* workspace, size_t ws_bytes,
+                               omni_stream_t stream);
+int omni_conv2d_bwd_weight_f16x3(const float* dz, const float* src1, const float* src2, const float* scale, float* dw, int M, int H, int W,
+                                 int C1, int C2, int Cout, int KH, int KW, int stride, int pad, void* workspace, size_t ws_bytes,
+                                 omni_stream_t stream);
+int omni_conv2d_split_weights_f16x3(const float* wt, void* wt16, int Cout, int K, omni_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

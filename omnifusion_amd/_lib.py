@@ -55,6 +55,8 @@ EXPORTS = [
     "omni_augment_rgb_u8", "omni_augment_depth_u16", "omni_augment_planes",
     "omni_planefit_workspace_bytes", "omni_planefit_normals_f32", "omni_planefit_normals_grad_f32", "omni_planefit_loss_f32",
     "omni_planefit_loss_grad_f32",
+    "omni_conv2d_bwd_workspace_bytes", "omni_conv2d_bwd_epilogue_f32", "omni_conv2d_bwd_data_f16x3", "omni_conv2d_bwd_weight_f16x3",
+    "omni_conv2d_split_weights_f16x3",
 ]
 
 
@@ -139,6 +141,12 @@ def load():
     lib.omni_planefit_normals_grad_f32.argtypes = [vp] * 3 + [ci] * 3 + [vp] * 3
     lib.omni_planefit_loss_f32.argtypes = [vp] * 4 + [ci] * 4 + [vp] * 3
     lib.omni_planefit_loss_grad_f32.argtypes = [vp] * 4 + [ci] * 4 + [vp] * 4
+    lib.omni_conv2d_bwd_workspace_bytes.restype = sz
+    lib.omni_conv2d_bwd_workspace_bytes.argtypes = [ci] * 10
+    lib.omni_conv2d_bwd_epilogue_f32.argtypes = [vp] * 5 + [ctypes.c_longlong, ci, ci, vp, sz, vp]
+    lib.omni_conv2d_bwd_data_f16x3.argtypes = [vp] * 5 + [ci] * 10 + [vp, sz, vp]
+    lib.omni_conv2d_bwd_weight_f16x3.argtypes = [vp] * 5 + [ci] * 10 + [vp, sz, vp]
+    lib.omni_conv2d_split_weights_f16x3.argtypes = [vp, vp, ci, ci, vp]
     for name in EXPORTS:
         getattr(lib, name)          # AttributeError here = header/library mismatch
     _lib = lib

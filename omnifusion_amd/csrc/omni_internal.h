@@ -74,6 +74,7 @@ struct OmniOptions {
     int geom_cache_max;   // OMNI_GEOM_CACHE_MAX geometry handles kept per process (LRU), default 16
     int chamfer_split;    // OMNI_CHAMFER_SPLIT  1 (default): the nearest-neighbour search cuts the targets into chunks over gridDim.y where the queries alone give fewer than 2048 blocks | 0: never (same bits)
     int augment_lut;      // OMNI_AUGMENT_LUT    1 (default): gamma of the uint8 augmentation kernels through a 256-entry table built per block in LDS | 0: powf per value (same bits)
+    int conv_wgrad_rows;  // OMNI_CONV_WGRAD_ROWS output pixels per chunk of the convolution's weight gradient (omni_conv_bwd.hip): 0 (default) the library's plan | n >= 32, rounded up to a multiple of 32 — changes the summation order of dW, nothing else
 };
 OmniOptions& omni_options();
 int omni_num_cus();                // compute units of the current device (cached per device)
