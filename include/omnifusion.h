@@ -645,6 +645,30 @@ int omni_conv2d_bwd_weight_f16x3(const float* dz, const float* src1, const float
                                  omni_stream_t stream);
 int omni_conv2d_split_weights_f16x3(const float* wt, void* wt16, int Cout, int K, omni_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Batch normalisation with a fused residual and ReLU, and its backward (csrc/omni_batchnorm.hip):
+ *     y = act(fmaf(x - mean, invstd . gamma, beta) + res),   fp32, contiguous NHWC: rows = M.H.W rows of C channels, C a multiple of 4,
+ * act NONE or RELU (GELU: OMNI_ERR_UNSUPPORTED).  gamma / beta [C] may be NULL (no affine), res may be NULL.  Nothing is allocated, nothing
+ * synchronises, nothing is read back; no atomics, every sum in a fixed order (partials and finish in double): the same bits on every run.
+ * omni_batchnorm_fwd_f32, training != 0: mean and the biased variance of each channel over the rows (rows >= 2), saved[0][c] = mean,
+ * saved[1][c] = invstd = 1 / sqrt(var + eps); with running buffers (both or neither) running_mean = (1 - momentum) running_mean + momentum mean
+ * and running_var likewise with var . rows / (rows - 1), in place.  training == 0: mean = running_mean, invstd from running_var (both
+ * required, unchanged); saved is written all the same, so the backward reads one pair.  eps > 0 and finite, momentum in [0, 1].
+ * omni_batchnorm_bwd_f32: dZ = g . [y > 0] (a select; act NONE: dZ = g, y is not read).  dbeta[c] = sum_r dZ, dgamma[c] = sum_r dZ . xhat,
+ * xhat = (x - mean) . invstd; dx = gamma . invstd . (dZ - dbeta / rows - xhat . dgamma / rows) in training mode, gamma . invstd . dZ in eval
+ * mode; dres = dZ (act RELU only: with act NONE the residual's gradient is g itself and dres must be NULL).  Every output pointer may be
+ * NULL (not computed), not all four; a pass nobody needs is not launched (no dx: no apply pass; eval mode without dgamma and dbeta: no
+ * reduction pass).  x, y, gamma, saved are the forward's; `training` and `act` must be the forward's.
+ * `workspace`: omni_batchnorm_workspace_bytes(rows, C) bytes (0 for arguments outside the scope), any content, 16-byte aligned; the eval-mode
+ * forward does not touch it.  The two calls share no state through it. */
+size_t omni_batchnorm_workspace_bytes(long long rows, int C);
+int omni_batchnorm_fwd_f32(const float* x, const float* res, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                           float* y, float* saved, long long rows, int C, int training, double momentum, double eps, int act,
+                           void* workspace, size_t ws_bytes, omni_stream_t stream);
+int omni_batchnorm_bwd_f32(const float* g, const float* x, const float* y, const float* gamma, const float* saved, float* dx, float* dres,
+                           float* dgamma, float* dbeta, long long rows, int C, int training, int act, void* workspace, size_t ws_bytes,
+                           omni_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

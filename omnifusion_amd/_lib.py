@@ -57,6 +57,7 @@ EXPORTS = [
     "omni_planefit_loss_grad_f32",
     "omni_conv2d_bwd_workspace_bytes", "omni_conv2d_bwd_epilogue_f32", "omni_conv2d_bwd_data_f16x3", "omni_conv2d_bwd_weight_f16x3",
     "omni_conv2d_split_weights_f16x3",
+    "omni_batchnorm_workspace_bytes", "omni_batchnorm_fwd_f32", "omni_batchnorm_bwd_f32",
 ]
 
 
@@ -147,6 +148,11 @@ def load():
     lib.omni_conv2d_bwd_data_f16x3.argtypes = [vp] * 5 + [ci] * 10 + [vp, sz, vp]
     lib.omni_conv2d_bwd_weight_f16x3.argtypes = [vp] * 5 + [ci] * 10 + [vp, sz, vp]
     lib.omni_conv2d_split_weights_f16x3.argtypes = [vp, vp, ci, ci, vp]
+    cd = ctypes.c_double
+    lib.omni_batchnorm_workspace_bytes.restype = sz
+    lib.omni_batchnorm_workspace_bytes.argtypes = [ctypes.c_longlong, ci]
+    lib.omni_batchnorm_fwd_f32.argtypes = [vp] * 8 + [ctypes.c_longlong, ci, ci, cd, cd, ci, vp, sz, vp]
+    lib.omni_batchnorm_bwd_f32.argtypes = [vp] * 9 + [ctypes.c_longlong, ci, ci, ci, vp, sz, vp]
     for name in EXPORTS:
         getattr(lib, name)          # AttributeError here = header/library mismatch
     _lib = lib

@@ -1,7 +1,12 @@
-"""Differentiable operators of libomnifusion_hip.so for torch models: the network's convolution with its backward.
+"""Differentiable operators of libomnifusion_hip.so for torch models: the network's convolution and its batch normalisation, each with
+its backward.
 
     y = conv2d(x, weight, bias=None, *, x2=None, res=None, stride=1, padding=0, act="none" | "relu")
     layer = Conv2d(64, 64, 3, padding=1, act="relu")          # an nn.Conv2d whose forward is the call above
+    y = batch_norm(x, weight=None, bias=None, running_mean=None, running_var=None, *, res=None, training=True, momentum=0.1, eps=1e-5,
+                   act="none" | "relu")
+    layer = BatchNorm2d(64, act="relu")                       # an nn.BatchNorm2d whose forward(x, res=None) is the call above
+    model, names = convert(model)                             # swaps the nn.Conv2d / nn.BatchNorm2d layers of a torch model in place
 
 y = act(conv(cat(x, x2), weight) + bias + res) — the operator that is about 99 % of spherical_fusion's work (csrc/omni_conv.hip, f16x3
 products on the matrix cores) — and its gradients w.r.t. x, x2, weight, bias and res (csrc/omni_conv_bwd.hip): the same
@@ -12,6 +17,13 @@ Tensors: x [M,C1,H,W], x2 [M,C2,H,W], weight [Cout,C1+C2,k,k], res and y [M,Cout
 without a copy and y is channels-last; other formats are converted.  Limits: C1, C2, Cout multiples of 32 (the concat is never
 materialised), k = 1 or 3, stride 1 or 2, no groups, no dilation; act "gelu" has no backward and is rejected (apply GELU outside).
 No double backward.  There is no CPU path.
+
+y = act(batch_norm(x) + res) (csrc/omni_batchnorm.hip) on x [M,C,H,W], C a multiple of 4: batch statistics over M.H.W with
+`training=True` (the running buffers, when given, are updated in place, the variance unbiased), the running statistics with
+`training=False` (the usual way to fine-tune).  Gradients w.r.t. x, weight, bias and res; the same rules: fixed summation order (in
+double), no atomics, no host synchronisation, only what autograd asks for, channels-last tensors without a copy.  The per-channel
+statistics of a BatchNorm3d over [B,C,P,P,N] are those of this operator over [M = B.N, C, P, P].  Not covered: momentum=None (the
+cumulative average reads a counter on the host), statistics across GPUs, fp16, double backward.
 """
 import ctypes
 
@@ -172,3 +184,171 @@ class Conv2d(torch.nn.Conv2d):
 
     def forward(self, x, x2=None, res=None):
         return conv2d(x, self.weight, self.bias, x2=x2, res=res, stride=self.stride[0], padding=self.padding[0], act=self.act)
+
+
+# ------------------------------------------------------------------------------------------------ batch normalisation
+def _check_bn_args(x, weight, bias, running_mean, running_var, res, training, momentum, eps, act):
+    """Every rejection of batch_norm, raised before anything is launched."""
+    for t, name, opt in ((x, "x", False), (weight, "weight", True), (bias, "bias", True), (running_mean, "running_mean", True),
+                         (running_var, "running_var", True), (res, "res", True)):
+        if t is None and opt:
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{name} must be a tensor on an MI355X device; there is no CPU path")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32 (got {t.dtype})")
+    if act not in ACTS:
+        if act == "gelu":
+            raise ValueError("act='gelu' is not supported: the batch normalisation's backward covers 'none' and 'relu' only (the forward "
+                             "does not keep the pre-activation); apply GELU outside")
+        raise ValueError(f"act must be 'none' or 'relu' (got {act!r})")
+    if x.dim() != 4 or x.numel() == 0:
+        raise ValueError(f"x must be a non-empty [M,C,H,W] tensor (got {tuple(x.shape)})")
+    M, C, H, W = x.shape
+    if C % 4:
+        raise ValueError(f"the channel count must be a multiple of 4 (got C = {C})")
+    for t, name in ((weight, "weight"), (bias, "bias"), (running_mean, "running_mean"), (running_var, "running_var")):
+        if t is not None and tuple(t.shape) != (C,):
+            raise ValueError(f"{name} must be [C] = [{C}] (got {tuple(t.shape)})")
+    for t, name in ((running_mean, "running_mean"), (running_var, "running_var")):
+        if t is not None and t.requires_grad:
+            raise ValueError(f"{name} is a buffer, updated in place: it cannot require a gradient")
+    if (running_mean is None) != (running_var is None):
+        raise ValueError("running_mean and running_var come together (got one of them)")
+    if res is not None and tuple(res.shape) != tuple(x.shape):
+        raise ValueError(f"res must have x's shape {tuple(x.shape)} (got {tuple(res.shape)})")
+    if momentum is None:
+        raise ValueError("momentum=None (the cumulative average) is not supported: it reads num_batches_tracked on the host")
+    if not isinstance(momentum, (int, float)) or not 0.0 <= momentum <= 1.0:
+        raise ValueError(f"momentum must be a number in [0, 1] (got {momentum!r})")
+    if not isinstance(eps, (int, float)) or not 0.0 < eps < float("inf"):
+        raise ValueError(f"eps must be a positive finite number (got {eps!r})")
+    if training and M * H * W == 1:
+        raise ValueError(f"Expected more than 1 value per channel when training (got x of shape {tuple(x.shape)})")
+    if not training and running_mean is None:
+        raise ValueError("training=False needs running_mean and running_var")
+
+
+def _bn_workspace(lib, rows, C, dev):
+    nbytes = lib.omni_batchnorm_workspace_bytes(rows, C)
+    if nbytes == 0:
+        raise ValueError(f"batch_norm: {rows} rows of {C} channels are outside the operator's scope")
+    return _empty(nbytes // 4, dtype=torch.float32, device=dev), nbytes
+
+
+class _BatchNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, res, training, momentum, eps, act):
+        lib = _lib.load()
+        xn, resn = _nhwc(x), _nhwc(res)
+        w = weight.contiguous() if weight is not None else None
+        b = bias.contiguous() if bias is not None else None
+        M, H, W, C = xn.shape
+        rows, dev = M * H * W, xn.device
+        y = _empty((M, H, W, C), dtype=torch.float32, device=dev)
+        saved = _empty((2, C), dtype=torch.float32, device=dev)
+        ws, nbytes = _bn_workspace(lib, rows, C, dev) if training else (None, 0)
+        with torch.cuda.device(dev):
+            _lib.check(lib.omni_batchnorm_fwd_f32(_p(xn), _p(resn), _p(w), _p(b), _p(running_mean), _p(running_var), _p(y), _p(saved), rows, C,
+                                                  int(training), float(momentum), float(eps), ACTS[act], _p(ws), nbytes, _lib.stream_of(xn)),
+                       "batch_norm")
+        ctx.conf = (bool(training), act)
+        ctx.save_for_backward(xn, w, saved, y if act == "relu" else None)
+        return _nchw(y)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        xn, w, saved, y = ctx.saved_tensors
+        training, act = ctx.conf
+        need_x, need_w, need_b, _, _, need_res = ctx.needs_input_grad[:6]
+        relu = act == "relu"
+        g = _nhwc(grad_out.to(torch.float32))
+        M, H, W, C = xn.shape
+        rows, dev = M * H * W, xn.device
+        new = lambda shape: _empty(shape, dtype=torch.float32, device=dev)
+        dx = new((M, H, W, C)) if need_x else None
+        dres = new((M, H, W, C)) if need_res and relu else None
+        dgamma, dbeta = new((C,)) if need_w else None, new((C,)) if need_b else None
+        if dx is not None or dres is not None or dgamma is not None or dbeta is not None:
+            reduce = need_w or need_b or (training and need_x)
+            ws, nbytes = _bn_workspace(lib, rows, C, dev) if reduce else (None, 0)
+            with torch.cuda.device(dev):
+                _lib.check(lib.omni_batchnorm_bwd_f32(_p(g), _p(xn), _p(y), _p(w), _p(saved), _p(dx), _p(dres), _p(dgamma), _p(dbeta), rows, C,
+                                                      int(training), ACTS[act], _p(ws), nbytes, _lib.stream_of(xn)),
+                           "batch_norm_bwd" if reduce else "batch_norm_bwd_apply")
+        if need_res and not relu:
+            dres = g                                                           # the residual's gradient is grad_out itself: no copy
+        return (_nchw(dx), dgamma, dbeta, None, None, _nchw(dres), None, None, None, None)
+
+
+def batch_norm(x, weight=None, bias=None, running_mean=None, running_var=None, *, res=None, training=True, momentum=0.1, eps=1e-5, act="none"):
+    """act(batch_norm(x) + res), differentiable w.r.t. x, weight, bias and res; running_mean / running_var are updated in place when
+    `training` (module docstring)."""
+    _check_bn_args(x, weight, bias, running_mean, running_var, res, training, momentum, eps, act)
+    return _BatchNorm.apply(x, weight, bias, running_mean, running_var, res, bool(training), momentum, eps, act)
+
+
+class BatchNorm2d(torch.nn.BatchNorm2d):
+    """nn.BatchNorm2d with the library's kernels under forward and backward: the same parameters, buffers and state dict.  `act`
+    ("none" | "relu") is fused; forward(x, res=None) takes the optional residual: y = act(bn(x) + res).  Batch statistics when
+    self.training or not track_running_stats, else the running ones."""
+
+    def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True, act="none", **kw):
+        if momentum is None:
+            raise ValueError("ops.BatchNorm2d: momentum=None (the cumulative average) is not supported: it reads num_batches_tracked on the host")
+        if act not in ACTS:
+            raise ValueError(f"ops.BatchNorm2d: act must be 'none' or 'relu' (got {act!r}; GELU has no backward here)")
+        if num_features % 4:
+            raise ValueError(f"ops.BatchNorm2d: the channel count must be a multiple of 4 (got {num_features})")
+        super().__init__(num_features, eps=eps, momentum=momentum, affine=affine, track_running_stats=track_running_stats, **kw)
+        self.act = act
+
+    def forward(self, x, res=None):
+        batch_stats = self.training or not self.track_running_stats
+        if self.training and self.track_running_stats:
+            self.num_batches_tracked.add_(1)                                   # on the device; nothing reads it here
+        return batch_norm(x, self.weight, self.bias, self.running_mean, self.running_var, res=res, training=batch_stats,
+                          momentum=self.momentum, eps=self.eps, act=self.act)
+
+
+def _conv_in_scope(m):
+    return (m.groups == 1 and tuple(m.dilation) == (1, 1) and m.padding_mode == "zeros" and not isinstance(m.padding, str)
+            and m.kernel_size[0] == m.kernel_size[1] and m.kernel_size[0] in (1, 3) and m.stride[0] == m.stride[1] and m.stride[0] in (1, 2)
+            and m.padding[0] == m.padding[1] and m.in_channels % 32 == 0 and m.out_channels % 32 == 0)
+
+
+def _swap_class(old, cls):
+    """A `cls` layer that holds old's own Parameter and buffer objects (and hooks, mode, dtype): no tensor is copied or re-created."""
+    new = cls.__new__(cls)
+    new.__dict__.update(old.__dict__)
+    for reg in ("_parameters", "_buffers", "_modules"):
+        new.__dict__[reg] = dict(old.__dict__[reg])
+    new.act = "none"
+    return new
+
+
+def convert(module):
+    """Replaces, in place, every nn.Conv2d inside Conv2d's scope (module docstring) and every nn.BatchNorm2d (channels a multiple of 4, a
+    numeric momentum) by the class of this module, act="none".  The new layers hold the SAME Parameter and buffer objects, so an optimiser
+    built before or after sees the same tensors and the state dict keeps its keys.  Everything else — a 3-channel stem, grouped or dilated
+    convolutions, momentum=None layers, subclasses — is left alone.  Returns (module, [the names replaced])."""
+    def swapped(m):
+        if type(m) is torch.nn.Conv2d and _conv_in_scope(m):
+            return _swap_class(m, Conv2d)
+        if type(m) is torch.nn.BatchNorm2d and m.momentum is not None and m.num_features % 4 == 0:
+            return _swap_class(m, BatchNorm2d)
+        return None
+
+    root = swapped(module)
+    if root is not None:
+        return root, [""]
+    names = []
+    for pname, parent in list(module.named_modules()):
+        for cname, child in list(parent.named_children()):
+            new = swapped(child)
+            if new is not None:
+                setattr(parent, cname, new)
+                names.append(f"{pname}.{cname}" if pname else cname)
+    return module, names
