@@ -669,6 +669,39 @@ int omni_batchnorm_bwd_f32(const float* g, const float* x, const float* y, const
                            float* dgamma, float* dbeta, long long rows, int C, int training, int act, void* workspace, size_t ws_bytes,
                            omni_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * The transformer's training operators beyond its linear layers (csrc/omni_transformer_bwd.hip): layer normalisation over
+ * the last axis with its backward, the backward of omni_attention_f32, the exact GELU with its backward.  fp32, contiguous.  Nothing is
+ * allocated, nothing synchronises, nothing is read back; no atomics, every sum in a fixed order that depends on the shapes alone: the same
+ * bits on every run.  Every rejection happens before a launch.  No backward reads anything a forward left behind except the operator's
+ * own inputs.
+ * omni_layernorm_fwd_f32: y[r] = (x[r] - mean_r) . rstd_r . gamma + beta over rows of C values, C a multiple of 4 in [4, 1024] (else
+ * INVALID / past 1024 UNSUPPORTED), biased variance, rstd = 1 / sqrt(var + eps), eps > 0; gamma / beta [C] may be NULL.  One wave per row; at
+ * C = 512 the bits of omni_layernorm512_f32.
+ * omni_layernorm_bwd_f32: recomputes mean and rstd from x (the forward's code).  xhat = (x - mean) . rstd, a = grad_y . gamma,
+ * dx = rstd . (a - mean_c(a) - xhat . mean_c(a . xhat)); dgamma[c] = sum_r grad_y . xhat, dbeta[c] = sum_r grad_y: per-slab partials in
+ * double, rows ascending, then the slabs ascending, one rounding.  Each of dx, dgamma, dbeta may be NULL (not computed), not all three; no
+ * dgamma and no dbeta: no reduction pass and no workspace.  gamma, eps: the forward's.
+ * `workspace`: omni_layernorm_bwd_workspace_bytes(rows, C) = nslab . 2 . C . 8 + rows . 8 bytes, rounded up to 16 (0 outside the scope), with
+ * slab = max(8, ceil(rows / 1024)) rows and nslab = ceil(rows / slab); any content, 16-byte aligned.
+ * omni_attention_bwd_f32: the gradients of omni_attention_f32's out [B.N, 512] w.r.t. q [B.N, 512] and kv [B.N, 1024] (k | v), N <= 64
+ * (else UNSUPPORTED).  P is recomputed from q and k with the forward's arithmetic.  dP_ij = dO_i . v_j, delta_i = sum_j P_ij dP_ij,
+ * dS_ij = P_ij (dP_ij - delta_i), dq_i = scale . sum_j dS_ij k_j, dv_j = sum_i P_ij dO_i, dk_j = scale . sum_i dS_ij q_i, every sum over i
+ * or j in ascending order.  dq or dkv may be NULL (not computed), not both; dkv is written whole.  `workspace` (needed for dkv only):
+ * omni_attention_bwd_workspace_bytes(B, N) = 2 . B . 4 . N . N floats (0 outside the scope), any content, 16-byte aligned.
+ * omni_gelu_fwd_f32: y = 0.5 x (1 + erf(x / sqrt 2)), the expression of the fused act = GELU epilogues; n a positive multiple of 4.
+ * omni_gelu_bwd_f32: dx = grad_y . (0.5 (1 + erf(x / sqrt 2)) + x exp(-x^2 / 2) / sqrt(2 pi)); reads x, not y. */
+size_t omni_layernorm_bwd_workspace_bytes(long long rows, int C);
+int omni_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta, float* y, long long rows, int C, float eps,
+                           omni_stream_t stream);
+int omni_layernorm_bwd_f32(const float* grad_y, const float* x, const float* gamma, float* dx, float* dgamma, float* dbeta, long long rows,
+                           int C, float eps, void* workspace, size_t ws_bytes, omni_stream_t stream);
+size_t omni_attention_bwd_workspace_bytes(int B, int N);
+int omni_attention_bwd_f32(const float* q, const float* kv, const float* grad_out, float* dq, float* dkv, int B, int N, void* workspace,
+                           size_t ws_bytes, omni_stream_t stream);
+int omni_gelu_fwd_f32(const float* x, float* y, long long n, omni_stream_t stream);
+int omni_gelu_bwd_f32(const float* grad_y, const float* x, float* dx, long long n, omni_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,6 +58,8 @@ EXPORTS = [
     "omni_conv2d_bwd_workspace_bytes", "omni_conv2d_bwd_epilogue_f32", "omni_conv2d_bwd_data_f16x3", "omni_conv2d_bwd_weight_f16x3",
     "omni_conv2d_split_weights_f16x3",
     "omni_batchnorm_workspace_bytes", "omni_batchnorm_fwd_f32", "omni_batchnorm_bwd_f32",
+    "omni_layernorm_bwd_workspace_bytes", "omni_layernorm_fwd_f32", "omni_layernorm_bwd_f32",
+    "omni_attention_bwd_workspace_bytes", "omni_attention_bwd_f32", "omni_gelu_fwd_f32", "omni_gelu_bwd_f32",
 ]
 
 
@@ -153,6 +155,16 @@ def load():
     lib.omni_batchnorm_workspace_bytes.argtypes = [ctypes.c_longlong, ci]
     lib.omni_batchnorm_fwd_f32.argtypes = [vp] * 8 + [ctypes.c_longlong, ci, ci, cd, cd, ci, vp, sz, vp]
     lib.omni_batchnorm_bwd_f32.argtypes = [vp] * 9 + [ctypes.c_longlong, ci, ci, ci, vp, sz, vp]
+    ll = ctypes.c_longlong
+    lib.omni_layernorm_bwd_workspace_bytes.restype = sz
+    lib.omni_layernorm_bwd_workspace_bytes.argtypes = [ll, ci]
+    lib.omni_layernorm_fwd_f32.argtypes = [vp] * 4 + [ll, ci, cf, vp]
+    lib.omni_layernorm_bwd_f32.argtypes = [vp] * 6 + [ll, ci, cf, vp, sz, vp]
+    lib.omni_attention_bwd_workspace_bytes.restype = sz
+    lib.omni_attention_bwd_workspace_bytes.argtypes = [ci, ci]
+    lib.omni_attention_bwd_f32.argtypes = [vp] * 5 + [ci, ci, vp, sz, vp]
+    lib.omni_gelu_fwd_f32.argtypes = [vp, vp, ll, vp]
+    lib.omni_gelu_bwd_f32.argtypes = [vp] * 3 + [ll, vp]
     for name in EXPORTS:
         getattr(lib, name)          # AttributeError here = header/library mismatch
     _lib = lib

@@ -24,6 +24,18 @@ y = act(batch_norm(x) + res) (csrc/omni_batchnorm.hip) on x [M,C
 double), no atomics, no host synchronisation, only what autograd asks for, channels-last tensors without a copy.  The per-channel
 statistics of a BatchNorm3d over [B,C,P,P,N] are those of this operator over [M = B.N, C, P, P].  Not covered: momentum=None (the
 cumulative average reads a counter on the host), statistics across GPUs, fp16, double backward.
+
+The transformer between layer4 and the decoder (csrc/omni_transformer_bwd.hip), under the reference's state-dict names:
+
+    y = layer_norm(x, weight=None, bias=None, eps=1e-5)       # over the last axis of x [..., C], C a multiple of 4, C <= 1024
+    y = gelu(x)                                               # exact (erf); x.numel() a multiple of 4
+    o = attention(q, kv, batch)                               # q [B.N, 512], kv [B.N, 1024] (k | v) -> [B.N, 512]; 4 heads of 128, N <= 64
+    y = linear(x, weight, bias=None, res=None)                # x [rows, K] -> x W^T + bias + res through conv2d (K, out multiples of 32)
+    LayerNorm, GELU, Linear                                   # the torch layers' parameters and state dicts
+    TransformerBlock(512, 4), TransformerCascade(512, num_patch, depth=6, num_heads=4)
+
+The same rules: fp32, fixed summation orders, no atomics, no host synchronisation, only the gradients autograd asks for.  No backward keeps
+anything of its forward but the operator's inputs: layer_norm recomputes its statistics, attention its probabilities, gelu reads x.
 """
 import ctypes
 
@@ -311,6 +323,291 @@ class BatchNorm2d(torch.nn.BatchNorm2d):
             self.num_batches_tracked.add_(1)                                   # on the device; nothing reads it here
         return batch_norm(x, self.weight, self.bias, self.running_mean, self.running_var, res=res, training=batch_stats,
                           momentum=self.momentum, eps=self.eps, act=self.act)
+
+
+# ------------------------------------------------------------------------------------------------ the transformer
+LN_MAX_C = 1024                # one wave per row, four quads per lane
+ATT_DIM, ATT_HEADS, ATT_MAX_N = 512, 4, 64
+
+
+def _check_f32_dev(named, optional=()):
+    for name, t in named:
+        if t is None and name in optional:
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{name} must be a tensor on an MI355X device; there is no CPU path")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32 (got {t.dtype})")
+
+
+def _check_ln_width(who, C):
+    if C % 4 or C < 4:
+        raise ValueError(f"{who}: the normalised axis must be a positive multiple of 4 (got C = {C})")
+    if C > LN_MAX_C:
+        raise ValueError(f"{who}: at most {LN_MAX_C} values per row (got C = {C})")
+
+
+def _check_ln_args(x, weight, bias, eps):
+    _check_f32_dev((("x", x), ("weight", weight), ("bias", bias)), optional=("weight", "bias"))
+    if x.dim() < 1 or x.numel() == 0:
+        raise ValueError(f"x must be a non-empty [..., C] tensor (got {tuple(x.shape)})")
+    C = x.shape[-1]
+    _check_ln_width("layer_norm", C)
+    for t, name in ((weight, "weight"), (bias, "bias")):
+        if t is not None and tuple(t.shape) != (C,):
+            raise ValueError(f"{name} must be [C] = [{C}] (got {tuple(t.shape)})")
+    if not isinstance(eps, (int, float)) or not 0.0 < eps < float("inf"):
+        raise ValueError(f"eps must be a positive finite number (got {eps!r})")
+
+
+class _LayerNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps):
+        lib = _lib.load()
+        C = x.shape[-1]
+        xc = x.contiguous().view(-1, C)
+        w = weight.contiguous() if weight is not None else None
+        b = bias.contiguous() if bias is not None else None
+        rows, dev = xc.shape[0], xc.device
+        y = _empty((rows, C), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.omni_layernorm_fwd_f32(_p(xc), _p(w), _p(b), _p(y), rows, C, float(eps), _lib.stream_of(xc)), "layer_norm")
+        ctx.eps = float(eps)
+        ctx.save_for_backward(xc, w)
+        return y.view(x.shape)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        xc, w = ctx.saved_tensors
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        rows, C = xc.shape
+        dev = xc.device
+        if not (need_x or need_w or need_b):
+            return None, None, None, None
+        g = grad_out.to(torch.float32).contiguous().view(rows, C)
+        new = lambda shape: _empty(shape, dtype=torch.float32, device=dev)
+        dx = new((rows, C)) if need_x else None
+        dgamma, dbeta = new((C,)) if need_w else None, new((C,)) if need_b else None
+        ws, nbytes = None, 0
+        if need_w or need_b:
+            nbytes = lib.omni_layernorm_bwd_workspace_bytes(rows, C)
+            if nbytes == 0:
+                raise ValueError(f"layer_norm: {rows} rows of {C} values are outside the operator's scope")
+            ws = new((nbytes // 4,))
+        with torch.cuda.device(dev):
+            _lib.check(lib.omni_layernorm_bwd_f32(_p(g), _p(xc), _p(w), _p(dx), _p(dgamma), _p(dbeta), rows, C, ctx.eps, _p(ws), nbytes,
+                                                  _lib.stream_of(xc)), "layer_norm_bwd")
+        return (dx.view(grad_out.shape) if dx is not None else None), dgamma, dbeta, None
+
+
+def layer_norm(x, weight=None, bias=None, eps=1e-5):
+    """Layer normalisation over the last axis of x [..., C] (biased variance, eps inside the root), differentiable w.r.t. x, weight and bias.
+    At C = 512 the forward gives the bits of the engine's omni_layernorm512_f32."""
+    _check_ln_args(x, weight, bias, eps)
+    return _LayerNorm.apply(x, weight, bias, eps)
+
+
+class LayerNorm(torch.nn.LayerNorm):
+    """nn.LayerNorm over ONE axis with the library's kernels under forward and backward: the same parameters and state dict."""
+
+    def __init__(self, normalized_shape, eps=1e-5, elementwise_affine=True, bias=True, **kw):
+        shape = (normalized_shape,) if isinstance(normalized_shape, int) else tuple(normalized_shape)
+        if len(shape) != 1:
+            raise ValueError(f"ops.LayerNorm: one normalised axis (got normalized_shape = {shape})")
+        _check_ln_width("ops.LayerNorm", shape[0])
+        if not isinstance(eps, (int, float)) or not 0.0 < eps < float("inf"):
+            raise ValueError(f"ops.LayerNorm: eps must be a positive finite number (got {eps!r})")
+        super().__init__(shape, eps=eps, elementwise_affine=elementwise_affine, bias=bias, **kw)
+
+    def forward(self, x):
+        return layer_norm(x, self.weight, self.bias, self.eps)
+
+
+class _Gelu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        lib = _lib.load()
+        xc = x.contiguous()
+        y = _empty(tuple(xc.shape), dtype=torch.float32, device=xc.device)
+        with torch.cuda.device(xc.device):
+            _lib.check(lib.omni_gelu_fwd_f32(_p(xc), _p(y), xc.numel(), _lib.stream_of(xc)), "gelu")
+        ctx.save_for_backward(xc)                                              # x, not y: the backward needs erf and exp of x
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        xc, = ctx.saved_tensors
+        g = grad_out.to(torch.float32).contiguous()
+        dx = _empty(tuple(xc.shape), dtype=torch.float32, device=xc.device)
+        with torch.cuda.device(xc.device):
+            _lib.check(lib.omni_gelu_bwd_f32(_p(g), _p(xc), _p(dx), xc.numel(), _lib.stream_of(xc)), "gelu_bwd")
+        return dx
+
+
+def gelu(x):
+    """0.5 x (1 + erf(x / sqrt 2)), the expression of the library's fused GELU epilogues, differentiable; x.numel() a multiple of 4."""
+    _check_f32_dev((("x", x),))
+    if x.numel() == 0 or x.numel() % 4:
+        raise ValueError(f"gelu: the element count must be a positive multiple of 4 (got {x.numel()})")
+    return _Gelu.apply(x)
+
+
+class GELU(torch.nn.Module):
+    def forward(self, x):
+        return gelu(x)
+
+
+def _check_attention_args(q, kv, batch):
+    _check_f32_dev((("q", q), ("kv", kv)))
+    if not isinstance(batch, int) or isinstance(batch, bool) or batch < 1:
+        raise ValueError(f"batch must be a positive int (got {batch!r})")
+    if q.dim() != 2 or kv.dim() != 2 or q.shape[0] == 0:
+        raise ValueError(f"q must be a non-empty [B.N, 512] tensor and kv [B.N, 1024] (got {tuple(q.shape)} and {tuple(kv.shape)})")
+    if q.shape[1] != ATT_DIM or kv.shape[1] != 2 * ATT_DIM:
+        raise ValueError(f"attention: the model width is 512, four heads of 128: q [B.N, 512], kv [B.N, 1024] (got {tuple(q.shape)} and "
+                         f"{tuple(kv.shape)})")
+    rows = q.shape[0]
+    if kv.shape[0] != rows or rows % batch:
+        raise ValueError(f"attention: q and kv must have the same B.N rows, a multiple of batch = {batch} (got {rows} and {kv.shape[0]})")
+    if rows // batch > ATT_MAX_N:
+        raise ValueError(f"attention: at most {ATT_MAX_N} tokens per item (got N = {rows // batch})")
+    return rows // batch
+
+
+class _Attention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, kv, batch, N):
+        lib = _lib.load()
+        qc, kvc = q.contiguous(), kv.contiguous()
+        out = _empty((batch * N, ATT_DIM), dtype=torch.float32, device=qc.device)
+        with torch.cuda.device(qc.device):
+            _lib.check(lib.omni_attention_f32(_p(qc), _p(kvc), _p(out), batch, N, _lib.stream_of(qc)), "attention")
+        ctx.conf = (batch, N)
+        ctx.save_for_backward(qc, kvc)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        qc, kvc = ctx.saved_tensors
+        batch, N = ctx.conf
+        need_q, need_kv = ctx.needs_input_grad[:2]
+        if not (need_q or need_kv):
+            return None, None, None, None
+        dev = qc.device
+        g = grad_out.to(torch.float32).contiguous()
+        dq = _empty((batch * N, ATT_DIM), dtype=torch.float32, device=dev) if need_q else None
+        dkv = _empty((batch * N, 2 * ATT_DIM), dtype=torch.float32, device=dev) if need_kv else None
+        ws, nbytes = None, 0
+        if need_kv:
+            nbytes = lib.omni_attention_bwd_workspace_bytes(batch, N)
+            if nbytes == 0:
+                raise ValueError(f"attention: {batch} items of {N} tokens are outside the operator's scope")
+            ws = _empty((nbytes // 4,), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.omni_attention_bwd_f32(_p(qc), _p(kvc), _p(g), _p(dq), _p(dkv), batch, N, _p(ws), nbytes, _lib.stream_of(qc)),
+                       "attention_bwd")
+        return dq, dkv, None, None
+
+
+def attention(q, kv, batch):
+    """softmax(q k^T / sqrt(128)) v per item and head: q [B.N, 512], kv [B.N, 1024] (k at column 0, v at column 512), B = batch ->
+    [B.N, 512].  The forward is the engine's omni_attention_f32; differentiable w.r.t. q and kv."""
+    N = _check_attention_args(q, kv, batch)
+    return _Attention.apply(q, kv, batch, N)
+
+
+def linear(x, weight, bias=None, res=None):
+    """x W^T + bias + res for x [rows, K], weight [out, K], res [rows, out]: conv2d on [rows, K, 1, 1] (its kernels, its backward, its
+    checks: K and out multiples of 32)."""
+    _check_f32_dev((("x", x), ("weight", weight), ("bias", bias), ("res", res)), optional=("bias", "res"))
+    if x.dim() != 2 or weight.dim() != 2 or x.numel() == 0:
+        raise ValueError(f"x must be a non-empty [rows, K] tensor and weight [out, K] (got {tuple(x.shape)} and {tuple(weight.shape)})")
+    rows, out = x.shape[0], weight.shape[0]
+    if res is not None and tuple(res.shape) != (rows, out):
+        raise ValueError(f"res must have the result's shape {(rows, out)} (got {tuple(res.shape)})")
+    y = conv2d(x[:, :, None, None], weight[:, :, None, None], bias, res=res[:, :, None, None] if res is not None else None)
+    return y.reshape(rows, out)
+
+
+class Linear(torch.nn.Linear):
+    """nn.Linear with the convolution's kernels under forward and backward; forward(x [..., K], res=None) adds the residual in the kernel."""
+
+    def forward(self, x, res=None):
+        if not isinstance(x, torch.Tensor) or x.dim() < 1:
+            raise ValueError("x must be a tensor on an MI355X device; there is no CPU path")
+        lead = x.shape[:-1]
+        y = linear(x.reshape(-1, x.shape[-1]), self.weight, self.bias, res.reshape(-1, self.out_features) if res is not None else None)
+        return y.reshape(*lead, self.out_features)
+
+
+def _check_transformer_conf(who, dim, num_heads):
+    if dim != ATT_DIM or num_heads != ATT_HEADS:
+        raise ValueError(f"{who}: the attention kernels cover width 512 with 4 heads of 128 (got dim = {dim}, num_heads = {num_heads})")
+
+
+class _AttentionLayers(torch.nn.Module):
+    def __init__(self, dim):
+        super().__init__()
+        self.q, self.kv, self.proj = Linear(dim, dim, bias=False), Linear(dim, 2 * dim, bias=False), Linear(dim, dim)
+
+
+class _MlpLayers(torch.nn.Module):
+    def __init__(self, dim):
+        super().__init__()
+        self.fc1, self.fc2 = Linear(dim, 4 * dim), Linear(4 * dim, dim)
+
+
+class TransformerBlock(torch.nn.Module):
+    """The reference's pre-LN block under its parameter names (norm1, attn.q, attn.kv, attn.proj, norm2, mlp.fc1, mlp.fc2):
+    x + proj(attention(q(norm1 x), kv(norm1 x))), then x + fc2(gelu(fc1(norm2 x))); the two additions are the `res` of proj and fc2.
+    forward(x [B.N, 512], batch = B).  Dropout and drop-path are identity in the reference's configuration and are not built."""
+
+    def __init__(self, dim=ATT_DIM, num_heads=ATT_HEADS):
+        _check_transformer_conf("ops.TransformerBlock", dim, num_heads)
+        super().__init__()
+        self.norm1 = LayerNorm(dim, eps=1e-5)
+        self.attn = _AttentionLayers(dim)
+        self.norm2 = LayerNorm(dim, eps=1e-5)
+        self.mlp = _MlpLayers(dim)
+
+    def forward(self, x, batch):
+        y = self.norm1(x)
+        a = attention(self.attn.q(y), self.attn.kv(y), batch)
+        x = self.attn.proj(a, res=x)
+        return self.mlp.fc2(gelu(self.mlp.fc1(self.norm2(x))), res=x)
+
+
+class TransformerCascade(torch.nn.Module):
+    """The reference's Transformer_cascade under its parameter names (pos_emb [1, num_patch, 512], layer.{i}, encoder_norm with eps 1e-6):
+    forward(x [bs, num_patch, 512]) -> [bs, num_patch, 512].  The `transformer.*` entries of a spherical_fusion state dict load into it."""
+
+    def __init__(self, emb_dims=ATT_DIM, num_patch=18, depth=6, num_heads=ATT_HEADS):
+        _check_transformer_conf("ops.TransformerCascade", emb_dims, num_heads)
+        if not isinstance(num_patch, int) or not 1 <= num_patch <= ATT_MAX_N:
+            raise ValueError(f"ops.TransformerCascade: 1 to {ATT_MAX_N} patches (got num_patch = {num_patch!r})")
+        if not isinstance(depth, int) or depth < 1:
+            raise ValueError(f"ops.TransformerCascade: depth >= 1 (got {depth!r})")
+        super().__init__()
+        self.layer = torch.nn.ModuleList([TransformerBlock(emb_dims, num_heads) for _ in range(depth)])
+        self.encoder_norm = LayerNorm(emb_dims, eps=1e-6)
+        self.pos_emb = torch.nn.Parameter(torch.zeros(1, num_patch, emb_dims))
+        torch.nn.init.normal_(self.pos_emb, std=0.02)
+
+    def forward(self, x):
+        _check_f32_dev((("x", x),))
+        if x.dim() != 3 or tuple(x.shape[1:]) != tuple(self.pos_emb.shape[1:]) or x.shape[0] == 0:
+            raise ValueError(f"x must be [bs, {self.pos_emb.shape[1]}, {self.pos_emb.shape[2]}] (got {tuple(x.shape)})")
+        bs, N, C = x.shape
+        h = (x + self.pos_emb).reshape(bs * N, C)
+        for blk in self.layer:
+            h = blk(h, bs)
+        return self.encoder_norm(h).reshape(bs, N, C)
 
 
 def _conv_in_scope(m):
