@@ -668,6 +668,18 @@ static void conv_sh_select(const ShConvArgs& a, int fmt, hipStream_t s)
     // 0: 64x64 everywhere; 1: 128x64 (4 waves); 2: 128x128 (4 waves); 3 / 4: the 8-wave forms everywhere; 5..7: auto without 256x128, with 64 / 128 / 256 blocks
     int tile = omni_options().conv_sh_tile;
     if (tile < 0) tile = 8;
+    // 3x3 on 8 x 8 and 4 x 4 images: the position-major form of the two ping-pong tile kernels (omni_conv_pm.hip) skips the K-steps of the taps that are
+    // zero padding for every row of a tile — the same bits, so the choice may depend on anything.  Option conv_pm: 1 (default) where the launch would take
+    // one of those two kernels | 0 never | 2 wherever the shape allows, whatever the row count (tests) | 3 / 4: as 1 for the 8 x 8 / the 4 x 4 images only
+    const int pm = omni_options().conv_pm;
+    const bool pm_shape = pm > 0 && KH == 3 && KW == 3 && stride == 1 && pad == 1 && H == W && (W == 8 || W == 4) && Cout % 64 == 0 && !a.post &&
+                          omni_options().conv_pingpong && !(pm == 3 && W != 8) && !(pm == 4 && W != 4);
+    if (pm_shape && pm == 2) { omni_conv_pm_launch(&a, Cout % 128 == 0 ? 128 : 64, X1, s); return; }
+    const bool big256 = tile == 8 && Cout % 128 == 0 && ((rows + 255) / 256) * (long long)(Cout / 128) * a.splitk >= std::max(1, omni_options().conv_big_blocks);
+    if (pm_shape && tile == 8 && !big256) {
+        if (Cout % 128 == 0 && ((rows + 127) / 128) * (long long)(Cout / 128) * a.splitk >= 128) { omni_conv_pm_launch(&a, 128, X1, s); return; }
+        if (((rows + 127) / 128) * (long long)(Cout / 64) * a.splitk >= 128) { omni_conv_pm_launch(&a, 64, X1, s); return; }
+    }
     if (Cout % 64 != 0) launch_sh<X1, 128, 32, 4, 1>(a, s);
     else if (tile == 2 && Cout % 128 == 0) launch_sh<X1, 128, 128, 2, 2>(a, s);
     else if (tile == 1) launch_sh<X1, 128, 64, 2, 2>(a, s);
@@ -772,7 +784,7 @@ extern "C" int omni_sh_overflow(int* flag, int reset)
     OMNI_HIP(hipDeviceSynchronize());                    // diagnostic entry point, never on the hot path
     unsigned v = 0;
     if (omni_sh_overflow_conv(&v, reset) != 0 || omni_sh_overflow_halo(&v, reset) != 0 || omni_sh_overflow_up2(&v, reset) != 0 ||
-        omni_sh_overflow_rows(&v, reset) != 0 || omni_sh_overflow_net(&v, reset) != 0)
+        omni_sh_overflow_rows(&v, reset) != 0 || omni_sh_overflow_net(&v, reset) != 0 || omni_sh_overflow_pm(&v, reset) != 0)
         OMNI_FAIL(OMNI_ERR_HIP, "omni_sh_overflow: could not read the device flag");
     *flag = v ? 1 : 0;
     return OMNI_OK;

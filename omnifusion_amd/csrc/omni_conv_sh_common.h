@@ -288,6 +288,9 @@ constexpr int HT_W = 32, HPW = HT_W + 2;                     // the halo kernels
 // omni_conv_halo.hip: conv3x3_halo_sh_kernel<bn, th, up2, iw, x1> on `grid` blocks of 64 * th threads; aborts on a form that is not instantiated.  `args`: the caller's
 // ShConvArgs (the type lives in every unit's anonymous namespace, like the kernels that take it, so it crosses as bytes)
 void omni_halo_launch(const void* args, int bn, int th, bool up2, int iw, bool x1, unsigned grid, hipStream_t s);
+// omni_conv_pm.hip: conv_pm_sh_kernel<bn, x1>, the position-major form of the 128 x bn ping-pong tile kernel (3x3, stride 1, pad 1, H = W in {4, 8}; bn 128 | 64)
+void omni_conv_pm_launch(const void* args, int bn, bool x1, hipStream_t s);
+int omni_sh_overflow_pm(unsigned* out, int reset);
 // the sticky range flag of omni_sh.h, one copy per translation unit whose kernels write SH: omni_sh_overflow (omni_conv_sh.hip) reads them all
 int omni_sh_overflow_halo(unsigned* out, int reset);
 int omni_sh_overflow_up2(unsigned* out, int reset);
