@@ -622,6 +622,7 @@ extern "C" int omni_gemm_sh_f16x3_ln512_ws(const void* x, const void* wt16, cons
     return OMNI_OK;
 }
 
+constexpr int OMNI_HALO2_MIN_BLOCKS = 256;               // option conv_halo2 = 1: the least number of halo2_sh_kernel blocks a launch must have (a block per CU)
 // The kernel choice of conv2d_sh_impl (everything but the checks and the split-K second pass), once per arithmetic mode: X1 (fmt bit 3) picks the
 // f16x1 instantiation of whichever form the shape and the tuning options select — the same forms, the same block counts.
 template <bool X1>
@@ -630,6 +631,16 @@ static void conv_sh_select(const ShConvArgs& a, int fmt, hipStream_t s)
     const int KH = a.KH, KW = a.KW, stride = a.stride, pad = a.pad, H = a.H, W = a.W, M = a.M, Cout = a.Cout;
     const int ksteps = KH * KW * ((a.C1 + a.C2) / 32);
     const long long rows = a.rows;
+    // 64 output channels per block on 256-pixel tiles with 64 x 64 wave tiles (omni_conv_halo2.hip): the two 64-channel halo forms below with 0.59x the
+    // operand bytes into LDS and 0.56x the fragment reads per matrix instruction — the same bits, so the choice may depend on anything.  Option conv_halo2:
+    // 0 never | 1 where the launch has at least OMNI_HALO2_MIN_BLOCKS blocks of the new size | 2 wherever the shape allows (tests) | n > 2: as 1 with n blocks
+    // (tuning).  Never for the latency form (fmt bit 2), nor where an option asks for the tile kernels or for 32-channel blocks.
+    if (const int h2 = omni_options().conv_halo2; h2 > 0 && a.splitk <= 1 && KH == 3 && KW == 3 && stride == 1 && pad == 1 && Cout % 64 == 0 && rows % 256 == 0 &&
+        !(fmt & 4) && !omni_options().conv_nohalo && omni_options().conv_halo_bn != 32) {
+        const int iw = (H == 16 && W == 16 && omni_options().conv_img > 0) ? 16 : (W % HT_W == 0 && H % 8 == 0) ? 0 : -1;
+        const long long blocks = (rows / 256) * (Cout / 64);
+        if (iw >= 0 && (h2 == 2 || blocks >= (h2 == 1 ? OMNI_HALO2_MIN_BLOCKS : h2))) { omni_halo2_launch(&a, iw, X1, s); return; }
+    }
     // small square images: the halo kernel over bands of whole image rows (IW > 0) — 16 x 16 (layer2, de_conv1_x: 61.6 -> 49.3 us per layer2
     // convolution at 8 panoramas) by default, 8 x 8 as well with conv_img = 2 (layer3: 52.7 -> 50.9)
     // (the choice must not depend on the number of images: a panorama's bits are the same in every batch size; a caller that runs ONE panorama,
@@ -784,7 +795,8 @@ extern "C" int omni_sh_overflow(int* flag, int reset)
     OMNI_HIP(hipDeviceSynchronize());                    // diagnostic entry point, never on the hot path
     unsigned v = 0;
     if (omni_sh_overflow_conv(&v, reset) != 0 || omni_sh_overflow_halo(&v, reset) != 0 || omni_sh_overflow_up2(&v, reset) != 0 ||
-        omni_sh_overflow_rows(&v, reset) != 0 || omni_sh_overflow_net(&v, reset) != 0 || omni_sh_overflow_pm(&v, reset) != 0)
+        omni_sh_overflow_rows(&v, reset) != 0 || omni_sh_overflow_net(&v, reset) != 0 || omni_sh_overflow_pm(&v, reset) != 0 ||
+        omni_sh_overflow_halo2(&v, reset) != 0)
         OMNI_FAIL(OMNI_ERR_HIP, "omni_sh_overflow: could not read the device flag");
     *flag = v ? 1 : 0;
     return OMNI_OK;

@@ -291,6 +291,10 @@ void omni_halo_launch(const void* args, int bn, int th, bool up2, int iw, bool x
 // omni_conv_pm.hip: conv_pm_sh_kernel<bn, x1>, the position-major form of the 128 x bn ping-pong tile kernel (3x3, stride 1, pad 1, H = W in {4, 8}; bn 128 | 64)
 void omni_conv_pm_launch(const void* args, int bn, bool x1, hipStream_t s);
 int omni_sh_overflow_pm(unsigned* out, int reset);
+// omni_conv_halo2.hip: halo2_sh_kernel<iw, x1>, the 64-channel halo convolution on 256-pixel tiles with 64 x 64 wave tiles (3x3, stride 1, pad 1, no split-K, Cout % 64 == 0;
+// iw 0: W % 32 == 0 and H % 8 == 0 | iw 16: H == W == 16 and rows % 256 == 0); aborts on any other shape
+void omni_halo2_launch(const void* args, int iw, bool x1, hipStream_t s);
+int omni_sh_overflow_halo2(unsigned* out, int reset);
 // the sticky range flag of omni_sh.h, one copy per translation unit whose kernels write SH: omni_sh_overflow (omni_conv_sh.hip) reads them all
 int omni_sh_overflow_halo(unsigned* out, int reset);
 int omni_sh_overflow_up2(unsigned* out, int reset);

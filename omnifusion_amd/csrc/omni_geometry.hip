@@ -73,6 +73,7 @@ const OptName kOpts[] = {
     {"geom_cache_max", "OMNI_GEOM_CACHE_MAX", &OmniOptions::geom_cache_max, 16},
     {"chamfer_split", "OMNI_CHAMFER_SPLIT", &OmniOptions::chamfer_split, 1},
     {"augment_lut", "OMNI_AUGMENT_LUT", &OmniOptions::augment_lut, 1},
+    {"conv_halo2", "OMNI_CONV_HALO2", &OmniOptions::conv_halo2, 1},
     {"conv_wgrad_rows", "OMNI_CONV_WGRAD_ROWS", &OmniOptions::conv_wgrad_rows, 0},
 };
 }  // namespace

@@ -75,6 +75,7 @@ struct OmniOptions {
     int geom_cache_max;   // OMNI_GEOM_CACHE_MAX geometry handles kept per process (LRU), default 16
     int chamfer_split;    // OMNI_CHAMFER_SPLIT  1 (default): the nearest-neighbour search cuts the targets into chunks over gridDim.y where the queries alone give fewer than 2048 blocks | 0: never (same bits)
     int augment_lut;      // OMNI_AUGMENT_LUT    1 (default): gamma of the uint8 augmentation kernels through a 256-entry table built per block in LDS | 0: powf per value (same bits)
+    int conv_halo2;       // OMNI_CONV_HALO2     3x3 stride-1 convolutions with 64-channel halo blocks on halo2_sh_kernel (omni_conv_halo2.hip: 256-pixel tiles, 64 x 64 wave tiles; same bits): 1 (default) where the launch has at least 256 such blocks (three forwards in flight: +1.5 %; profiles/EXPERIMENTS.md, r21a) | 0 never | 2 wherever the shape allows | n > 2: as 1 with n blocks
     int conv_wgrad_rows;  // OMNI_CONV_WGRAD_ROWS output pixels per chunk of the convolution's weight gradient (omni_conv_bwd.hip): 0 (default) the library's plan | n >= 32, rounded up to a multiple of 32 — changes the summation order of dW, nothing else
 };
 OmniOptions& omni_options();

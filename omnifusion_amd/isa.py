@@ -32,7 +32,7 @@ COUNTED = ("e2p_box_kernel", "p2e_lds_kernel", "p2e_walk_kernel", "e2p_ref_kerne
 # kernels that hold >= 1 % of the bench's GPU time (profiles/r04e_bench_kernel_stats.txt): a spill there is a performance bug —
 # scratch 0 is required of every instantiation (conv_sh_kernel<128,128,4,2,3,4> carried 236 B of it)
 HOT = ("conv_sh_kernel", "conv3x3_halo_sh_kernel", "conv3x3_up2_g1_kernel", "stem_f16x3_pc_kernel", "heads_kernel", "maxpool_kernel",
-       "layernorm512_kernel", "attention_kernel", "upsample_sh8_kernel")
+       "layernorm512_kernel", "attention_kernel", "upsample_sh8_kernel", "halo2_sh_kernel")
 # the translation units WITHOUT device code (host-only): every other object must yield a code object, or the check fails
 HOST_ONLY = ("omni_png.o", "omni_geometry.o")
 
