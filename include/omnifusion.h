@@ -189,6 +189,18 @@ int omni_conv2d_sh_f16x3_ws(const void* src1, const void* src2, const void* wt16
                             const void* res, void* dst, int fmt, int M, int H, int W, int C1, int C2, int Cout,
                             int KH, int KW, int stride, int pad, int act, int splitk, float* ws, size_t ws_bytes,
                             omni_stream_t stream);
+/* Which kernel omni_conv2d_sh_f16x3_ws (has_post != 0: omni_conv2d_sh_f16x3_post_ws) would launch for these arguments under the options set at
+ * the time of the call, without launching anything: host code only, no device needed.  Same argument checks and the same status codes as the
+ * convolution itself (the pointer checks apart).  Writes 14 integers to out (n_out >= 14), in this order:
+ *   family     0 conv_sh_kernel (im2col tiles) | 1 conv_pm_sh_kernel (position-major tiles) | 2 conv3x3_halo_sh_kernel | 3 halo2_sh_kernel
+ *   bm, bn, wm, wn, nst, nl, pp    the tile kernel's template arguments: block tile, matrix waves, stages, loader waves, ping-pong
+ *                                  (families 1 and 2: bn only, the output channels per block)
+ *   th, iw     family 2: rows per block, image width of the whole-image forms or 0; family 3: iw
+ *   grid_x, grid_y, threads        the launch
+ *   splitk     the split-K factor in effect (the caller's, at most KH*KW*(C1+C2)/32, at least 1)
+ * A template argument the family does not have is 0.  The arithmetic mode (fmt bit 3) does not enter the choice. */
+int omni_conv2d_sh_plan(int fmt, int M, int H, int W, int C1, int C2, int Cout, int KH, int KW, int stride, int pad, int splitk, int has_post,
+                        int* out, int n_out);
 /* The nn.Linear layers of ONE panorama's transformer (model/blocks.py:19-21,43-46 at 18 tokens): out[rows, N] =
  * act(x . W^T + bias + res) for rows <= 32.  x SH [rows, K], res fp32 [rows, N] or null, fmt bit 0: dst is SH
  * (else fp32).  K in {512, 2048}, N % 32 == 0.  Operands go straight into registers, K is split over the waves of a block and

@@ -4,7 +4,6 @@
 // Why the stem is HERE: it and the 32-channel halo forms are the two users of epilogue_tile_lds<1, true, X1>, and only the halo kernel leaves that helper's
 // last argument at its default.  Alone in a unit every call site passes the same constant, the compiler folds it into the helper BEFORE inlining and the ten
 // 32-channel halo kernels come out one or two instructions shorter than the pinned code (tools/split_isa_diff.py).  Same arithmetic either way; kept bit-identical.
-#include <stdio.h>
 #include <string.h>
 #include "omni_conv_sh_common.h"
 
@@ -582,7 +581,7 @@ __global__ __launch_bounds__(768) void stem_f16x3_pc_kernel(const float* __restr
 
 OMNI_SH_OVERFLOW_ACCESSOR(omni_sh_overflow_halo)
 
-void omni_halo_launch(const void* args, int bn, int th, bool up2, int iw, bool x1, unsigned grid, hipStream_t s)
+int omni_halo_launch(const void* args, int bn, int th, bool up2, int iw, bool x1, unsigned grid, hipStream_t s)
 {
     ShConvArgs a;
     memcpy(&a, args, sizeof(a));
@@ -590,13 +589,13 @@ void omni_halo_launch(const void* args, int bn, int th, bool up2, int iw, bool x
     if (bn == BN && th == TH && up2 == UP2 && iw == IW) { \
         if (x1) hipLaunchKernelGGL((conv3x3_halo_sh_kernel<BN, TH, UP2, IW, true>), dim3(grid), dim3(64 * TH), 0, s, a); \
         else    hipLaunchKernelGGL((conv3x3_halo_sh_kernel<BN, TH, UP2, IW, false>), dim3(grid), dim3(64 * TH), 0, s, a); \
-        return; }
+        return OMNI_OK; }
     OMNI_HALO(32, 4, false, 16) OMNI_HALO(32, 4, false, 8) OMNI_HALO(64, 4, false, 16) OMNI_HALO(64, 4, false, 8)     // small square images
     OMNI_HALO(64, 8, false, 0) OMNI_HALO(32, 8, false, 0) OMNI_HALO(64, 4, false, 0) OMNI_HALO(32, 4, false, 0)       // wide images
     OMNI_HALO(64, 4, true, 0) OMNI_HALO(32, 4, true, 0)                                                               // the up-sampling halo
 #undef OMNI_HALO
-    fprintf(stderr, "omni_halo_launch: no conv3x3_halo_sh_kernel<%d, %d, %d, %d>\n", bn, th, (int)up2, iw);        // a programming error, not a user error
-    abort();
+    OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_halo_launch: no conv3x3_halo_sh_kernel<" + std::to_string(bn) + ", " + std::to_string(th) + ", " + std::to_string((int)up2) +
+                                    ", " + std::to_string(iw) + ">");        // a programming error, not a user error
 }
 
 // conv1 7x7 s2 p3 (3 -> 64) + bn1 + ReLU on the fp16 matrix cores.  src planar [M,3,P,P]; wt16: the folded filter bank as

@@ -14,7 +14,6 @@
 //     ring = 75 KiB, two blocks per CU as the parent (its 2 x 24-KiB kernel-row double buffer does not fit beside the larger halo).
 // Same bits as the parent: every accumulator takes its products in the parent's order (group, ky, kx, chunk; acc: Wh.Ah, acc1: Wl.Ah then Wh.Al) and the
 // epilogues are the shared helpers'.  Both arithmetic modes (X1) and the post-activation addend are supported, so no launch of these shapes falls back.
-#include <stdio.h>
 #include <string.h>
 #include "omni_conv_sh_common.h"
 
@@ -214,19 +213,15 @@ __global__ __launch_bounds__(256, 2) void halo2_sh_kernel(ShConvArgs a)
 
 OMNI_SH_OVERFLOW_ACCESSOR(omni_sh_overflow_halo2)         // this translation unit's copy of the sticky range flag
 
-void omni_halo2_launch(const void* args, int iw, bool x1, hipStream_t s)
+int omni_halo2_launch(const void* args, int iw, bool x1, unsigned grid, hipStream_t s)
 {
     ShConvArgs a;
     memcpy(&a, args, sizeof(a));
-    const bool shape = a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.splitk <= 1 && a.Cout % 64 == 0 && a.rows % 256 == 0 &&
-                       (iw == 16 ? (a.H == 16 && a.W == 16) : (iw == 0 && a.W % HT_W == 0 && a.H % 8 == 0));
-    if (!shape) {                                                 // a programming error, not a user error
-        fprintf(stderr, "omni_halo2_launch: no halo2_sh_kernel<%d> for %d x %d x %d, %d -> %d channels\n", iw, a.M, a.H, a.W, a.C1 + a.C2, a.Cout);
-        abort();
-    }
-    const dim3 grid((unsigned)(a.rows / 256) * (unsigned)(a.Cout / 64)), block(256);
-    if (iw == 16 && !x1) hipLaunchKernelGGL((halo2_sh_kernel<16, false>), grid, block, 0, s, a);
-    else if (iw == 16)   hipLaunchKernelGGL((halo2_sh_kernel<16, true>), grid, block, 0, s, a);
-    else if (!x1)        hipLaunchKernelGGL((halo2_sh_kernel<0, false>), grid, block, 0, s, a);
-    else                 hipLaunchKernelGGL((halo2_sh_kernel<0, true>), grid, block, 0, s, a);
+    const dim3 block(256);
+    if (iw == 16 && !x1)     hipLaunchKernelGGL((halo2_sh_kernel<16, false>), dim3(grid), block, 0, s, a);
+    else if (iw == 16)       hipLaunchKernelGGL((halo2_sh_kernel<16, true>), dim3(grid), block, 0, s, a);
+    else if (iw == 0 && !x1) hipLaunchKernelGGL((halo2_sh_kernel<0, false>), dim3(grid), block, 0, s, a);
+    else if (iw == 0)        hipLaunchKernelGGL((halo2_sh_kernel<0, true>), dim3(grid), block, 0, s, a);
+    else OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_halo2_launch: no halo2_sh_kernel<" + std::to_string(iw) + ">");      // a programming error, not a user error
+    return OMNI_OK;
 }

@@ -14,7 +14,6 @@
 // the eight matrix waves, the XCD remap and wt_major, the epilogues' arithmetic — is conv_sh_kernel<128, BN, 4, 2, 3, 4, PP>'s.
 // (Not here: a matrix wave skipping the taps that are dead for its own 32 rows only.  Built and measured — a wave-uniform branch per phase — it was 0.7 %
 //  SLOWER with three forwards in flight than skipping per tile alone: profiles/EXPERIMENTS.md, r20a.)
-#include <stdio.h>
 #include <string.h>
 #include "omni_conv_sh_common.h"
 
@@ -397,14 +396,15 @@ __global__ __launch_bounds__(768) void conv_pm_sh_kernel(ShConvArgs a)
 
 OMNI_SH_OVERFLOW_ACCESSOR(omni_sh_overflow_pm)            // this translation unit's copy of the sticky range flag
 
-void omni_conv_pm_launch(const void* args, int bn, bool x1, hipStream_t s)
+int omni_conv_pm_launch(const void* args, int bn, bool x1, unsigned grid_x, unsigned grid_y, hipStream_t s)
 {
     ShConvArgs a;
     memcpy(&a, args, sizeof(a));
-    const dim3 grid(((a.rows + 127) / 128) * (a.Cout / bn), a.splitk > 1 ? a.splitk : 1), block(768);
+    const dim3 grid(grid_x, grid_y), block(768);
     if (bn == 128 && !x1)     hipLaunchKernelGGL((conv_pm_sh_kernel<128, false>), grid, block, 0, s, a);
     else if (bn == 128)       hipLaunchKernelGGL((conv_pm_sh_kernel<128, true>), grid, block, 0, s, a);
     else if (bn == 64 && !x1) hipLaunchKernelGGL((conv_pm_sh_kernel<64, false>), grid, block, 0, s, a);
     else if (bn == 64)        hipLaunchKernelGGL((conv_pm_sh_kernel<64, true>), grid, block, 0, s, a);
-    else { fprintf(stderr, "omni_conv_pm_launch: no conv_pm_sh_kernel<%d>\n", bn); abort(); }      // a programming error, not a user error
+    else OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_conv_pm_launch: no conv_pm_sh_kernel<" + std::to_string(bn) + ">");      // a programming error, not a user error
+    return OMNI_OK;
 }

@@ -560,19 +560,6 @@ __global__ __launch_bounds__(256) void sh_to_f32_kernel(const void* __restrict__
     *reinterpret_cast<f4v*>(dst + i * 4) = sh_join4(*reinterpret_cast<const h4v*>(sp), *reinterpret_cast<const h4v*>(sp + 64));
 }
 
-template <bool X1, int BM, int BN, int WM, int WN, int NST = 3, int NL = 0>
-void launch_sh(ShConvArgs a, hipStream_t s)
-{
-    const int tiles = ((a.rows + BM - 1) / BM) * (a.Cout / BN);
-    if constexpr (NL > 0 && WM * WN == 8) {
-        if (omni_options().conv_pingpong) {                       // the SIMD's two matrix waves in anti-phase (same bits)
-            hipLaunchKernelGGL((conv_sh_kernel<BM, BN, WM, WN, NST, NL, true, false, X1>), dim3(tiles, a.splitk > 1 ? a.splitk : 1), dim3(64 * (WM * WN + NL)), 0, s, a);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((conv_sh_kernel<BM, BN, WM, WN, NST, NL, false, false, X1>), dim3(tiles, a.splitk > 1 ? a.splitk : 1), dim3(64 * (WM * WN + NL)), 0, s, a);
-}
-
 }  // namespace
 
 // out[M,Ho,Wo,Cout] = act(conv(src1 ++ src2, wt16) + bias + res) with SH activations (see the file header).
@@ -623,53 +610,78 @@ extern "C" int omni_gemm_sh_f16x3_ln512_ws(const void* x, const void* wt16, cons
 }
 
 constexpr int OMNI_HALO2_MIN_BLOCKS = 256;               // option conv_halo2 = 1: the least number of halo2_sh_kernel blocks a launch must have (a block per CU)
-// The kernel choice of conv2d_sh_impl (everything but the checks and the split-K second pass), once per arithmetic mode: X1 (fmt bit 3) picks the
-// f16x1 instantiation of whichever form the shape and the tuning options select — the same forms, the same block counts.
-template <bool X1>
-static void conv_sh_select(const ShConvArgs& a, int fmt, hipStream_t s)
+
+// Which kernel runs a convolution, with which template arguments, on what grid: what conv_sh_plan decides and conv_sh_launch launches (and what
+// omni_conv2d_sh_plan reports, field for field in this order, followed by the split-K factor).  A family's unused arguments are 0.
+// family: conv_sh_kernel | conv_pm_sh_kernel | conv3x3_halo_sh_kernel | halo2_sh_kernel; bm .. pp: the tile kernel's (position-major, halo: bn); th, iw: halo (halo2: iw)
+enum { CONV_SH_TILE = 0, CONV_SH_PM = 1, CONV_SH_HALO = 2, CONV_SH_HALO2 = 3 };
+struct ConvShPlan { int family, bm, bn, wm, wn, nst, nl, pp, th, iw; unsigned grid_x, grid_y; int threads; };
+
+// The argument checks of omni_conv2d_sh_f16x3_ws that need no pointer.  Fills the shape of `a`: M .. pad as given, Ho, Wo, rows and splitk (>= 1: the caller's
+// factor, at most the K-steps) — all that conv_sh_plan reads of it.
+static int conv_sh_ksteps(const ShConvArgs& a) { return a.KH * a.KW * ((a.C1 + a.C2) / 32); }
+static int conv_sh_shape(ShConvArgs& a, int M, int H, int W, int C1, int C2, int Cout, int KH, int KW, int stride, int pad, int splitk, bool has_post)
 {
-    const int KH = a.KH, KW = a.KW, stride = a.stride, pad = a.pad, H = a.H, W = a.W, M = a.M, Cout = a.Cout;
-    const int ksteps = KH * KW * ((a.C1 + a.C2) / 32);
-    const long long rows = a.rows;
+    if (C1 <= 0 || C1 % 32 || C2 < 0 || C2 % 32 || Cout <= 0 || Cout % 32)
+        OMNI_FAIL(OMNI_ERR_INVALID, "omni_conv2d_sh: channels must be multiples of 32");
+    if (M <= 0 || H <= 0 || W <= 0 || KH <= 0 || KW <= 0 || KH > 3 || KW > 3 || stride <= 0 || pad < 0)
+        OMNI_FAIL(OMNI_ERR_INVALID, "omni_conv2d_sh: bad shape (kernels up to 3x3)");
+    a.M = M; a.H = H; a.W = W; a.C1 = C1; a.C2 = C2; a.Cout = Cout; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad;
+    a.Ho = (H + 2 * pad - KH) / stride + 1; a.Wo = (W + 2 * pad - KW) / stride + 1;
+    const long long rows = (long long)M * a.Ho * a.Wo;
+    if (rows <= 0 || rows >= (1ll << 31) || (long long)M * H * W >= (1ll << 31))
+        OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_conv2d_sh: too many pixels for 32-bit row indices");
+    a.rows = (int)rows;
+    if ((long long)M * H * W * (C1 > C2 ? C1 : C2) * 4 >= (1ll << 31) || (long long)Cout * conv_sh_ksteps(a) * 128 >= (1ll << 31))
+        OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_conv2d_sh: an operand of 2 GiB or more (32-bit buffer offsets)");
+    a.splitk = std::max(1, std::min(splitk, conv_sh_ksteps(a)));
+    if (has_post && a.splitk > 1) OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_conv2d_sh: no post-activation addend with split-K");
+    return OMNI_OK;
+}
+
+// blocks of a launch of BM x BN tiles: every block-count rule of conv_sh_plan, and the grid of the tile kernels
+static long long conv_sh_tiles(const ShConvArgs& p, int bm, int bn) { return (((long long)p.rows + bm - 1) / bm) * (p.Cout / bn); }
+static long long conv_sh_blocks(const ShConvArgs& p, int bm, int bn) { return conv_sh_tiles(p, bm, bn) * p.splitk; }
+
+static ConvShPlan tile_plan(const ShConvArgs& p, const OmniOptions& o, int bm, int bn, int wm, int wn, int nst = 3, int nl = 0)
+{
+    const int pp = nl > 0 && wm * wn == 8 && o.conv_pingpong;    // the SIMD's two matrix waves in anti-phase (same bits)
+    return {CONV_SH_TILE, bm, bn, wm, wn, nst, nl, pp, 0, 0, (unsigned)conv_sh_tiles(p, bm, bn), (unsigned)p.splitk, 64 * (wm * wn + nl)};
+}
+static ConvShPlan pm_plan(const ShConvArgs& p, int bn) { return {CONV_SH_PM, 0, bn, 0, 0, 0, 0, 0, 0, 0, (unsigned)conv_sh_tiles(p, 128, bn), (unsigned)p.splitk, 768}; }
+static ConvShPlan halo_plan(int bn, int th, int iw, unsigned grid) { return {CONV_SH_HALO, 0, bn, 0, 0, 0, 0, 0, th, iw, grid, 1, 64 * th}; }
+
+// The kernel choice of omni_conv2d_sh_f16x3_ws: a function of the shape, the caller's fmt bits, whether there is a post-activation addend, and the tuning
+// options — nothing else, no HIP call.  The arithmetic mode (fmt bit 3) plays no part: every form has both instantiations (conv_sh_launch).
+static ConvShPlan conv_sh_plan(const ShConvArgs& p, int fmt, bool has_post, const OmniOptions& o)
+{
+    const int H = p.H, W = p.W, M = p.M, Cout = p.Cout, rows = p.rows;
+    const bool conv3x3 = p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad == 1;
     // 64 output channels per block on 256-pixel tiles with 64 x 64 wave tiles (omni_conv_halo2.hip): the two 64-channel halo forms below with 0.59x the
     // operand bytes into LDS and 0.56x the fragment reads per matrix instruction — the same bits, so the choice may depend on anything.  Option conv_halo2:
     // 0 never | 1 where the launch has at least OMNI_HALO2_MIN_BLOCKS blocks of the new size | 2 wherever the shape allows (tests) | n > 2: as 1 with n blocks
     // (tuning).  Never for the latency form (fmt bit 2), nor where an option asks for the tile kernels or for 32-channel blocks.
-    if (const int h2 = omni_options().conv_halo2; h2 > 0 && a.splitk <= 1 && KH == 3 && KW == 3 && stride == 1 && pad == 1 && Cout % 64 == 0 && rows % 256 == 0 &&
-        !(fmt & 4) && !omni_options().conv_nohalo && omni_options().conv_halo_bn != 32) {
-        const int iw = (H == 16 && W == 16 && omni_options().conv_img > 0) ? 16 : (W % HT_W == 0 && H % 8 == 0) ? 0 : -1;
-        const long long blocks = (rows / 256) * (Cout / 64);
-        if (iw >= 0 && (h2 == 2 || blocks >= (h2 == 1 ? OMNI_HALO2_MIN_BLOCKS : h2))) { omni_halo2_launch(&a, iw, X1, s); return; }
+    if (const int h2 = o.conv_halo2; h2 > 0 && p.splitk <= 1 && conv3x3 && Cout % 64 == 0 && rows % 256 == 0 && !(fmt & 4) && !o.conv_nohalo && o.conv_halo_bn != 32) {
+        const int iw = (H == 16 && W == 16 && o.conv_img > 0) ? 16 : (W % HT_W == 0 && H % 8 == 0) ? 0 : -1;
+        const long long blocks = (long long)(rows / 256) * (Cout / 64);
+        if (iw >= 0 && (h2 == 2 || blocks >= (h2 == 1 ? OMNI_HALO2_MIN_BLOCKS : h2))) return {CONV_SH_HALO2, 0, 0, 0, 0, 0, 0, 0, 0, iw, (unsigned)blocks, 1, 256};
     }
     // small square images: the halo kernel over bands of whole image rows (IW > 0) — 16 x 16 (layer2, de_conv1_x: 61.6 -> 49.3 us per layer2
     // convolution at 8 panoramas) by default, 8 x 8 as well with conv_img = 2 (layer3: 52.7 -> 50.9)
     // (the choice must not depend on the number of images: a panorama's bits are the same in every batch size; a caller that runs ONE panorama,
     //  where the launch would be a quarter block per CU, asks for the tile kernel with fmt bit 2)
-    if (a.splitk <= 1 && KH == 3 && KW == 3 && stride == 1 && pad == 1 && H == W && (W == 16 || (W == 8 && omni_options().conv_img >= 2)) && rows % 128 == 0 &&
-        Cout % 64 == 0 && !(fmt & 4) && omni_options().conv_img > 0 && !omni_options().conv_nohalo) {
-        const int grid = (int)(rows / 128) * (Cout / 64);
-        if (omni_options().conv_halo_bn == 32) {
-            if (W == 16) omni_halo_launch(&a, 32, 4, false, 16, X1, 2 * grid, s);
-            else         omni_halo_launch(&a, 32, 4, false, 8, X1, 2 * grid, s);
-        }
-        else if (W == 16) omni_halo_launch(&a, 64, 4, false, 16, X1, grid, s);
-        else         omni_halo_launch(&a, 64, 4, false, 8, X1, grid, s);
-        return;
+    if (p.splitk <= 1 && conv3x3 && H == W && (W == 16 || (W == 8 && o.conv_img >= 2)) && rows % 128 == 0 &&
+        Cout % 64 == 0 && !(fmt & 4) && o.conv_img > 0 && !o.conv_nohalo) {
+        const int bn = o.conv_halo_bn == 32 ? 32 : 64;
+        return halo_plan(bn, 4, W, (unsigned)((int)(rows / 128) * (Cout / bn)));
     }
-    if (a.splitk <= 1 && KH == 3 && KW == 3 && stride == 1 && pad == 1 && W % HT_W == 0 && H % 4 == 0 && !omni_options().conv_nohalo) {
-        const int th = (H % 8 == 0 && omni_options().conv_halo_th == 8) ? 8 : 4;
-        const int grid = M * (H / th) * (W / HT_W);
-        if (th == 8) {
-            if (Cout % 64 == 0 && omni_options().conv_halo_bn != 32) omni_halo_launch(&a, 64, 8, false, 0, X1, grid * (Cout / 64), s);
-            else                omni_halo_launch(&a, 32, 8, false, 0, X1, grid * (Cout / 32), s);
-        } else {
-            // (fmt bit 2, ONE panorama: the launch is a fraction of a block per CU and costs the length of a block's life — 32-channel blocks are twice as many and
-            //  half as long; option conv_halo_bn_lat)
-            const bool bn32 = omni_options().conv_halo_bn == 32 || ((fmt & 4) && omni_options().conv_halo_bn_lat == 32);
-            if (Cout % 64 == 0 && !bn32) omni_halo_launch(&a, 64, 4, false, 0, X1, grid * (Cout / 64), s);
-            else                omni_halo_launch(&a, 32, 4, false, 0, X1, grid * (Cout / 32), s);
-        }
-        return;
+    if (p.splitk <= 1 && conv3x3 && W % HT_W == 0 && H % 4 == 0 && !o.conv_nohalo) {
+        const int th = (H % 8 == 0 && o.conv_halo_th == 8) ? 8 : 4;
+        // (fmt bit 2, ONE panorama: the launch is a fraction of a block per CU and costs the length of a block's life — 32-channel blocks are twice as many and
+        //  half as long; option conv_halo_bn_lat, for the 4-row blocks)
+        const bool bn32 = o.conv_halo_bn == 32 || (th == 4 && (fmt & 4) && o.conv_halo_bn_lat == 32);
+        const int bn = (Cout % 64 == 0 && !bn32) ? 64 : 32;
+        return halo_plan(bn, th, 0, (unsigned)(M * (H / th) * (W / HT_W) * (Cout / bn)));
     }
     // tile: results do not depend on it (every output element is the same k-ordered chain), so it is a pure tuning choice
     // -1 auto (= 8): the largest 8-wave tile the layer allows (256x128, 128x128, else 128x64: 3/8, 1/2, 3/4 of the L2 -> LDS bytes per MFMA
@@ -677,44 +689,59 @@ static void conv_sh_select(const ShConvArgs& a, int fmt, hipStream_t s)
     // (tools/pipe_ab.py, tools/plain_ab.py): +5.1 % panoramas/s with three forwards in flight (+1.2 % of it from 256x128), +1.7 % for plain
     // calls at 8 panoramas, -1 % at 4, 0 at 1.
     // 0: 64x64 everywhere; 1: 128x64 (4 waves); 2: 128x128 (4 waves); 3 / 4: the 8-wave forms everywhere; 5..7: auto without 256x128, with 64 / 128 / 256 blocks
-    int tile = omni_options().conv_sh_tile;
-    if (tile < 0) tile = 8;
+    const int tile = o.conv_sh_tile < 0 ? 8 : o.conv_sh_tile;
+    const bool c128 = Cout % 128 == 0;
+    const bool fill128 = c128 && conv_sh_blocks(p, 128, 128) >= 128, fill64 = conv_sh_blocks(p, 128, 64) >= 128;   // 128 blocks of the 128-row tiles remain
+    const bool big256 = tile == 8 && c128 && conv_sh_blocks(p, 256, 128) >= std::max(1, o.conv_big_blocks);
     // 3x3 on 8 x 8 and 4 x 4 images: the position-major form of the two ping-pong tile kernels (omni_conv_pm.hip) skips the K-steps of the taps that are
     // zero padding for every row of a tile — the same bits, so the choice may depend on anything.  Option conv_pm: 1 (default) where the launch would take
     // one of those two kernels | 0 never | 2 wherever the shape allows, whatever the row count (tests) | 3 / 4: as 1 for the 8 x 8 / the 4 x 4 images only
-    const int pm = omni_options().conv_pm;
-    const bool pm_shape = pm > 0 && KH == 3 && KW == 3 && stride == 1 && pad == 1 && H == W && (W == 8 || W == 4) && Cout % 64 == 0 && !a.post &&
-                          omni_options().conv_pingpong && !(pm == 3 && W != 8) && !(pm == 4 && W != 4);
-    if (pm_shape && pm == 2) { omni_conv_pm_launch(&a, Cout % 128 == 0 ? 128 : 64, X1, s); return; }
-    const bool big256 = tile == 8 && Cout % 128 == 0 && ((rows + 255) / 256) * (long long)(Cout / 128) * a.splitk >= std::max(1, omni_options().conv_big_blocks);
-    if (pm_shape && tile == 8 && !big256) {
-        if (Cout % 128 == 0 && ((rows + 127) / 128) * (long long)(Cout / 128) * a.splitk >= 128) { omni_conv_pm_launch(&a, 128, X1, s); return; }
-        if (((rows + 127) / 128) * (long long)(Cout / 64) * a.splitk >= 128) { omni_conv_pm_launch(&a, 64, X1, s); return; }
-    }
-    if (Cout % 64 != 0) launch_sh<X1, 128, 32, 4, 1>(a, s);
-    else if (tile == 2 && Cout % 128 == 0) launch_sh<X1, 128, 128, 2, 2>(a, s);
-    else if (tile == 1) launch_sh<X1, 128, 64, 2, 2>(a, s);
-    else if (tile == 3) launch_sh<X1, 128, 64, 4, 2>(a, s);            // 8 waves
-    else if (tile == 4 && Cout % 128 == 0) launch_sh<X1, 128, 128, 4, 2>(a, s);
-    else if (tile == 8 && Cout % 128 == 0 && ((rows + 255) / 256) * (long long)(Cout / 128) * a.splitk >= std::max(1, omni_options().conv_big_blocks)) launch_sh<X1, 256, 128, 4, 2>(a, s);   // each wave a 64x64 tile: 0.67 KB of LDS reads per MFMA instead of 1
+    const int pm = o.conv_pm;
+    const bool pm_shape = pm > 0 && conv3x3 && H == W && (W == 8 || W == 4) && Cout % 64 == 0 && !has_post &&
+                          o.conv_pingpong && !(pm == 3 && W != 8) && !(pm == 4 && W != 4);
+    if (pm_shape && pm == 2) return pm_plan(p, c128 ? 128 : 64);
+    if (pm_shape && tile == 8 && !big256 && (fill128 || fill64)) return pm_plan(p, fill128 ? 128 : 64);
+    if (Cout % 64 != 0) return tile_plan(p, o, 128, 32, 4, 1);
+    if (tile == 2 && c128) return tile_plan(p, o, 128, 128, 2, 2);
+    if (tile == 1) return tile_plan(p, o, 128, 64, 2, 2);
+    if (tile == 3) return tile_plan(p, o, 128, 64, 4, 2);            // 8 waves
+    if (tile == 4 && c128) return tile_plan(p, o, 128, 128, 4, 2);
+    if (big256) return tile_plan(p, o, 256, 128, 4, 2);              // each wave a 64x64 tile: 0.67 KB of LDS reads per MFMA instead of 1
     // (128x128 and 128x64 with four LOADER waves beside the eight matrix waves: layer3 51.3 -> 45.8 us, de_conv0_0 90 -> 79, layer4 43.3 -> 41.3, same bits;
     //  tile = 9: without them.  256x128 has no registers to spare for a third wave per SIMD.)
-    else if (tile == 8 && Cout % 128 == 0 && ((rows + 127) / 128) * (long long)(Cout / 128) * a.splitk >= 128) launch_sh<X1, 128, 128, 4, 2, 3, 4>(a, s);
-    else if (tile == 8 && ((rows + 127) / 128) * (long long)(Cout / 64) * a.splitk >= 128) launch_sh<X1, 128, 64, 4, 2, 3, 4>(a, s);
-    else if (tile == 9 && Cout % 128 == 0 && ((rows + 255) / 256) * (long long)(Cout / 128) * a.splitk >= 128) launch_sh<X1, 256, 128, 4, 2>(a, s);
-    else if (tile == 9 && Cout % 128 == 0 && ((rows + 127) / 128) * (long long)(Cout / 128) * a.splitk >= 128) launch_sh<X1, 128, 128, 4, 2>(a, s);
-    else if (tile == 9 && ((rows + 127) / 128) * (long long)(Cout / 64) * a.splitk >= 128) launch_sh<X1, 128, 64, 4, 2>(a, s);
-    else if (tile >= 5 && tile <= 7 && Cout % 128 == 0 && ((rows + 127) / 128) * (long long)(Cout / 128) * a.splitk >= (32ll << (tile - 4))) launch_sh<X1, 128, 128, 4, 2>(a, s);
-    else if (tile >= 5 && tile <= 7 && ((rows + 127) / 128) * (long long)(Cout / 64) * a.splitk >= (32ll << (tile - 4))) launch_sh<X1, 128, 64, 4, 2>(a, s);
+    if (tile == 8 && fill128) return tile_plan(p, o, 128, 128, 4, 2, 3, 4);
+    if (tile == 8 && fill64) return tile_plan(p, o, 128, 64, 4, 2, 3, 4);
+    if (tile == 9 && c128 && conv_sh_blocks(p, 256, 128) >= 128) return tile_plan(p, o, 256, 128, 4, 2);
+    if (tile == 9 && fill128) return tile_plan(p, o, 128, 128, 4, 2);
+    if (tile == 9 && fill64) return tile_plan(p, o, 128, 64, 4, 2);
+    if (tile >= 5 && tile <= 7 && c128 && conv_sh_blocks(p, 128, 128) >= (32ll << (tile - 4))) return tile_plan(p, o, 128, 128, 4, 2);
+    if (tile >= 5 && tile <= 7 && conv_sh_blocks(p, 128, 64) >= (32ll << (tile - 4))) return tile_plan(p, o, 128, 64, 4, 2);
     // one round of at most one block per CU (the transformer GEMMs; every deep layer at batch 1): the K loop is pure latency,
     // keep 5 stages in flight instead of 2 (96 KiB of LDS, which a single resident block can afford)
-    else if (((rows + 63) / 64) * (long long)(Cout / 64) * a.splitk <= 256 && ksteps >= 8 && !omni_options().conv_nodeep) {
-        // (conv_deep_loaders = 1: four loader waves beside the four matrix waves — at one block per CU a K-step is the four DMA pieces a matrix wave issues,
-        //  ~400 cycles for its 192 of matrix work)
-        if (omni_options().conv_deep_loaders) launch_sh<X1, 64, 64, 2, 2, 6, 4>(a, s);
-        else launch_sh<X1, 64, 64, 2, 2, 6>(a, s);
-    }
-    else launch_sh<X1, 64, 64, 2, 2>(a, s);
+    // (conv_deep_loaders = 1: four loader waves beside the four matrix waves — at one block per CU a K-step is the four DMA pieces a matrix wave issues,
+    //  ~400 cycles for its 192 of matrix work)
+    if (conv_sh_blocks(p, 64, 64) <= 256 && conv_sh_ksteps(p) >= 8 && !o.conv_nodeep) return tile_plan(p, o, 64, 64, 2, 2, 6, o.conv_deep_loaders ? 4 : 0);
+    return tile_plan(p, o, 64, 64, 2, 2);
+}
+
+// Launches what a plan says: the one place that instantiates conv_sh_kernel for omni_conv2d_sh_f16x3_ws (the Winograd entry point launches its own form),
+// in both arithmetic modes (x1: fmt bit 3, f16x1); the other families through their units' launchers.
+static int conv_sh_launch(const ConvShPlan& p, const ShConvArgs& a, bool x1, hipStream_t s)
+{
+    if (p.family == CONV_SH_HALO2) return omni_halo2_launch(&a, p.iw, x1, p.grid_x, s);
+    if (p.family == CONV_SH_HALO) return omni_halo_launch(&a, p.bn, p.th, false, p.iw, x1, p.grid_x, s);
+    if (p.family == CONV_SH_PM) return omni_conv_pm_launch(&a, p.bn, x1, p.grid_x, p.grid_y, s);
+#define OMNI_TILE(BM, BN, WM, WN, NST, NL, PP) \
+    if (p.bm == BM && p.bn == BN && p.wm == WM && p.wn == WN && p.nst == NST && p.nl == NL && p.pp == PP) { \
+        if (x1) hipLaunchKernelGGL((conv_sh_kernel<BM, BN, WM, WN, NST, NL, PP, false, true>), dim3(p.grid_x, p.grid_y), dim3(p.threads), 0, s, a); \
+        else    hipLaunchKernelGGL((conv_sh_kernel<BM, BN, WM, WN, NST, NL, PP, false, false>), dim3(p.grid_x, p.grid_y), dim3(p.threads), 0, s, a); \
+        return OMNI_OK; }
+    OMNI_TILE(128, 32, 4, 1, 3, 0, false) OMNI_TILE(128, 128, 2, 2, 3, 0, false) OMNI_TILE(128, 64, 2, 2, 3, 0, false)                                   // four waves
+    OMNI_TILE(64, 64, 2, 2, 6, 4, false) OMNI_TILE(64, 64, 2, 2, 6, 0, false) OMNI_TILE(64, 64, 2, 2, 3, 0, false)                                       // ... 64 x 64, deep and plain
+    OMNI_TILE(128, 64, 4, 2, 3, 0, false) OMNI_TILE(128, 128, 4, 2, 3, 0, false) OMNI_TILE(256, 128, 4, 2, 3, 0, false)                                  // eight
+    OMNI_TILE(128, 128, 4, 2, 3, 4, true) OMNI_TILE(128, 128, 4, 2, 3, 4, false) OMNI_TILE(128, 64, 4, 2, 3, 4, true) OMNI_TILE(128, 64, 4, 2, 3, 4, false)   // eight + four loader waves
+#undef OMNI_TILE
+    OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_conv2d_sh: no conv_sh_kernel<" + std::to_string(p.bm) + ", " + std::to_string(p.bn) + ", ..> of this plan");   // a programming error, not a user error
 }
 
 static int conv2d_sh_impl(const void* src1, const void* src2, const void* wt16, const float* bias,
@@ -722,47 +749,30 @@ static int conv2d_sh_impl(const void* src1, const void* src2, const void* wt16, 
                           int KH, int KW, int stride, int pad, int act, int splitk, float* ws, size_t ws_bytes,
                           const float* post, size_t post_elems, omni_stream_t stream, bool reduce)
 {
-    const int dst_sh = fmt & 1;
-    if (!src1 || !wt16 || !dst) OMNI_FAIL(OMNI_ERR_INVALID, "omni_conv2d_sh: null pointer");
-    if (C1 <= 0 || C1 % 32 || C2 < 0 || C2 % 32 || Cout <= 0 || Cout % 32 || (C2 > 0 && !src2))
-        OMNI_FAIL(OMNI_ERR_INVALID, "omni_conv2d_sh: channels must be multiples of 32");
-    if (M <= 0 || H <= 0 || W <= 0 || KH <= 0 || KW <= 0 || KH > 3 || KW > 3 || stride <= 0 || pad < 0)
-        OMNI_FAIL(OMNI_ERR_INVALID, "omni_conv2d_sh: bad shape (kernels up to 3x3)");
+    if (!src1 || !wt16 || !dst || (C2 > 0 && !src2)) OMNI_FAIL(OMNI_ERR_INVALID, "omni_conv2d_sh: null pointer");
     ShConvArgs a;
-    a.src1 = src1; a.src2 = src2; a.wt = wt16; a.bias = bias; a.res = res; a.dst = dst; a.dst_sh = dst_sh; a.res_f32 = (fmt >> 1) & 1;
+    if (const int rc = conv_sh_shape(a, M, H, W, C1, C2, Cout, KH, KW, stride, pad, splitk, post != nullptr); rc != OMNI_OK) return rc;
+    const long long rows = a.rows;
+    a.src1 = src1; a.src2 = src2; a.wt = wt16; a.bias = bias; a.res = res; a.dst = dst; a.dst_sh = fmt & 1; a.res_f32 = (fmt >> 1) & 1; a.act = act;
     a.dbg = 0; a.noxcd = omni_options().conv_noxcd; a.wt_major = 0; a.epi_lds = omni_options().conv_epi_lds && !(fmt & 4);   // (fmt bit 2, one panorama: the extra barrier and LDS round trip cost more than the wider stores save)
 #ifdef OMNI_DEBUG_BUILD
     a.dbg = omni_debug_bits("OMNI_CONV_DBG");
 #endif
-    a.M = M; a.H = H; a.W = W; a.C1 = C1; a.C2 = C2; a.Cout = Cout;
-    a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.act = act;
-    a.Ho = (H + 2 * pad - KH) / stride + 1; a.Wo = (W + 2 * pad - KW) / stride + 1;
-    const long long rows = (long long)M * a.Ho * a.Wo;
-    if (rows <= 0 || rows >= (1ll << 31) || (long long)M * H * W >= (1ll << 31))
-        OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_conv2d_sh: too many pixels for 32-bit row indices");
-    a.rows = (int)rows;
-    const int ksteps = KH * KW * ((C1 + C2) / 32);
-    if ((long long)M * H * W * (C1 > C2 ? C1 : C2) * 4 >= (1ll << 31) || (long long)Cout * ksteps * 128 >= (1ll << 31))
-        OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_conv2d_sh: an operand of 2 GiB or more (32-bit buffer offsets)");
-    int S = splitk;
-    if (S > ksteps) S = ksteps;
-    if (S > 1 && (!ws || ws_bytes < (size_t)S * rows * Cout * sizeof(float)))
+    if (a.splitk > 1 && (!ws || ws_bytes < (size_t)a.splitk * rows * Cout * sizeof(float)))
         OMNI_FAIL(OMNI_ERR_INVALID, "omni_conv2d_sh: split-K workspace too small");
-    a.splitk = S > 1 ? S : 1; a.ws = ws;
+    a.ws = ws;
     // block order of conv_sh_kernel: weight-stationary per XCD where the weight matrix is larger than the activation tensor(s) (option conv_wt_major:
     // 1 auto | 0 never | 2 always)
     a.wt_major = omni_options().conv_wt_major == 2 || (omni_options().conv_wt_major == 1 &&
-                 (long long)Cout * ksteps * 128 > (long long)M * H * W * (C1 + C2) * 4) ? 1 : 0;
+                 (long long)Cout * conv_sh_ksteps(a) * 128 > (long long)M * H * W * (C1 + C2) * 4) ? 1 : 0;
     a.post = post; a.post_rows = 1; a.wino_th = a.wino_tw = a.wino_pix = 0;
     if (post) {
-        if (Cout <= 0 || post_elems == 0 || post_elems % (size_t)Cout || post_elems / (size_t)Cout > 0x7fffffffull)
+        if (post_elems == 0 || post_elems % (size_t)Cout || post_elems / (size_t)Cout > 0x7fffffffull)
             OMNI_FAIL(OMNI_ERR_INVALID, "omni_conv2d_sh: the post-activation addend must hold whole rows of Cout channels");
-        if (a.splitk > 1) OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_conv2d_sh: no post-activation addend with split-K");
         a.post_rows = (unsigned)(post_elems / (size_t)Cout);
     }
     hipStream_t s = (hipStream_t)stream;
-    if (fmt & 8) conv_sh_select<true>(a, fmt, s);            // f16x1: every form below has its X1 instantiation
-    else         conv_sh_select<false>(a, fmt, s);
+    if (const int rc = conv_sh_launch(conv_sh_plan(a, fmt, post != nullptr, omni_options()), a, (fmt & 8) != 0, s); rc != OMNI_OK) return rc;   // fmt bit 3: f16x1
     OMNI_HIP(hipGetLastError());
     if (a.splitk > 1 && reduce) {
         const size_t n4 = (size_t)rows * Cout / 4;
@@ -770,6 +780,19 @@ static int conv2d_sh_impl(const void* src1, const void* src2, const void* wt16, 
                            n4, Cout, a.splitk, (size_t)rows * Cout, act, a.dst_sh, a.res_f32);
         OMNI_HIP(hipGetLastError());
     }
+    return OMNI_OK;
+}
+
+// The plan omni_conv2d_sh_f16x3_ws (has_post: ..._post_ws) would launch for these arguments under the current options (include/omnifusion.h); host only.
+extern "C" int omni_conv2d_sh_plan(int fmt, int M, int H, int W, int C1, int C2, int Cout, int KH, int KW, int stride, int pad, int splitk, int has_post,
+                                   int* out, int n_out)
+{
+    if (!out || n_out < 14) OMNI_FAIL(OMNI_ERR_INVALID, "omni_conv2d_sh_plan: needs room for 14 integers");
+    ShConvArgs p{};
+    if (const int rc = conv_sh_shape(p, M, H, W, C1, C2, Cout, KH, KW, stride, pad, splitk, has_post != 0); rc != OMNI_OK) return rc;
+    const ConvShPlan q = conv_sh_plan(p, fmt, has_post != 0, omni_options());
+    const int v[14] = {q.family, q.bm, q.bn, q.wm, q.wn, q.nst, q.nl, q.pp, q.th, q.iw, (int)q.grid_x, (int)q.grid_y, q.threads, p.splitk};
+    std::copy(v, v + 14, out);
     return OMNI_OK;
 }
 

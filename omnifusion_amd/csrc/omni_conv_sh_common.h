@@ -285,15 +285,18 @@ constexpr int HT_W = 32, HPW = HT_W + 2;                     // the halo kernels
 }  // namespace
 
 // ---- host functions that cross units
-// omni_conv_halo.hip: conv3x3_halo_sh_kernel<bn, th, up2, iw, x1> on `grid` blocks of 64 * th threads; aborts on a form that is not instantiated.  `args`: the caller's
-// ShConvArgs (the type lives in every unit's anonymous namespace, like the kernels that take it, so it crosses as bytes)
-void omni_halo_launch(const void* args, int bn, int th, bool up2, int iw, bool x1, unsigned grid, hipStream_t s);
-// omni_conv_pm.hip: conv_pm_sh_kernel<bn, x1>, the position-major form of the 128 x bn ping-pong tile kernel (3x3, stride 1, pad 1, H = W in {4, 8}; bn 128 | 64)
-void omni_conv_pm_launch(const void* args, int bn, bool x1, hipStream_t s);
+// The launchers of the kernel families that live in other units.  Which form runs and on what grid is the caller's decision (conv_sh_plan in omni_conv_sh.hip;
+// omni_conv3x3_up2_sh_f16x3 for the up-sampling halo): a launcher launches exactly that, or fails with OMNI_ERR_UNSUPPORTED on a form it does not instantiate.
+// `args`: the caller's ShConvArgs (the type lives in every unit's anonymous namespace, like the kernels that take it, so it crosses as bytes)
+// omni_conv_halo.hip: conv3x3_halo_sh_kernel<bn, th, up2, iw, x1> on `grid` blocks of 64 * th threads
+int omni_halo_launch(const void* args, int bn, int th, bool up2, int iw, bool x1, unsigned grid, hipStream_t s);
+// omni_conv_pm.hip: conv_pm_sh_kernel<bn, x1>, the position-major form of the 128 x bn ping-pong tile kernel (3x3, stride 1, pad 1, H = W in {4, 8}; bn 128 | 64) on
+// grid_x tiles x grid_y K ranges of 768 threads
+int omni_conv_pm_launch(const void* args, int bn, bool x1, unsigned grid_x, unsigned grid_y, hipStream_t s);
 int omni_sh_overflow_pm(unsigned* out, int reset);
 // omni_conv_halo2.hip: halo2_sh_kernel<iw, x1>, the 64-channel halo convolution on 256-pixel tiles with 64 x 64 wave tiles (3x3, stride 1, pad 1, no split-K, Cout % 64 == 0;
-// iw 0: W % 32 == 0 and H % 8 == 0 | iw 16: H == W == 16 and rows % 256 == 0); aborts on any other shape
-void omni_halo2_launch(const void* args, int iw, bool x1, hipStream_t s);
+// iw 0: W % 32 == 0 and H % 8 == 0 | iw 16: H == W == 16 and rows % 256 == 0) on `grid` blocks of 256 threads
+int omni_halo2_launch(const void* args, int iw, bool x1, unsigned grid, hipStream_t s);
 int omni_sh_overflow_halo2(unsigned* out, int reset);
 // the sticky range flag of omni_sh.h, one copy per translation unit whose kernels write SH: omni_sh_overflow (omni_conv_sh.hip) reads them all
 int omni_sh_overflow_halo(unsigned* out, int reset);

@@ -370,8 +370,8 @@ extern "C" int omni_conv3x3_up2_sh_f16x3(const void* src, const void* wt16, cons
     // (the up-sampling halo is COMPUTED per block — ~700 vector instructions per 2 x 2 cell: blocks of 32 output channels would do it twice — 64 per block here whatever conv_halo_bn says:
     //  de_conv2_0 51 -> 64 us, de_conv3_0 180 -> 240 us with 32, profiles/r06e_halo_bn.txt)
     const bool bn64 = Cout % 64 == 0 && !((fmt & 4) && omni_options().conv_halo_up2_bn_lat == 32);
-    if (bn64) omni_halo_launch(&a, 64, 4, true, 0, x1, grid * (Cout / 64), (hipStream_t)stream);
-    else      omni_halo_launch(&a, 32, 4, true, 0, x1, grid * (Cout / 32), (hipStream_t)stream);
+    const int bn = bn64 ? 64 : 32;
+    if (const int rc = omni_halo_launch(&a, bn, 4, true, 0, x1, grid * (Cout / bn), (hipStream_t)stream); rc != OMNI_OK) return rc;
     OMNI_HIP(hipGetLastError());
     return OMNI_OK;
 }
