@@ -714,6 +714,37 @@ int omni_attention_bwd_f32(const float* q, const float* kv, const float* grad_ou
 int omni_gelu_fwd_f32(const float* x, float* y, long long n, omni_stream_t stream);
 int omni_gelu_bwd_f32(const float* grad_y, const float* x, float* dx, long long n, omni_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * The encoder's first operators and the decoder's up-sampling in training mode.  fp32; activations contiguous NHWC.
+ * Nothing is allocated, nothing synchronises, nothing is read back; no atomics, every sum in a fixed order that depends on the shapes
+ * alone: the same bits on every run.  Every rejection (null pointers, M, H, W <= 0, C % 4, a short workspace: OMNI_ERR_INVALID)
+ * happens before a launch.
+ * omni_stem_conv_fwd_f32 (csrc/omni_stem_conv.hip): conv1 of model/spherical_model.py:254 ALONE — 7x7, stride 2, padding 3, 3 -> 64
+ * channels, y = conv(x, wt) + bias with no normalisation and no activation (omni_stem_f32 folds bn1 and the ReLU in).  x planar
+ * [M,3,H,W] with ANY H, W >= 1, wt [147][64] with k = (ky*7+kx)*3+c (omni_stem_f32's layout), bias [64] or NULL, y [M,Ho,Wo,64],
+ * Ho = (H-1)/2 + 1, Wo = (W-1)/2 + 1.
+ * omni_stem_conv_bwd_weight_f32: the gradient of that convolution (:254) w.r.t. wt and bias: dw[k][o] = sum over (m, oy, ox) of
+ * g[m,oy,ox,o] . x[m,c,2oy-3+ky,2ox-3+kx] (zero outside the image), dbias[o] = sum g[m,oy,ox,o], out of one pass.  g [M,Ho,Wo,64],
+ * dw [147][64], dbias [64]; either may be NULL (not written), not both.  fp32 FMAs over chunks of 8x8-pixel output tiles, pixels
+ * ascending within a chunk; the chunks' partial sums are added in double in a fixed order and rounded once.  There is no gradient
+ * w.r.t. x (the image).
+ * `workspace`: omni_stem_conv_bwd_workspace_bytes(M, H, W) = nchunk . 148 . 64 . 4 bytes (0 outside the scope), with
+ * ntiles = M . ceil(Ho/8) . ceil(Wo/8), tpc = max(4, ceil(ntiles / 1024)) tiles per chunk and nchunk = ceil(ntiles / tpc); any content,
+ * 16-byte aligned.
+ * omni_maxpool3x3s2_bwd_f32 (csrc/omni_maxpool_bwd.hip): the backward of omni_maxpool3x3s2_f32 (:255) w.r.t. its input: x [M,H,W,C] the
+ * forward's input, g [M,Ho,Wo,C], dx [M,H,W,C] written whole.  A gather: each input pixel recomputes the winner of the at most 2 x 2
+ * windows that contain it — the FIRST greatest element in (ky, kx) order over the taps inside the map, torch's rule — and adds the g of
+ * the windows it wins, windows in (oy, ox) order.  A NaN never wins against a number (the forward's fmaxf drops it too).
+ * omni_upsample_bilinear2x_bwd_f32 (csrc/omni_upsample_bwd.hip): the backward of omni_upsample_bilinear_f32 at Ho = 2H, Wo = 2W
+ * (:271,279,286,293,300) w.r.t. its input: g [M,2H,2W,C], dx [M,H,W,C] written whole.  A gather with the constant weights 0.25 / 0.75 / 1
+ * per axis, the at most 4 x 4 taps added in (row, column) order. */
+int omni_stem_conv_fwd_f32(const float* x, const float* wt, const float* bias, float* y, int M, int H, int W, omni_stream_t stream);
+size_t omni_stem_conv_bwd_workspace_bytes(int M, int H, int W);
+int omni_stem_conv_bwd_weight_f32(const float* g, const float* x, float* dw, float* dbias, int M, int H, int W, void* workspace,
+                                  size_t ws_bytes, omni_stream_t stream);
+int omni_maxpool3x3s2_bwd_f32(const float* g, const float* x, float* dx, int M, int H, int W, int C, omni_stream_t stream);
+int omni_upsample_bilinear2x_bwd_f32(const float* g, float* dx, int M, int H, int W, int C, omni_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,8 @@ EXPORTS = [
     "omni_batchnorm_workspace_bytes", "omni_batchnorm_fwd_f32", "omni_batchnorm_bwd_f32",
     "omni_layernorm_bwd_workspace_bytes", "omni_layernorm_fwd_f32", "omni_layernorm_bwd_f32",
     "omni_attention_bwd_workspace_bytes", "omni_attention_bwd_f32", "omni_gelu_fwd_f32", "omni_gelu_bwd_f32",
+    "omni_stem_conv_fwd_f32", "omni_stem_conv_bwd_workspace_bytes", "omni_stem_conv_bwd_weight_f32", "omni_maxpool3x3s2_bwd_f32",
+    "omni_upsample_bilinear2x_bwd_f32",
 ]
 
 
@@ -165,6 +167,12 @@ def load():
     lib.omni_attention_bwd_f32.argtypes = [vp] * 5 + [ci, ci, vp, sz, vp]
     lib.omni_gelu_fwd_f32.argtypes = [vp, vp, ll, vp]
     lib.omni_gelu_bwd_f32.argtypes = [vp] * 3 + [ll, vp]
+    lib.omni_stem_conv_fwd_f32.argtypes = [vp] * 4 + [ci] * 3 + [vp]
+    lib.omni_stem_conv_bwd_workspace_bytes.restype = sz
+    lib.omni_stem_conv_bwd_workspace_bytes.argtypes = [ci] * 3
+    lib.omni_stem_conv_bwd_weight_f32.argtypes = [vp] * 4 + [ci] * 3 + [vp, sz, vp]
+    lib.omni_maxpool3x3s2_bwd_f32.argtypes = [vp] * 3 + [ci] * 4 + [vp]
+    lib.omni_upsample_bilinear2x_bwd_f32.argtypes = [vp, vp] + [ci] * 4 + [vp]
     lib.omni_conv2d_sh_plan.argtypes = [ci] * 13 + [ctypes.POINTER(ci), ci]
     for name in EXPORTS:
         getattr(lib, name)          # AttributeError here = header/library mismatch

@@ -36,6 +36,22 @@ The transformer between layer4 and the decoder (csrc/omni_transformer_bwd.hip, D
 
 The same rules: fp32, fixed summation orders, no atomics, no host synchronisation, only the gradients autograd asks for.  No backward keeps
 anything of its forward but the operator's inputs: layer_norm recomputes its statistics, attention its probabilities, gelu reads x.
+
+The encoder's first operators and the decoder's up-sampling (csrc/omni_stem_conv.hip, omni_maxpool_bwd.hip, omni_upsample_bwd.hip,
+DESIGN.md §22):
+
+    y = stem_conv2d(x, weight, bias=None)                     # conv1: 7x7, stride 2, padding 3, x [M,3,H,W] (any H, W), weight [64,3,7,7]
+    y = max_pool2d(x)                                         # 3x3, stride 2, padding 1; C a multiple of 4
+    y = upsample_bilinear2x(x)                                # F.interpolate(size=(2H, 2W), bilinear, align_corners=False); C a multiple of 4
+    StemConv2d(3, 64, 7, stride=2, padding=3, bias=False), MaxPool2d(3, 2, 1), UpsampleBilinear2x()
+    model, names = convert(model, spatial=True)               # also swaps the stem and the nn.MaxPool2d(3, 2, 1) layers
+
+stem_conv2d has no activation and no folded normalisation (batch_norm(..., act="relu") follows it) and is differentiable w.r.t. weight
+and bias — fp32 FMAs, partial sums per chunk of output tiles, added in double in a fixed order; an x that requires a gradient is
+rejected: the image gradient is not built.  max_pool2d and upsample_bilinear2x are differentiable w.r.t. x, both backwards as gathers:
+the pool recomputes each window's winner from x (the first greatest element in scan order, torch's rule; no index map), the up-sampling
+adds its at most 4 x 4 taps with constant weights.  The same rules: fp32, no atomics, no host synchronisation, only the gradients
+autograd asks for, channels-last tensors without a copy (the stem's x is planar, its 37-KiB filter bank is transposed every step).
 """
 import ctypes
 
@@ -610,6 +626,190 @@ class TransformerCascade(torch.nn.Module):
         return self.encoder_norm(h).reshape(bs, N, C)
 
 
+# ------------------------------------------------------------------------------------------------ stem, max-pool, up-sampling
+STEM_GEOMETRY = "a 7x7 convolution at stride 2 with padding 3 from 3 to 64 channels"
+POOL_GEOMETRY = "a 3x3 max-pool at stride 2 with padding 1"
+
+
+def _check_stem_args(x, weight, bias):
+    """Every rejection of stem_conv2d, raised before anything is launched."""
+    _check_f32_dev((("x", x), ("weight", weight), ("bias", bias)), optional=("bias",))
+    if weight.dim() != 4 or tuple(weight.shape) != (64, 3, 7, 7):
+        raise ValueError(f"stem_conv2d: weight must be [64,3,7,7]: {STEM_GEOMETRY} is the only geometry built (got {tuple(weight.shape)})")
+    if x.dim() != 4 or x.numel() == 0 or x.shape[1] != 3:
+        raise ValueError(f"stem_conv2d: x must be a non-empty [M,3,H,W] tensor (got {tuple(x.shape)})")
+    if bias is not None and tuple(bias.shape) != (64,):
+        raise ValueError(f"stem_conv2d: bias must be [64] (got {tuple(bias.shape)})")
+    if x.requires_grad:
+        raise ValueError("stem_conv2d: x requires a gradient, but the image gradient of the stem is not built (no training script asks "
+                         "for it); pass x.detach()")
+
+
+class _StemConv2d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        lib = _lib.load()
+        xc = x.contiguous()                                                    # planar [M,3,H,W]
+        wk = weight.permute(2, 3, 1, 0).contiguous()                           # [7,7,3,64] = the library's [147][64]; 37 KiB, every step
+        b = bias.contiguous() if bias is not None else None
+        M, _, H, W = xc.shape
+        y = _empty((M, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 64), dtype=torch.float32, device=xc.device)
+        with torch.cuda.device(xc.device):
+            _lib.check(lib.omni_stem_conv_fwd_f32(_p(xc), _p(wk), _p(b), _p(y), M, H, W, _lib.stream_of(xc)), "stem_conv2d")
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(xc)
+        return _nchw(y)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        xc, = ctx.saved_tensors
+        need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        if not (need_w or need_b):
+            return None, None, None
+        M, _, H, W = xc.shape
+        dev = xc.device
+        g = _nhwc(grad_out.to(torch.float32))
+        nbytes = lib.omni_stem_conv_bwd_workspace_bytes(M, H, W)
+        if nbytes == 0:
+            raise ValueError(f"stem_conv2d backward: x of shape {tuple(xc.shape)} is outside the operator's scope")
+        ws = _empty(nbytes // 4, dtype=torch.float32, device=dev)
+        dw = _empty((7, 7, 3, 64), dtype=torch.float32, device=dev) if need_w else None
+        db = _empty(64, dtype=torch.float32, device=dev) if need_b else None
+        with torch.cuda.device(dev):
+            _lib.check(lib.omni_stem_conv_bwd_weight_f32(_p(g), _p(xc), _p(dw), _p(db), M, H, W, _p(ws), nbytes, _lib.stream_of(xc)),
+                       "stem_conv2d_bwd_weight")
+        return None, (dw.permute(3, 2, 0, 1) if need_w else None), db            # a view of [147][64]: no copy
+
+
+def stem_conv2d(x, weight, bias=None):
+    """conv(x, weight) + bias for the encoder's conv1 alone — 7x7, stride 2, padding 3, x [M,3,H,W] (any H, W), weight [64,3,7,7] ->
+    channels-last [M,64,Ho,Wo]; no activation, no folded normalisation.  Differentiable w.r.t. weight and bias, not w.r.t. x."""
+    _check_stem_args(x, weight, bias)
+    return _StemConv2d.apply(x, weight, bias)
+
+
+def _stem_in_scope(m):
+    return (m.in_channels == 3 and m.out_channels == 64 and tuple(m.kernel_size) == (7, 7) and tuple(m.stride) == (2, 2)
+            and not isinstance(m.padding, str) and tuple(m.padding) == (3, 3) and m.groups == 1 and tuple(m.dilation) == (1, 1)
+            and m.padding_mode == "zeros")
+
+
+class StemConv2d(torch.nn.Conv2d):
+    """nn.Conv2d(3, 64, 7, stride=2, padding=3) with the library's kernels under forward and backward: the same parameters and state dict.
+    Any other geometry is rejected."""
+
+    def __init__(self, in_channels=3, out_channels=64, kernel_size=7, stride=2, padding=3, bias=False, **kw):
+        super().__init__(in_channels, out_channels, kernel_size, stride=stride, padding=padding, bias=bias, **kw)
+        if not _stem_in_scope(self):
+            raise ValueError(f"ops.StemConv2d: {STEM_GEOMETRY}, no groups, no dilation, zero padding, is the only geometry built (got {self})")
+
+    def forward(self, x):
+        return stem_conv2d(x, self.weight, self.bias)
+
+
+def _check_spatial_x(who, x):
+    _check_f32_dev((("x", x),))
+    if x.dim() != 4 or x.numel() == 0:
+        raise ValueError(f"{who}: x must be a non-empty [M,C,H,W] tensor (got {tuple(x.shape)})")
+    if x.shape[1] % 4:
+        raise ValueError(f"{who}: the channel count must be a multiple of 4 (got C = {x.shape[1]})")
+
+
+class _MaxPool2d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        lib = _lib.load()
+        xn = _nhwc(x)
+        M, H, W, C = xn.shape
+        y = _empty((M, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), dtype=torch.float32, device=xn.device)
+        with torch.cuda.device(xn.device):
+            _lib.check(lib.omni_maxpool3x3s2_f32(_p(xn), _p(y), M, H, W, C, _lib.stream_of(xn)), "max_pool2d")
+        ctx.save_for_backward(xn)                                              # the winners are recomputed from x: no index map
+        return _nchw(y)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None
+        lib = _lib.load()
+        xn, = ctx.saved_tensors
+        M, H, W, C = xn.shape
+        g = _nhwc(grad_out.to(torch.float32))
+        dx = _empty((M, H, W, C), dtype=torch.float32, device=xn.device)
+        with torch.cuda.device(xn.device):
+            _lib.check(lib.omni_maxpool3x3s2_bwd_f32(_p(g), _p(xn), _p(dx), M, H, W, C, _lib.stream_of(xn)), "max_pool2d_bwd")
+        return _nchw(dx)
+
+
+def max_pool2d(x):
+    """F.max_pool2d(x, 3, 2, 1) on x [M,C,H,W], C a multiple of 4, differentiable w.r.t. x: the gradient of a window goes to its first
+    greatest element in scan order, as in torch.  (A NaN is dropped, not propagated: DESIGN.md §7.)"""
+    _check_spatial_x("max_pool2d", x)
+    return _MaxPool2d.apply(x)
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def _pool_in_scope(m):
+    return (_pair(m.kernel_size) == (3, 3) and _pair(m.stride) == (2, 2) and _pair(m.padding) == (1, 1) and _pair(m.dilation) == (1, 1)
+            and not m.ceil_mode and not m.return_indices)
+
+
+class MaxPool2d(torch.nn.MaxPool2d):
+    """nn.MaxPool2d(3, 2, 1) with the library's kernels under forward and backward.  Any other geometry is rejected."""
+
+    def __init__(self, kernel_size=3, stride=2, padding=1, **kw):
+        super().__init__(kernel_size, stride=stride, padding=padding, **kw)
+        if not _pool_in_scope(self):
+            raise ValueError(f"ops.MaxPool2d: {POOL_GEOMETRY}, dilation 1, ceil_mode=False, return_indices=False, is the only geometry "
+                             f"built (got {self})")
+
+    def forward(self, x):
+        return max_pool2d(x)
+
+
+class _UpsampleBilinear2x(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        lib = _lib.load()
+        xn = _nhwc(x)
+        M, H, W, C = xn.shape
+        y = _empty((M, 2 * H, 2 * W, C), dtype=torch.float32, device=xn.device)
+        with torch.cuda.device(xn.device):
+            _lib.check(lib.omni_upsample_bilinear_f32(_p(xn), _p(y), M, H, W, C, 2 * H, 2 * W, _lib.stream_of(xn)), "upsample_bilinear2x")
+        ctx.shape = (M, H, W, C)                                               # the operator is linear: its backward reads grad_out alone
+        return _nchw(y)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None
+        lib = _lib.load()
+        M, H, W, C = ctx.shape
+        g = _nhwc(grad_out.to(torch.float32))
+        dx = _empty((M, H, W, C), dtype=torch.float32, device=g.device)
+        with torch.cuda.device(g.device):
+            _lib.check(lib.omni_upsample_bilinear2x_bwd_f32(_p(g), _p(dx), M, H, W, C, _lib.stream_of(g)), "upsample_bilinear2x_bwd")
+        return _nchw(dx)
+
+
+def upsample_bilinear2x(x):
+    """F.interpolate(x, size=(2H, 2W), mode="bilinear", align_corners=False) on x [M,C,H,W], C a multiple of 4, differentiable w.r.t. x."""
+    _check_spatial_x("upsample_bilinear2x", x)
+    return _UpsampleBilinear2x.apply(x)
+
+
+class UpsampleBilinear2x(torch.nn.Module):
+    def forward(self, x):
+        return upsample_bilinear2x(x)
+
+
 def _conv_in_scope(m):
     return (m.groups == 1 and tuple(m.dilation) == (1, 1) and m.padding_mode == "zeros" and not isinstance(m.padding, str)
             and m.kernel_size[0] == m.kernel_size[1] and m.kernel_size[0] in (1, 3) and m.stride[0] == m.stride[1] and m.stride[0] in (1, 2)
@@ -622,20 +822,27 @@ def _swap_class(old, cls):
     new.__dict__.update(old.__dict__)
     for reg in ("_parameters", "_buffers", "_modules"):
         new.__dict__[reg] = dict(old.__dict__[reg])
-    new.act = "none"
+    if cls in (Conv2d, BatchNorm2d):
+        new.act = "none"
     return new
 
 
-def convert(module):
+def convert(module, spatial=False):
     """Replaces, in place, every nn.Conv2d inside Conv2d's scope (module docstring) and every nn.BatchNorm2d (channels a multiple of 4, a
     numeric momentum) by the class of this module, act="none".  The new layers hold the SAME Parameter and buffer objects, so an optimiser
     built before or after sees the same tensors and the state dict keeps its keys.  Everything else — a 3-channel stem, grouped or dilated
-    convolutions, momentum=None layers, subclasses — is left alone.  Returns (module, [the names replaced])."""
+    convolutions, momentum=None layers, subclasses — is left alone.  With `spatial=True` the stem, nn.Conv2d(3, 64, 7, stride=2,
+    padding=3) (no groups, no dilation, zero padding; a bias is allowed), becomes a StemConv2d and nn.MaxPool2d(3, 2, 1) (dilation 1,
+    ceil_mode=False, return_indices=False) a MaxPool2d as well.  Returns (module, [the names replaced])."""
     def swapped(m):
         if type(m) is torch.nn.Conv2d and _conv_in_scope(m):
             return _swap_class(m, Conv2d)
         if type(m) is torch.nn.BatchNorm2d and m.momentum is not None and m.num_features % 4 == 0:
             return _swap_class(m, BatchNorm2d)
+        if spatial and type(m) is torch.nn.Conv2d and _stem_in_scope(m):
+            return _swap_class(m, StemConv2d)
+        if spatial and type(m) is torch.nn.MaxPool2d and _pool_in_scope(m):
+            return _swap_class(m, MaxPool2d)
         return None
 
     root = swapped(module)
