@@ -6,6 +6,7 @@ something else).
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OMNI_LIB_VARIANT") or os.path.join(_HERE, "csrc", "libomnifusion_hip.so")    # (OMNI_LIB_VARIANT: tools/ only — a variant build of the library for same-box A/B timings)
@@ -22,47 +23,173 @@ class OmniLibraryMissing(ImportError):
     pass
 
 
-# every symbol include/omnifusion.h declares (tests/test_boundary.py parses the header and
-# checks this list against it and against the built library)
-EXPORTS = [
-    "omni_version", "omni_last_error", "omni_set_option", "omni_get_option", "omni_num_patches", "omni_patch_centers",
-    "omni_geometry_create", "omni_geometry_destroy", "omni_geometry_cache_clear", "omni_geometry_cache_size",
-    "omni_equi2pers", "omni_equi2pers_aux", "omni_pers2equi", "omni_pers2equi_conf", "omni_patches_to_planar",
-    "omni_equi2pers_g", "omni_pers2equi_g", "omni_equi2pers_bwd", "omni_pers2equi_bwd",
-    "omni_conv2d_nhwc_f32", "omni_stem_f32", "omni_maxpool3x3s2_f32", "omni_upsample_bilinear_f32",
-    "omni_add_hw_f32", "omni_add_period_f32", "omni_token_pack_f32", "omni_layernorm512_f32",
-    "omni_attention_f32", "omni_heads_f32", "omni_mlp_points_f32",
-    "omni_conv2d_nhwc_f16x3_ws", "omni_conv2d_sh_f16x3_ws", "omni_conv2d_sh_f16x3_post_ws", "omni_gemm_rows_sh_f16x3", "omni_gemm_rows_ln_sh_f16x3", "omni_gemm_rows_pack", "omni_conv3x3_up2_sh_f16x3", "omni_conv3x3_up2_heads_sh_f16x3", "omni_conv3x3_up2_heads_sh_f16x1", "omni_up2_heads_scratch_bytes", "omni_heads_pack_f16x3", "omni_sh_from_f32", "omni_sh_to_f32", "omni_sh_overflow",
-    "omni_stem_sh", "omni_stem_sh_f16x3", "omni_stem_sh_f16x1", "omni_maxpool3x3s2_sh", "omni_upsample_bilinear_sh", "omni_up2_tapsum_sh", "omni_add_hw_sh", "omni_add_period_sh", "omni_layernorm512_sh", "omni_gemm_sh_f16x3_ln512_ws", "omni_gemm_rows_slices_sh_f16x3", "omni_gemm_rows_ln_parts_sh_f16x3", "omni_splitk_reduce_ln512", "omni_wino_input_sh", "omni_conv3x3_wino_sh_f16x3", "omni_attention_qkv_sh",
-    "omni_conv2d_splitk_plan", "omni_conv2d_sh_plan", "omni_conv2d_nhwc_f32_ws",
-    "omni_masked_median_f32", "omni_depth_metrics_f32",
-    "omni_png_info", "omni_png_decode", "omni_png_decode_batch", "omni_zlib_inflate", "omni_png_checksums",
-    "omni_preprocess_rgb_u8", "omni_preprocess_depth_u16", "omni_berhu_workspace_bytes", "omni_berhu_loss_f32", "omni_berhu_grad_f32",
-    "omni_pointcloud_ply_f32",
-    "omni_dibr_workspace_bytes", "omni_splat_render_f32", "omni_dibr_f32",
-    "omni_splat_render_wt_f32", "omni_dibr_wt_f32", "omni_dibr_bwd_workspace_bytes", "omni_splat_render_bwd_f32", "omni_dibr_bwd_f32",
-    "omni_ssim_f32", "omni_photometric_workspace_bytes", "omni_photometric_grad_scratch_bytes", "omni_photometric_loss_f32",
-    "omni_photometric_grad_f32",
-    "omni_freeview_rotations", "omni_freeview_equi2pers_f32", "omni_freeview_pers2equi_f32", "omni_freeview_merge_f32",
-    "omni_freeview_bwd_workspace_bytes", "omni_freeview_equi2pers_bwd_f32", "omni_freeview_pers2equi_bwd_f32", "omni_freeview_merge_bwd_f32",
-    "omni_semantic_workspace_bytes", "omni_semantic_step_f32", "omni_semantic_grad_f32", "omni_confusion_matrix_i64",
-    "omni_depth_normals_f32", "omni_sobel_f32", "omni_l1_workspace_bytes", "omni_l1_loss_f32", "omni_l1_grad_f32",
-    "omni_geometry_terms_workspace_bytes", "omni_geometry_terms_f32", "omni_geometry_terms_grad_f32",
-    "omni_image_diff_f32", "omni_image_diff_norm_f32", "omni_vertex_diff_norm_f32",
-    "omni_guided_smoothness_workspace_bytes", "omni_guided_smoothness_f32", "omni_guided_smoothness_grad_f32",
-    "omni_depth_smoothness_workspace_bytes", "omni_depth_smoothness_f32", "omni_depth_smoothness_grad_f32",
-    "omni_chamfer_workspace_bytes", "omni_chamfer_nn_f32", "omni_chamfer_grad_f32",
-    "omni_augment_rgb_u8", "omni_augment_depth_u16", "omni_augment_planes",
-    "omni_planefit_workspace_bytes", "omni_planefit_normals_f32", "omni_planefit_normals_grad_f32", "omni_planefit_loss_f32",
-    "omni_planefit_loss_grad_f32",
-    "omni_conv2d_bwd_workspace_bytes", "omni_conv2d_bwd_epilogue_f32", "omni_conv2d_bwd_data_f16x3", "omni_conv2d_bwd_weight_f16x3",
-    "omni_conv2d_split_weights_f16x3",
-    "omni_batchnorm_workspace_bytes", "omni_batchnorm_fwd_f32", "omni_batchnorm_bwd_f32",
-    "omni_layernorm_bwd_workspace_bytes", "omni_layernorm_fwd_f32", "omni_layernorm_bwd_f32",
-    "omni_attention_bwd_workspace_bytes", "omni_attention_bwd_f32", "omni_gelu_fwd_f32", "omni_gelu_bwd_f32",
-    "omni_stem_conv_fwd_f32", "omni_stem_conv_bwd_workspace_bytes", "omni_stem_conv_bwd_weight_f32", "omni_maxpool3x3s2_bwd_f32",
-    "omni_upsample_bilinear2x_bwd_f32",
-]
+# The whole C ABI: one line per prototype of include/omnifusion.h, in header order — name, return type, parameter types.
+# A letter is a type and a number after it repeats it ("p3ii" = five parameters: three pointers, two ints).  `p` is every
+# pointer, out-parameters and omni_stream_t included; `s` is const char*.  tests/test_boundary.py parses the header and
+# holds this table to it, type by type.
+_CTYPE = {"v": None, "p": ctypes.c_void_p, "s": ctypes.c_char_p, "i": ctypes.c_int, "z": ctypes.c_size_t, "l": ctypes.c_longlong,
+          "q": ctypes.c_int64, "f": ctypes.c_float, "d": ctypes.c_double}
+_TABLE = """
+omni_version i
+omni_last_error s
+omni_set_option i si
+omni_get_option i sp
+omni_num_patches i i
+omni_patch_centers i iip
+omni_geometry_create i piffi4p
+omni_geometry_destroy v p
+omni_geometry_cache_clear v
+omni_geometry_cache_size i
+omni_equi2pers i ppi8ffip
+omni_equi2pers_aux i ppi3ffp
+omni_pers2equi i ppi8ffip
+omni_patches_to_planar i ppi6p
+omni_pers2equi_conf i p3i7ffip
+omni_equi2pers_g i p3i4p
+omni_pers2equi_g i p3i4p
+omni_equi2pers_bwd i ppi8ffip
+omni_pers2equi_bwd i ppi8ffip
+omni_conv2d_nhwc_f32 i p6i11p
+omni_conv2d_splitk_plan i lii
+omni_conv2d_nhwc_f32_ws i p6i12pzp
+omni_conv2d_nhwc_f16x3_ws i p6i12pzp
+omni_conv2d_sh_f16x3_ws i p6i13pzp
+omni_conv2d_sh_plan i i13pi
+omni_gemm_rows_sh_f16x3 i p5i5p
+omni_gemm_rows_pack i ppiip
+omni_gemm_rows_ln_sh_f16x3 i p3fp4i4p
+omni_conv3x3_up2_sh_f16x3 i p4i7p
+omni_up2_heads_scratch_bytes z ii
+omni_conv3x3_up2_heads_sh_f16x3 i p4ffpzppi3p
+omni_conv3x3_up2_heads_sh_f16x1 i p4ffpzppi3p
+omni_heads_pack_f16x3 i pp
+omni_conv2d_sh_f16x3_post_ws i p6i13pzpzp
+omni_wino_input_sh i ppi4p
+omni_conv3x3_wino_sh_f16x3 i p5i8pzp
+omni_sh_from_f32 i ppzp
+omni_sh_to_f32 i ppzp
+omni_sh_overflow i pi
+omni_stem_f32 i p4iip
+omni_maxpool3x3s2_f32 i ppi4p
+omni_upsample_bilinear_f32 i ppi6p
+omni_add_hw_f32 i ppi3p
+omni_add_period_f32 i ppzzp
+omni_stem_sh i p4iip
+omni_stem_sh_f16x3 i p4iip
+omni_stem_sh_f16x1 i p4iip
+omni_maxpool3x3s2_sh i ppi4p
+omni_upsample_bilinear_sh i ppi6p
+omni_up2_tapsum_sh i p3i5p
+omni_add_hw_sh i ppi3p
+omni_add_period_sh i ppzzp
+omni_layernorm512_sh i p4ifp
+omni_gemm_rows_slices_sh_f16x3 i p3i4p
+omni_gemm_rows_ln_parts_sh_f16x3 i pip5fp3i4p
+omni_splitk_reduce_ln512 i pip5fpiip
+omni_gemm_sh_f16x3_ln512_ws i p7fpi4pzp
+omni_attention_qkv_sh i ppiip
+omni_token_pack_f32 i p3i4p
+omni_layernorm512_f32 i p4ifp
+omni_attention_f32 i p3iip
+omni_heads_f32 i ppffppi3p
+omni_mlp_points_f32 i p7i3p
+omni_masked_median_f32 i ppzp3
+omni_depth_metrics_f32 i p5zp3
+omni_semantic_workspace_bytes z z
+omni_semantic_step_f32 i ppiizqip5
+omni_semantic_grad_f32 i ppiizqp4
+omni_confusion_matrix_i64 i ppzip3
+omni_preprocess_rgb_u8 i ppi5p
+omni_preprocess_depth_u16 i p3i5ffp
+omni_augment_rgb_u8 i p4i5p
+omni_augment_depth_u16 i p4i5ffp
+omni_augment_planes i ppippi6p
+omni_png_info i pzp4
+omni_png_decode i pzpi3
+omni_png_decode_batch i p3i5
+omni_zlib_inflate i pzpzpp
+omni_png_checksums i pzpp
+omni_berhu_workspace_bytes z i
+omni_berhu_loss_f32 i p4izp3
+omni_berhu_grad_f32 i p4izp4
+omni_pointcloud_ply_f32 i p3i3p
+omni_dibr_workspace_bytes z i4
+omni_splat_render_f32 i p3fppi4pp
+omni_dibr_f32 i p4ifippi4pp
+omni_splat_render_wt_f32 i p3fp3i4pp
+omni_dibr_wt_f32 i p4ifip3i4pp
+omni_dibr_bwd_workspace_bytes z i4
+omni_splat_render_bwd_f32 i p6fp3i4pp
+omni_dibr_bwd_f32 i p7ifippi4pp
+omni_ssim_f32 i ppi5pipp
+omni_photometric_workspace_bytes z i4
+omni_photometric_grad_scratch_bytes z i4
+omni_photometric_loss_f32 i p3ipi6pifp3
+omni_photometric_grad_f32 i p3ipi6pifp5
+omni_freeview_rotations i ppipp
+omni_freeview_equi2pers_f32 i p3i7ffip
+omni_freeview_pers2equi_f32 i p4i6ffp
+omni_freeview_merge_f32 i p4i7ffp
+omni_freeview_bwd_workspace_bytes z i5
+omni_freeview_equi2pers_bwd_f32 i p3i7ffipp
+omni_freeview_pers2equi_bwd_f32 i p3i6ffpp
+omni_freeview_merge_bwd_f32 i p3i7ffpp
+omni_depth_normals_f32 i ppi3pp
+omni_sobel_f32 i pi4p3
+omni_l1_workspace_bytes z i
+omni_l1_loss_f32 i p3iizip3
+omni_l1_grad_f32 i p3iizip4
+omni_geometry_terms_workspace_bytes z i3
+omni_geometry_terms_f32 i p4i5p3
+omni_geometry_terms_grad_f32 i p4i4p5
+omni_planefit_workspace_bytes z i3
+omni_planefit_normals_f32 i ppi3pp
+omni_planefit_normals_grad_f32 i p3i3p3
+omni_planefit_loss_f32 i p4i4p3
+omni_planefit_loss_grad_f32 i p4i4p4
+omni_image_diff_f32 i pi5pp
+omni_image_diff_norm_f32 i pi4pp
+omni_vertex_diff_norm_f32 i pi3pp
+omni_guided_smoothness_workspace_bytes z z
+omni_guided_smoothness_f32 i p4zp3
+omni_guided_smoothness_grad_f32 i p3zp4
+omni_depth_smoothness_workspace_bytes z i3
+omni_depth_smoothness_f32 i p5i4p3
+omni_depth_smoothness_grad_f32 i p5i4p4
+omni_chamfer_workspace_bytes z i4
+omni_chamfer_nn_f32 i p4i4p5
+omni_chamfer_grad_f32 i p6i4p4
+omni_conv2d_bwd_workspace_bytes z i10
+omni_conv2d_bwd_epilogue_f32 i p5liipzp
+omni_conv2d_bwd_data_f16x3 i p5i10pzp
+omni_conv2d_bwd_weight_f16x3 i p5i10pzp
+omni_conv2d_split_weights_f16x3 i ppiip
+omni_batchnorm_workspace_bytes z li
+omni_batchnorm_fwd_f32 i p8liiddipzp
+omni_batchnorm_bwd_f32 i p9li3pzp
+omni_layernorm_bwd_workspace_bytes z li
+omni_layernorm_fwd_f32 i p4lifp
+omni_layernorm_bwd_f32 i p6lifpzp
+omni_attention_bwd_workspace_bytes z ii
+omni_attention_bwd_f32 i p5iipzp
+omni_gelu_fwd_f32 i pplp
+omni_gelu_bwd_f32 i p3lp
+omni_stem_conv_fwd_f32 i p4i3p
+omni_stem_conv_bwd_workspace_bytes z i3
+omni_stem_conv_bwd_weight_f32 i p4i3pzp
+omni_maxpool3x3s2_bwd_f32 i p3i4p
+omni_upsample_bilinear2x_bwd_f32 i ppi4p
+"""
+
+
+def _signature(ret, params=""):
+    params = re.sub(r"([a-z])(\d+)", lambda m: m[1] * int(m[2]), params)
+    return _CTYPE[ret], tuple(_CTYPE[c] for c in params)
+
+
+# name -> (restype, argtypes) of every exported function; EXPORTS: their names
+SIGNATURES = {name: _signature(*sig) for name, *sig in map(str.split, _TABLE.strip().splitlines())}
+EXPORTS = list(SIGNATURES)
 
 
 def load():
@@ -79,103 +206,9 @@ def load():
     # two runtimes in the process and the second one sees no device).
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    lib.omni_last_error.restype = ctypes.c_char_p
-    lib.omni_version.restype = ctypes.c_int
-    lib.omni_up2_heads_scratch_bytes.restype = ctypes.c_size_t
-    lib.omni_dibr_workspace_bytes.restype = ctypes.c_size_t
-    lib.omni_splat_render_f32.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_float] + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
-    lib.omni_dibr_f32.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_float, ctypes.c_int] + [ctypes.c_void_p] * 2 + \
-        [ctypes.c_int] * 4 + [ctypes.c_void_p] * 2
-    vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-    lib.omni_splat_render_wt_f32.argtypes = [vp] * 3 + [cf] + [vp] * 3 + [ci] * 4 + [vp] * 2
-    lib.omni_dibr_wt_f32.argtypes = [vp] * 4 + [ci, cf, ci] + [vp] * 3 + [ci] * 4 + [vp] * 2
-    lib.omni_dibr_bwd_workspace_bytes.restype = ctypes.c_size_t
-    lib.omni_splat_render_bwd_f32.argtypes = [vp] * 6 + [cf] + [vp] * 3 + [ci] * 4 + [vp] * 2
-    lib.omni_dibr_bwd_f32.argtypes = [vp] * 7 + [ci, cf, ci] + [vp] * 2 + [ci] * 4 + [vp] * 2
-    lib.omni_ssim_f32.argtypes = [vp] * 2 + [ci] * 5 + [vp, ci, vp, vp]
-    lib.omni_photometric_workspace_bytes.restype = ctypes.c_size_t
-    lib.omni_photometric_grad_scratch_bytes.restype = ctypes.c_size_t
-    lib.omni_photometric_loss_f32.argtypes = [vp, vp, vp, ci, vp, ci] + [ci] * 5 + [vp, ci, cf] + [vp] * 3
-    lib.omni_photometric_grad_f32.argtypes = [vp, vp, vp, ci, vp, ci] + [ci] * 5 + [vp, ci, cf] + [vp] * 5
-    lib.omni_freeview_rotations.argtypes = [vp, vp, ci, vp, vp]
-    lib.omni_freeview_equi2pers_f32.argtypes = [vp] * 3 + [ci] * 7 + [cf, cf, ci, vp]
-    lib.omni_freeview_pers2equi_f32.argtypes = [vp] * 4 + [ci] * 6 + [cf, cf, vp]
-    lib.omni_freeview_merge_f32.argtypes = [vp] * 4 + [ci] * 7 + [cf, cf, vp]
-    lib.omni_freeview_bwd_workspace_bytes.restype = ctypes.c_size_t
-    lib.omni_freeview_bwd_workspace_bytes.argtypes = [ci] * 5
-    lib.omni_freeview_equi2pers_bwd_f32.argtypes = [vp] * 3 + [ci] * 7 + [cf, cf, ci, vp, vp]
-    lib.omni_freeview_pers2equi_bwd_f32.argtypes = [vp] * 3 + [ci] * 6 + [cf, cf, vp, vp]
-    lib.omni_freeview_merge_bwd_f32.argtypes = [vp] * 3 + [ci] * 7 + [cf, cf, vp, vp]
-    sz, i64 = ctypes.c_size_t, ctypes.c_int64
-    lib.omni_semantic_workspace_bytes.restype = sz
-    lib.omni_semantic_workspace_bytes.argtypes = [sz]
-    lib.omni_semantic_step_f32.argtypes = [vp, vp, ci, ci, sz, i64, ci] + [vp] * 5
-    lib.omni_semantic_grad_f32.argtypes = [vp, vp, ci, ci, sz, i64] + [vp] * 4
-    lib.omni_confusion_matrix_i64.argtypes = [vp, vp, sz, ci] + [vp] * 3
-    lib.omni_depth_normals_f32.argtypes = [vp, vp, ci, ci, ci, vp, vp]
-    lib.omni_sobel_f32.argtypes = [vp] + [ci] * 4 + [vp] * 3
-    lib.omni_l1_workspace_bytes.restype = sz
-    lib.omni_l1_workspace_bytes.argtypes = [ci]
-    lib.omni_l1_loss_f32.argtypes = [vp] * 3 + [ci, ci, sz, ci] + [vp] * 3
-    lib.omni_l1_grad_f32.argtypes = [vp] * 3 + [ci, ci, sz, ci] + [vp] * 4
-    lib.omni_geometry_terms_workspace_bytes.restype = sz
-    lib.omni_geometry_terms_workspace_bytes.argtypes = [ci] * 3
-    lib.omni_geometry_terms_f32.argtypes = [vp] * 4 + [ci] * 5 + [vp] * 3
-    lib.omni_geometry_terms_grad_f32.argtypes = [vp] * 4 + [ci] * 4 + [vp] * 5
-    lib.omni_image_diff_f32.argtypes = [vp] + [ci] * 5 + [vp] * 2
-    lib.omni_image_diff_norm_f32.argtypes = [vp] + [ci] * 4 + [vp] * 2
-    lib.omni_vertex_diff_norm_f32.argtypes = [vp] + [ci] * 3 + [vp] * 2
-    lib.omni_guided_smoothness_workspace_bytes.restype = sz
-    lib.omni_guided_smoothness_workspace_bytes.argtypes = [sz]
-    lib.omni_guided_smoothness_f32.argtypes = [vp] * 4 + [sz] + [vp] * 3
-    lib.omni_guided_smoothness_grad_f32.argtypes = [vp] * 3 + [sz] + [vp] * 4
-    lib.omni_depth_smoothness_workspace_bytes.restype = sz
-    lib.omni_depth_smoothness_workspace_bytes.argtypes = [ci] * 3
-    lib.omni_depth_smoothness_f32.argtypes = [vp] * 5 + [ci] * 4 + [vp] * 3
-    lib.omni_depth_smoothness_grad_f32.argtypes = [vp] * 5 + [ci] * 4 + [vp] * 4
-    lib.omni_chamfer_workspace_bytes.restype = sz
-    lib.omni_chamfer_workspace_bytes.argtypes = [ci] * 4
-    lib.omni_chamfer_nn_f32.argtypes = [vp] * 4 + [ci] * 4 + [vp] * 5
-    lib.omni_chamfer_grad_f32.argtypes = [vp] * 6 + [ci] * 4 + [vp] * 4
-    lib.omni_augment_rgb_u8.argtypes = [vp] * 4 + [ci] * 5 + [vp]
-    lib.omni_augment_depth_u16.argtypes = [vp] * 4 + [ci] * 5 + [cf, cf, vp]
-    lib.omni_augment_planes.argtypes = [vp, vp, ci, vp, vp] + [ci] * 6 + [vp]
-    lib.omni_planefit_workspace_bytes.restype = sz
-    lib.omni_planefit_workspace_bytes.argtypes = [ci] * 3
-    lib.omni_planefit_normals_f32.argtypes = [vp, vp, ci, ci, ci, vp, vp]
-    lib.omni_planefit_normals_grad_f32.argtypes = [vp] * 3 + [ci] * 3 + [vp] * 3
-    lib.omni_planefit_loss_f32.argtypes = [vp] * 4 + [ci] * 4 + [vp] * 3
-    lib.omni_planefit_loss_grad_f32.argtypes = [vp] * 4 + [ci] * 4 + [vp] * 4
-    lib.omni_conv2d_bwd_workspace_bytes.restype = sz
-    lib.omni_conv2d_bwd_workspace_bytes.argtypes = [ci] * 10
-    lib.omni_conv2d_bwd_epilogue_f32.argtypes = [vp] * 5 + [ctypes.c_longlong, ci, ci, vp, sz, vp]
-    lib.omni_conv2d_bwd_data_f16x3.argtypes = [vp] * 5 + [ci] * 10 + [vp, sz, vp]
-    lib.omni_conv2d_bwd_weight_f16x3.argtypes = [vp] * 5 + [ci] * 10 + [vp, sz, vp]
-    lib.omni_conv2d_split_weights_f16x3.argtypes = [vp, vp, ci, ci, vp]
-    cd = ctypes.c_double
-    lib.omni_batchnorm_workspace_bytes.restype = sz
-    lib.omni_batchnorm_workspace_bytes.argtypes = [ctypes.c_longlong, ci]
-    lib.omni_batchnorm_fwd_f32.argtypes = [vp] * 8 + [ctypes.c_longlong, ci, ci, cd, cd, ci, vp, sz, vp]
-    lib.omni_batchnorm_bwd_f32.argtypes = [vp] * 9 + [ctypes.c_longlong, ci, ci, ci, vp, sz, vp]
-    ll = ctypes.c_longlong
-    lib.omni_layernorm_bwd_workspace_bytes.restype = sz
-    lib.omni_layernorm_bwd_workspace_bytes.argtypes = [ll, ci]
-    lib.omni_layernorm_fwd_f32.argtypes = [vp] * 4 + [ll, ci, cf, vp]
-    lib.omni_layernorm_bwd_f32.argtypes = [vp] * 6 + [ll, ci, cf, vp, sz, vp]
-    lib.omni_attention_bwd_workspace_bytes.restype = sz
-    lib.omni_attention_bwd_workspace_bytes.argtypes = [ci, ci]
-    lib.omni_attention_bwd_f32.argtypes = [vp] * 5 + [ci, ci, vp, sz, vp]
-    lib.omni_gelu_fwd_f32.argtypes = [vp, vp, ll, vp]
-    lib.omni_gelu_bwd_f32.argtypes = [vp] * 3 + [ll, vp]
-    lib.omni_stem_conv_fwd_f32.argtypes = [vp] * 4 + [ci] * 3 + [vp]
-    lib.omni_stem_conv_bwd_workspace_bytes.restype = sz
-    lib.omni_stem_conv_bwd_workspace_bytes.argtypes = [ci] * 3
-    lib.omni_stem_conv_bwd_weight_f32.argtypes = [vp] * 4 + [ci] * 3 + [vp, sz, vp]
-    lib.omni_maxpool3x3s2_bwd_f32.argtypes = [vp] * 3 + [ci] * 4 + [vp]
-    lib.omni_upsample_bilinear2x_bwd_f32.argtypes = [vp, vp] + [ci] * 4 + [vp]
-    lib.omni_conv2d_sh_plan.argtypes = [ci] * 13 + [ctypes.POINTER(ci), ci]
-    for name in EXPORTS:
-        getattr(lib, name)          # AttributeError here = header/library mismatch
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)          # AttributeError here = header/library mismatch
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
@@ -221,7 +254,7 @@ def check(status, what=""):
 
 
 def ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def stream_of(t):

@@ -31,21 +31,17 @@ The per-item parameters reach the kernels as a table in DEVICE memory (`Augmenta
 feeder it travels in the frames' pinned slot.  Nothing is read back, the calls are capturable, a replayed graph reads the table's
 current contents.
 """
-import ctypes
 from typing import NamedTuple
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr as _p
 
 
 def _hw(size):
     return (int(size[0]), int(size[1])) if isinstance(size, (tuple, list)) else (int(size), int(size))
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 def preprocess_rgb(frames_u8, size, out=None):
@@ -77,8 +73,8 @@ def preprocess_depth(frames_u16, size, min_depth=0.1, max_depth=8.0):
     depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=f.device)
     mask = torch.empty((B, 1, H, W), dtype=torch.uint8, device=f.device)
     with torch.cuda.device(f.device):
-        _lib.check(_lib.load().omni_preprocess_depth_u16(_p(f), _p(depth), _p(mask), B, Hs, Ws, H, W, ctypes.c_float(min_depth),
-                                                        ctypes.c_float(max_depth), _lib.stream_of(f)), "preprocess_depth")
+        _lib.check(_lib.load().omni_preprocess_depth_u16(_p(f), _p(depth), _p(mask), B, Hs, Ws, H, W, min_depth, max_depth,
+                                                        _lib.stream_of(f)), "preprocess_depth")
     return depth, mask
 
 
@@ -304,10 +300,6 @@ def _device_aug(aug, B, device):
     return aug
 
 
-def _gp(aug):
-    return ctypes.c_void_p(None if aug.gamma is None else aug.gamma.data_ptr())
-
-
 def augment_rgb(frames_u8, size, aug, out=None):
     """`preprocess_rgb` with the augmentation folded in: [B,Hs,Ws,3] uint8 -> [B,3,H,W] float32, one pass."""
     if not isinstance(frames_u8, torch.Tensor) or not frames_u8.is_cuda:
@@ -324,7 +316,7 @@ def augment_rgb(frames_u8, size, aug, out=None):
           or not out.is_contiguous()):
         raise ValueError(f"out must be a contiguous float32 tensor [{B},3,{H},{W}] on {f.device} (the kernel writes through its raw pointer)")
     with torch.cuda.device(f.device):
-        _lib.check(_lib.load().omni_augment_rgb_u8(_p(f), _p(out), _p(a.table), _gp(a), B, Hs, Ws, H, W, _lib.stream_of(f)), "augment_rgb")
+        _lib.check(_lib.load().omni_augment_rgb_u8(_p(f), _p(out), _p(a.table), _p(a.gamma), B, Hs, Ws, H, W, _lib.stream_of(f)), "augment_rgb")
     return out
 
 
@@ -348,8 +340,8 @@ def augment_depth(frames_u16, size, aug, min_depth=0.1, max_depth=8.0, out=None)
             if not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != f.device or tuple(t.shape) != (B, 1, H, W) or not t.is_contiguous():
                 raise ValueError(f"out must be contiguous (float32, uint8) tensors [{B},1,{H},{W}] on {f.device}")
     with torch.cuda.device(f.device):
-        _lib.check(_lib.load().omni_augment_depth_u16(_p(f), _p(depth), _p(mask), _p(a.table), B, Hs, Ws, H, W, ctypes.c_float(min_depth),
-                                                     ctypes.c_float(max_depth), _lib.stream_of(f)), "augment_depth")
+        _lib.check(_lib.load().omni_augment_depth_u16(_p(f), _p(depth), _p(mask), _p(a.table), B, Hs, Ws, H, W, min_depth, max_depth,
+                                                     _lib.stream_of(f)), "augment_depth")
     return depth, mask
 
 
@@ -382,7 +374,7 @@ def augment(x, aug, color=False, inverse=False, out=None):
         raise ValueError(f"out must be a contiguous {f.dtype} tensor {tuple(f.shape)} on {f.device}")
     with torch.cuda.device(f.device):
         _lib.check(_lib.load().omni_augment_planes(_p(f), _p(out), f.element_size(), _p(a.table),
-                                                  ctypes.c_void_p(None if gamma is None else gamma.data_ptr()), B, C, H, W, int(color), int(bool(inverse)),
+                                                  _p(gamma), B, C, H, W, int(color), int(bool(inverse)),
                                                   _lib.stream_of(f)), "augment")
     return out
 

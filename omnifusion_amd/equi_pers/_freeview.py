@@ -9,18 +9,14 @@ with the same angles launches its kernel and nothing else, so it can be captured
 Angles given as a device tensor are read back on every call (one synchronisation): pass them on the host where that matters.
 """
 import collections
-import ctypes
 
 import torch
 
 from .. import _lib
+from .._lib import ptr as _p
 
 _TABLES = collections.OrderedDict()          # (theta bytes, phi bytes, device) -> (rot_fwd [N,9], rot_inv [N,18]) on the device
 _TABLES_MAX = 64
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 NO_BACKWARD = "the plain free-view mirrors have no backward; the differentiable operators are omnifusion_amd.equi_pers.differentiable"

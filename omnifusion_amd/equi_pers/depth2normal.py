@@ -9,16 +9,11 @@ det and inv over them; here one tiled kernel of libomnifusion_hip.so (csrc/omni_
 float64, and two kernels give the backward (no atomics: the bits do not change from run to run).  Any H, W >= 1; a NaN depth gives NaN normals at
 exactly the centres whose windows hold it.  The loss built on these normals is supervision.geometry.planefit_normal_loss.
 """
-import ctypes
-
 import torch
 
 from .. import _lib
+from .._lib import ptr as _p
 from ..spherical.grid import ray_tables
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 class _PlanefitNormals(torch.autograd.Function):

@@ -61,7 +61,7 @@ class _Equi2PersFn(torch.autograd.Function):
         grad_erp = torch.empty((B, C, H, W), dtype=torch.float32, device=g.device)
         with torch.cuda.device(g.device):
             rc = lib.omni_equi2pers_bwd(_lib.ptr(g), _lib.ptr(grad_erp), _lib.F32, B, C, H, W, ph, pw, int(nrows),
-                                        ctypes.c_float(fov_h), ctypes.c_float(fov_w), int(layout), _lib.stream_of(g))
+                                        fov_h, fov_w, int(layout), _lib.stream_of(g))
         _lib.check(rc, "equi2pers backward")
         return grad_erp, None, None, None, None
 
@@ -84,7 +84,7 @@ def equi2pers_patches(erp_img, fov, nrows, patch_size, layout=_lib.LAYOUT_BCHWN)
     pers = torch.empty(shape, dtype=erp.dtype, device=erp.device)
     with torch.cuda.device(erp.device):
         rc = lib.omni_equi2pers(_lib.ptr(erp), _lib.ptr(pers), _lib.dtype_code(erp), B, C, H, W, ph, pw,
-                                int(nrows), ctypes.c_float(fov_h), ctypes.c_float(fov_w), int(layout),
+                                int(nrows), fov_h, fov_w, int(layout),
                                 _lib.stream_of(erp))
     _lib.check(rc, "equi2pers")
     return pers
@@ -105,7 +105,7 @@ def equi2pers_aux(device, fov, nrows, patch_size, want_xyz=True, want_uv=True):
     if ref is not None:
         with torch.cuda.device(device):
             rc = lib.omni_equi2pers_aux(_lib.ptr(xyz) if want_xyz else None, _lib.ptr(uv) if want_uv else None,
-                                        ph, pw, int(nrows), ctypes.c_float(fov_h), ctypes.c_float(fov_w),
+                                        ph, pw, int(nrows), fov_h, fov_w,
                                         _lib.stream_of(ref))
         _lib.check(rc, "equi2pers_aux")
     cp = (ctypes.c_float * (2 * N))()

@@ -11,8 +11,6 @@
 All arithmetic runs in libomnifusion_hip.so (csrc/omni_pers2equi.hip; tables: csrc/omni_p2e_tables.hip).  Differentiable w.r.t. `pers_img` (float32) like
 the reference's indexing gathers (:174-196): the backward is the HIP scatter kernel `omni_pers2equi_bwd` (csrc/omni_pers2equi_bwd.hip).
 """
-import ctypes
-
 import torch
 
 from .. import _lib
@@ -62,7 +60,7 @@ class _Pers2EquiFn(torch.autograd.Function):
         grad_pers = torch.empty(shape, dtype=torch.float32, device=g.device)
         with torch.cuda.device(g.device):
             rc = lib.omni_pers2equi_bwd(_lib.ptr(g), _lib.ptr(grad_pers), _lib.F32, B, C, ph, pw, H, W, int(nrows),
-                                        ctypes.c_float(fov_h), ctypes.c_float(fov_w), int(layout), _lib.stream_of(g))
+                                        fov_h, fov_w, int(layout), _lib.stream_of(g))
         _lib.check(rc, "pers2equi backward")
         return grad_pers, None, None, None, None, None
 
@@ -89,7 +87,7 @@ def pers2equi(pers_img, fov, nrows, patch_size, erp_size, layer_name=None, layou
                        "patches_to_planar")
             pers, layout = planar, _lib.LAYOUT_BNCHW
         rc = lib.omni_pers2equi(_lib.ptr(pers), _lib.ptr(erp), _lib.dtype_code(pers), B, C, ph, pw, H, W,
-                                int(nrows), ctypes.c_float(fov_h), ctypes.c_float(fov_w), int(layout),
+                                int(nrows), fov_h, fov_w, int(layout),
                                 _lib.stream_of(pers))
     _lib.check(rc, "pers2equi")
     return erp
@@ -111,7 +109,7 @@ def pers2equi_conf(pred_w, conf, fov, nrows, patch_size, erp_size, layout=_lib.L
     out = torch.empty((B, 1, H, W), dtype=torch.float32, device=a.device)
     with torch.cuda.device(a.device):
         rc = lib.omni_pers2equi_conf(_lib.ptr(a), _lib.ptr(b), _lib.ptr(out), _lib.dtype_code(a), B, ph, pw,
-                                     H, W, int(nrows), ctypes.c_float(fov_h), ctypes.c_float(fov_w),
+                                     H, W, int(nrows), fov_h, fov_w,
                                      int(layout), _lib.stream_of(a))
     _lib.check(rc, "pers2equi_conf")
     return out

@@ -9,17 +9,12 @@
 Everything numeric (masked medians by radix select, the seven masked reductions) runs in libomnifusion_hip.so
 (csrc/omni_eval.hip); nothing is copied to the host until `averages()` is called.
 """
-import ctypes
-
 import torch
 
 from . import _lib
+from ._lib import ptr as _p
 
 NAMES = ("abs_rel", "sq_rel", "rms_sq_lin", "rms_sq_log", "d1", "d2", "d3")
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 def masked_median(x, mask):
@@ -29,7 +24,7 @@ def masked_median(x, mask):
     ws = torch.empty(260, dtype=torch.int32, device=x.device)
     out = torch.empty(1, dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.check(lib.omni_masked_median_f32(_p(x), _p(mask), ctypes.c_size_t(x.numel()), _p(ws), _p(out), _lib.stream_of(x)), "masked_median")
+        _lib.check(lib.omni_masked_median_f32(_p(x), _p(mask), x.numel(), _p(ws), _p(out), _lib.stream_of(x)), "masked_median")
     return out
 
 
@@ -50,7 +45,7 @@ def compute_eval_metrics(output, gt, depth_mask):
     ws = torch.empty(2048 * 9, dtype=torch.float64, device=output.device)
     out = torch.empty(9, dtype=torch.float32, device=output.device)
     with torch.cuda.device(output.device):
-        _lib.check(lib.omni_depth_metrics_f32(_p(output), _p(gt), _p(mask), _p(num), _p(den), ctypes.c_size_t(output.numel()),
+        _lib.check(lib.omni_depth_metrics_f32(_p(output), _p(gt), _p(mask), _p(num), _p(den), output.numel(),
                                               _p(ws), _p(out), _lib.stream_of(output)), "depth_metrics")
     return out
 

@@ -15,22 +15,17 @@ Divergences: a pair whose gt is >= K or whose prediction is outs
 `pred*13 + gt` spills into the next row or makes `reshape` fail); for a class absent from both maps the reference's `get_iou` returns a bare
 float('nan') and its `evaluate` then dies with TypeError on `[0]` — here `get_iou` returns (nan, 0, 0) and `evaluate` a NaN mean.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr as _p
 
 # the reference's constants (iou.py:12-16), as it ships them
 VALID_CLASS_IDS = np.array([0, 1])
 CLASS_LABELS = ['beam', 'board', 'bookcase', 'ceiling', 'chair', 'clutter', 'column', 'door', 'floor', 'sofa', 'table', 'wall', 'window']
 UNKNOWN_ID = -100
 N_CLASSES = len(CLASS_LABELS)
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def printout(flog, data):

@@ -13,6 +13,7 @@ import os
 import torch
 
 from .. import _lib
+from .._lib import ptr as _p
 from ..equi_pers.equi2pers_v3 import equi2pers_patches, equi2pers_aux, pair, _NPATCH
 from ..equi_pers.pers2equi_v3 import pers2equi, pers2equi_conf
 
@@ -20,10 +21,6 @@ ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 _LAYERS = [("layer1", 3, 1), ("layer2", 4, 2), ("layer3", 6, 2), ("layer4", 3, 2)]
 _BN_EPS = 1e-5
 PRECISIONS = ("f16x3", "f16x1", "fp32")
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def split_weights_f16x3(w):
@@ -200,19 +197,19 @@ class Engine:
             late_post, post = post, None
         if self.sh and post is not None:                            # `+ post` after the activation, inside the epilogue (SH mode, never split)
             rc = lib.omni_conv2d_sh_f16x3_post_ws(_p(x), _p(x2), _p(self.w[key + ".w16"]), b, _p(res), _p(out), (0 if out_f32 else 1) | self._x1,
-                                                  M, H, Wd, C1, C2, Cout, k, k, stride, pad, act, S, _p(ws), ctypes.c_size_t(nb),
-                                                  _p(post), ctypes.c_size_t(post.numel()), self._s)
+                                                  M, H, Wd, C1, C2, Cout, k, k, stride, pad, act, S, _p(ws), nb,
+                                                  _p(post), post.numel(), self._s)
         elif self.sh:
             lat = 4 if (self._bs == 1 and self.latency_plan) else 0     # fmt bit 2: a lone panorama keeps the im2col tiles for 16-wide images
             rc = lib.omni_conv2d_sh_f16x3_ws(_p(x), _p(x2), _p(self.w[key + ".w16"]), b, _p(res), _p(out), (0 if out_f32 else 1) | lat | self._x1,
-                                             M, H, Wd, C1, C2, Cout, k, k, stride, pad, act, S, _p(ws), ctypes.c_size_t(nb), self._s)
+                                             M, H, Wd, C1, C2, Cout, k, k, stride, pad, act, S, _p(ws), nb, self._s)
         else:
             rc = lib.omni_conv2d_nhwc_f32_ws(_p(x), _p(x2), _p(self.w[key + ".w"]), b, _p(res), _p(out), M, H, Wd, C1, C2, Cout,
-                                             k, k, stride, pad, act, S, _p(ws), ctypes.c_size_t(nb), self._s)
+                                             k, k, stride, pad, act, S, _p(ws), nb, self._s)
         _lib.check(rc, "conv2d " + key)
         if late_post is not None:
             _lib.check((lib.omni_add_period_f32 if (out_f32 or not self.sh) else lib.omni_add_period_sh)(   # an fp32 NHWC output is never split-half
-                _p(out), _p(late_post), ctypes.c_size_t(out.numel()), ctypes.c_size_t(late_post.numel()), self._s), "add post " + key)
+                _p(out), _p(late_post), out.numel(), late_post.numel(), self._s), "add post " + key)
         return out
 
     NOMINAL_BATCH = 8
@@ -230,7 +227,7 @@ class Engine:
         plan_batch = self.SINGLE_BATCH if (self._bs == 1 and self.latency_plan) else self.NOMINAL_BATCH
         rows_plan = rows // self._bs * plan_batch
         lib = _lib.load()
-        S = int(lib.omni_conv2d_splitk_plan(ctypes.c_longlong(rows_plan), Cout, ksteps))
+        S = int(lib.omni_conv2d_splitk_plan(rows_plan, Cout, ksteps))
         if S <= 1:
             return 1, None, 0
         ws, nb = self._workspace(S * rows * Cout * 4, device)
@@ -253,7 +250,7 @@ class Engine:
         out = torch.empty((rows, Nout), dtype=torch.float32, device=x.device)
         S, ws, nb = self._splitk(rows, Nout, K // 32, x.device)
         rc = lib.omni_conv2d_nhwc_f32_ws(_p(x), None, _p(self.w[wkey]), _p(self.w[bkey]) if bkey else None, _p(res), _p(out),
-                                         rows, 1, 1, K, 0, Nout, 1, 1, 1, 0, act, S, _p(ws), ctypes.c_size_t(nb), self._s)
+                                         rows, 1, 1, K, 0, Nout, 1, 1, 1, 0, act, S, _p(ws), nb, self._s)
         _lib.check(rc, "gemm " + wkey)
         return out
 
@@ -281,8 +278,7 @@ class Engine:
             return out
         S, ws, nb = (1, None, 0) if K <= 512 else self._splitk(rows, Nout, K // 32, x.device)
         rc = lib.omni_conv2d_sh_f16x3_ws(_p(x), None, _p(self.w[w16key]), _p(self.w[bkey]) if bkey else None, _p(res), _p(out),
-                                         (1 if out_sh else 0) | 2, rows, 1, 1, K, 0, Nout, 1, 1, 1, 0, act, S, _p(ws),
-                                         ctypes.c_size_t(nb), self._s)
+                                         (1 if out_sh else 0) | 2, rows, 1, 1, K, 0, Nout, 1, 1, 1, 0, act, S, _p(ws), nb, self._s)
         _lib.check(rc, "gemm " + w16key)
         return out
 
@@ -305,8 +301,8 @@ class Engine:
             return self._gemm_sh(h, w16key, bkey, rows, 2048, 512, res=tok), None, None
         wk, bk, eps, out_sh = nxt
         out, y = torch.empty((rows, 512), dtype=torch.float32, device=h.device), torch.empty((rows, 512), dtype=torch.float32, device=h.device)
-        rc = _lib.load().omni_gemm_sh_f16x3_ln512_ws(_p(h), _p(self.w[w16key]), _p(self.w[bkey]), _p(tok), _p(out), _p(self.w[wk]), _p(self.w[bk]), ctypes.c_float(eps),
-                                                     _p(y), 1 if out_sh else 0, rows, 2048, S, _p(ws), ctypes.c_size_t(nb), self._s)
+        rc = _lib.load().omni_gemm_sh_f16x3_ln512_ws(_p(h), _p(self.w[w16key]), _p(self.w[bkey]), _p(tok), _p(out), _p(self.w[wk]), _p(self.w[bk]), eps,
+                                                     _p(y), 1 if out_sh else 0, rows, 2048, S, _p(ws), nb, self._s)
         _lib.check(rc, "gemm+ln " + w16key)
         return out, y, None
 
@@ -315,7 +311,7 @@ class Engine:
         parts, S, bkey, res_tok = pending
         tok = torch.empty((rows, 512), dtype=torch.float32, device=parts.device)
         out = torch.empty((rows, Nout), dtype=torch.float32, device=parts.device)
-        rc = _lib.load().omni_gemm_rows_ln_parts_sh_f16x3(_p(parts), S, _p(self.w[bkey]), _p(res_tok), _p(tok), _p(self.w[lnw]), _p(self.w[lnb]), ctypes.c_float(eps),
+        rc = _lib.load().omni_gemm_rows_ln_parts_sh_f16x3(_p(parts), S, _p(self.w[bkey]), _p(res_tok), _p(tok), _p(self.w[lnw]), _p(self.w[lnb]), eps,
                                                           _p(self._rows_weights(w16key, Nout, 512)), None, _p(out), 0, rows, Nout, ACT_NONE, self._s)
         _lib.check(rc, "ln+gemm (slices) " + w16key)
         return tok, out
@@ -327,19 +323,19 @@ class Engine:
         if self._bs == 1 and self.latency_plan and self.rows_gemm and self.fuse_ln and rows <= 32:
             lib = _lib.load()
             out = torch.empty((rows, Nout), dtype=torch.float32, device=x.device)
-            _lib.check(lib.omni_gemm_rows_ln_sh_f16x3(_p(x), _p(self.w[lnw]), _p(self.w[lnb]), ctypes.c_float(eps), _p(self._rows_weights(w16key, Nout, 512)),
+            _lib.check(lib.omni_gemm_rows_ln_sh_f16x3(_p(x), _p(self.w[lnw]), _p(self.w[lnb]), eps, _p(self._rows_weights(w16key, Nout, 512)),
                                                       _p(self.w[bkey]) if bkey else None, None, _p(out), 1 if out_sh else 0, rows, Nout, act, self._s), "ln+gemm " + w16key)
             return out
         return self._gemm_sh(self._ln_sh(x, lnw, lnb, rows, eps), w16key, bkey, rows, 512, Nout, act=act, out_sh=out_sh)
 
     def _ln_sh(self, x, wk, bk, rows, eps):
         y = torch.empty_like(x)
-        _lib.check(_lib.load().omni_layernorm512_sh(_p(x), _p(self.w[wk]), _p(self.w[bk]), _p(y), rows, ctypes.c_float(eps), self._s), "layernorm")
+        _lib.check(_lib.load().omni_layernorm512_sh(_p(x), _p(self.w[wk]), _p(self.w[bk]), _p(y), rows, eps, self._s), "layernorm")
         return y
 
     def _ln(self, x, wk, bk, rows, eps):
         y = torch.empty_like(x)
-        _lib.check(_lib.load().omni_layernorm512_f32(_p(x), _p(self.w[wk]), _p(self.w[bk]), _p(y), rows, ctypes.c_float(eps), self._s), "layernorm")
+        _lib.check(_lib.load().omni_layernorm512_f32(_p(x), _p(self.w[wk]), _p(self.w[bk]), _p(y), rows, eps, self._s), "layernorm")
         return y
 
     def _up(self, x, M, H, Wd, C, Ho, Wo):
@@ -387,7 +383,7 @@ class Engine:
         d: fp32 [bs*N, P/32, P/32, 32] (the `down` projection of layer4).  Returns the fp32 token matrix [bs*N, 512]."""
         lib = _lib.load()
         dev = d.device
-        self._s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        self._s = _lib.stream_of(d)
         self._bs = bs
         N, P32 = self.npatches, self.patch_size[0] // 32
         M = bs * N
@@ -427,7 +423,7 @@ class Engine:
             parts, S, bkey, res_tok = pending
             tok_sum, tok = new(M, 512), new(M, 512)
             _lib.check(lib.omni_splitk_reduce_ln512(_p(parts), S, _p(self.w[bkey]), _p(res_tok), _p(tok_sum), _p(self.w["enc_norm.w"]), _p(self.w["enc_norm.b"]),
-                                                    ctypes.c_float(1e-6), _p(tok), 0, M, self._s), "reduce+ln")
+                                                    1e-6, _p(tok), 0, M, self._s), "reduce+ln")
         else:
             tok = normed if (sh and normed is not None) else self._ln(tok, "enc_norm.w", "enc_norm.b", M, 1e-6)
         return tok
@@ -438,7 +434,7 @@ class Engine:
         Returns (a, c) planar [bs, N, 1, P, P]: a = relu(pred) (* conf), c = sigmoid(weight) or None."""
         lib = _lib.load()
         dev = patches.device
-        self._s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        self._s = _lib.stream_of(patches)
         N, P = self.npatches, self.patch_size[0]
         M = bs * N
         self._bs = bs
@@ -475,7 +471,7 @@ class Engine:
                 cin = cout
             if lname == "layer1" and not (sh and self.fold_point_feat):                          # ... or as a pass of its own
                 _lib.check((lib.omni_add_period_sh if sh else lib.omni_add_period_f32)(
-                    _p(x), _p(point_feat), ctypes.c_size_t(x.numel()), ctypes.c_size_t(point_feat.numel()), self._s), "add point_feat")
+                    _p(x), _p(point_feat), x.numel(), point_feat.numel(), self._s), "add point_feat")
             feats[lname] = x
         layer1, layer2, layer3, layer4 = (feats[k] for k in ("layer1", "layer2", "layer3", "layer4"))
         # ---- transformer over the N tokens of each panorama (:263-268)
@@ -505,11 +501,11 @@ class Engine:
                 nb = int(lib.omni_up2_heads_scratch_bytes(Mc, P))
                 hs = new((nb + 3) // 4)
                 _lib.check((lib.omni_conv3x3_up2_heads_sh_f16x1 if self._x1 else lib.omni_conv3x3_up2_heads_sh_f16x3)(_p(x), _p(self.w["de_conv4_0.w16"]), _p(self.w["de_conv4_0.b"]), _p(self.w["heads.w16f"]),
-                                                               ctypes.c_float(self.head_bias[0]), ctypes.c_float(self.head_bias[1]), _p(hs), ctypes.c_size_t(nb),
+                                                               self.head_bias[0], self.head_bias[1], _p(hs), nb,
                                                                _p(av[m0:m1]), _p(cv[m0:m1]) if cv is not None else None, Mc, P, 1 if confidence else 0, self._s), "up+conv+heads")
                 continue
             self._up_conv(x, "de_conv4_0", Mc, P2, P2, 32, 32, ACT_RELU, out_f32=True, out=de4[m0:m1])
-            _lib.check(lib.omni_heads_f32(_p(de4[m0:m1]), _p(self.w["heads.w"]), ctypes.c_float(self.head_bias[0]), ctypes.c_float(self.head_bias[1]),
+            _lib.check(lib.omni_heads_f32(_p(de4[m0:m1]), _p(self.w["heads.w"]), self.head_bias[0], self.head_bias[1],
                                           _p(av[m0:m1]), _p(cv[m0:m1]) if cv is not None else None, Mc, P, 1 if confidence else 0, self._s), "heads")
         self.last = {"de_conv4_0": de4, "layer4": layer4}
         return a, c
@@ -539,7 +535,7 @@ class Engine:
         lib = _lib.load()
         P4 = self.patch_size[0] // 4
         out = torch.empty((Mo, P4, P4, 64), dtype=torch.float32, device=xyz.device)
-        s = ctypes.c_void_p(torch.cuda.current_stream(xyz.device).cuda_stream)
+        s = _lib.stream_of(xyz)
         _lib.check(lib.omni_mlp_points_f32(_p(xyz), _p(depth), _p(self.w[name + ".w1"]), _p(self.w[name + ".b1"]),
                                            _p(self.w[name + ".w2"]), _p(self.w[name + ".b2"]), _p(out), Mo, self.npatches,
                                            P4 * P4, s), "mlp_points")

@@ -53,18 +53,13 @@ the pool recomputes each window's winner from x (the first greatest element in s
 adds its at most 4 x 4 taps with constant weights.  The same rules: fp32, no atomics, no host synchronisation, only the gradients
 autograd asks for, channels-last tensors without a copy (the stem's x is planar, its 37-KiB filter bank is transposed every step).
 """
-import ctypes
-
 import torch
 
 from . import _lib
+from ._lib import ptr as _p
 
 ACTS = {"none": 0, "relu": 1}
 _empty = torch.empty          # every buffer of this module is allocated through this name (tests fill them with NaN)
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _nhwc(t):
@@ -131,7 +126,7 @@ def _forward_nhwc(x1, x2, w, bias, res, stride, pad, act):
         st = _lib.stream_of(x1)
         _lib.check(lib.omni_conv2d_split_weights_f16x3(_p(w), _p(w16), Cout, K, st), "conv2d_split_weights")
         _lib.check(lib.omni_conv2d_nhwc_f16x3_ws(_p(x1), _p(x2), _p(w16), _p(bias), _p(res), _p(y), M, H, W, C1, C2, Cout, k, k, stride, pad,
-                                                 ACTS[act], 1, None, ctypes.c_size_t(0), st), "conv2d")
+                                                 ACTS[act], 1, None, 0, st), "conv2d")
     return y
 
 

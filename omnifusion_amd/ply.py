@@ -8,7 +8,6 @@ The rays, the scaling and the 15-byte vertex records (3 x float32 + 3 x uint8, e
 ply.py:303-314) are produced by ONE kernel (csrc/omni_io.hip `pointcloud_kernel`); the host only copies the finished records
 and prepends the text header, instead of the reference's per-batch `.detach().cpu().numpy()` of four full-size tensors.
 """
-import ctypes
 import sys
 
 import numpy as np
@@ -28,7 +27,7 @@ def _records(depth, rgb):
     B, _, H, W = d.shape
     rec = torch.empty((B, H * W, 15), dtype=torch.uint8, device=d.device)
     with torch.cuda.device(d.device):
-        _lib.check(_lib.load().omni_pointcloud_ply_f32(ctypes.c_void_p(d.data_ptr()), ctypes.c_void_p(c.data_ptr()), ctypes.c_void_p(rec.data_ptr()),
+        _lib.check(_lib.load().omni_pointcloud_ply_f32(_lib.ptr(d), _lib.ptr(c), _lib.ptr(rec),
                                                       B, H, W, _lib.stream_of(d)), "pointcloud")
     return rec
 

@@ -46,7 +46,7 @@ def png_info(src):
     """(height, width, bit_depth, colour_type) from the header"""
     data = _bytes_of(src)
     w, h, d, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    _lib.check(_lib.load().omni_png_info(data, ctypes.c_size_t(len(data)), ctypes.byref(w), ctypes.byref(h), ctypes.byref(d), ctypes.byref(c)), "png_info")
+    _lib.check(_lib.load().omni_png_info(data, len(data), ctypes.byref(w), ctypes.byref(h), ctypes.byref(d), ctypes.byref(c)), "png_info")
     return h.value, w.value, d.value, c.value
 
 
@@ -58,7 +58,7 @@ def imread(src, unchanged=False):
         out = np.empty((H, W), np.uint16 if depth == 16 else np.uint8)
     else:
         out = np.empty((H, W, 3), np.uint8)
-    _lib.check(_lib.load().omni_png_decode(data, ctypes.c_size_t(len(data)), out.ctypes.data_as(ctypes.c_void_p), H, W, 1 if unchanged else 0), "png_decode")
+    _lib.check(_lib.load().omni_png_decode(data, len(data), out.ctypes.data_as(ctypes.c_void_p), H, W, 1 if unchanged else 0), "png_decode")
     return out
 
 

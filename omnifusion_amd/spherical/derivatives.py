@@ -8,16 +8,11 @@
 Everything numeric runs in libomnifusion_hip.so (csrc/omni_smoothness.hip); float32 tensors on the device, forward only:
 the differentiable path is supervision.smoothness.depth_smoothness.  There is no CPU path.
 """
-import ctypes
-
 import torch
 
 from .. import _lib
+from .._lib import ptr as _p
 from .cartesian import xi, yi, zeta
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 def _prepare(t, name, channels=None):

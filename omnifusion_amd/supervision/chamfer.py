@@ -18,15 +18,10 @@ gradient; a masked target is never a neighbour.  The gradient is 0 where dist ==
 coordinate of a valid target makes every dist of its item NaN, one of a valid query its own dist; a NaN at a masked point changes nothing.
 An item without a valid target has dist = +inf, idx = -1 and no gradient.
 """
-import ctypes
-
 import torch
 
 from .. import _lib
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+from .._lib import ptr as _p
 
 
 def _workspace(nbytes, device):

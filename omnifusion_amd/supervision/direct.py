@@ -11,15 +11,10 @@ calculate_l1_loss — mirror of :20-26 (the gradient term of the depth objective
 
     loss = calculate_l1_loss(pred, gt, mask)                  # mean_b(sum_b(|gt - pred| * mask) / sum_b(mask)), differentiable w.r.t. pred
 """
-import ctypes
-
 import torch
 
 from .. import _lib
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
+from .._lib import ptr as _p
 
 
 class _BerHu(torch.autograd.Function):
@@ -31,7 +26,7 @@ class _BerHu(torch.autograd.Function):
         ws = torch.empty(lib.omni_berhu_workspace_bytes(B) // 4 + 1, dtype=torch.int32, device=pred.device)
         loss = torch.empty((), dtype=torch.float32, device=pred.device)
         with torch.cuda.device(pred.device):
-            _lib.check(lib.omni_berhu_loss_f32(_p(pred), _p(gt), _p(mask), _p(weights), B, ctypes.c_size_t(per), _p(ws), _p(loss),
+            _lib.check(lib.omni_berhu_loss_f32(_p(pred), _p(gt), _p(mask), _p(weights), B, per, _p(ws), _p(loss),
                                                _lib.stream_of(pred)), "berhu_loss")
         ctx.save_for_backward(pred, gt, mask, weights, ws)
         return loss
@@ -45,7 +40,7 @@ class _BerHu(torch.autograd.Function):
         g = grad_out.contiguous().to(torch.float32)
         grad = torch.empty_like(pred)
         with torch.cuda.device(pred.device):
-            _lib.check(lib.omni_berhu_grad_f32(_p(pred), _p(gt), _p(mask), _p(weights), B, ctypes.c_size_t(per), _p(ws), _p(g), _p(grad),
+            _lib.check(lib.omni_berhu_grad_f32(_p(pred), _p(gt), _p(mask), _p(weights), B, per, _p(ws), _p(g), _p(grad),
                                                _lib.stream_of(pred)), "berhu_grad")
         return grad, None, None, None
 
@@ -103,6 +98,4 @@ def calculate_berhu_loss(pred, gt, mask, weights):
     if pred.shape[0] < 1 or pred.numel() == 0:
         raise ValueError("empty batch")
     f = lambda t: t.contiguous().to(torch.float32)
-    lib = _lib.load()
-    lib.omni_berhu_workspace_bytes.restype = ctypes.c_size_t
     return _BerHu.apply(f(pred), f(gt).detach(), f(mask).detach(), f(weights).detach())

@@ -22,18 +22,13 @@ Masks may be bool, uint8 or float (multiplied in by value); non-contiguous input
 whose mask sum is 0 gives a NaN normal_loss, an item whose mask sum is 0 a NaN grad_loss (0 / 0, as calculate_berhu_loss), with NaN gradients
 for the items concerned.
 """
-import ctypes
-
 import torch
 
 from .. import _lib
+from .._lib import ptr as _p
 from ..spherical.grid import ray_tables
 
 NORMAL, GRADIENT = 1, 2
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 class _GeometryTerms(torch.autograd.Function):

@@ -9,8 +9,6 @@ on the mask as given, [B,1,H,W] or [B,C,H,W] — and averaged over the batch.  E
 (csrc/omni_photometric.hip): one tiled forward kernel that writes no map, a deterministic two-stage sum (the scalar stays on the
 device), and for backward two tiled passes.  gt, mask and weights are constants of the backward, as in calculate_berhu_loss.
 """
-import ctypes
-
 import torch
 
 from .. import _lib

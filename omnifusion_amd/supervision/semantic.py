@@ -14,18 +14,13 @@ Pixel rules: `target == ignore_index` is outside the loss; a neg
 a target that is neither ignored nor in [0, C) — torch raises a device-side assert for it — is dropped from both and counted: pass
 `n_bad=` (a 1-element int64 device tensor) to accumulate the count, or read `last_n_bad(loss)` of a result.
 """
-import ctypes
-
 import torch
 
 from .. import _lib
+from .._lib import ptr as _p
 
 MAX_CLASSES = 64
 _INT_TARGETS = (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8)
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _check(logits, target, n_classes=None):

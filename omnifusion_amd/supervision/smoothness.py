@@ -20,16 +20,11 @@ sum(mask) == 0 gives the reference's 0 / 0 = NaN (and NaN gradients); it is not 
 Kinks, as torch autograd: d|x|/dx = 0 at 0 (every last-column du and last-row dv, by replicate padding), and the gradient of the 2-norm is
 0 where the norm is 0 (the bottom-right pixel).
 """
-import ctypes
-
 import torch
 
 from .. import _lib
+from .._lib import ptr as _p
 from ..spherical.grid import default_sgrid, direction_factors
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _f32(t):

@@ -13,15 +13,10 @@ no atomics: every source pixel re-derives its corners and reads its targets; DES
 for; mask is not differentiable.  Without a grad-requiring input the forward path is the inference one, launch for launch.
 `render_to` (:83-88) is not provided.  Divergences: DESIGN.md §7 (d5, NaN poisoning; d6, depth-0 gradients).
 """
-import ctypes
-
 import torch
 
 from .. import _lib
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+from .._lib import ptr as _p
 
 
 def _check(name, t, ndim=4):

@@ -13,12 +13,9 @@ import math
 import torch
 
 from .. import _lib
+from .._lib import ptr as _p
 
 MODES = {"gaussian": 0, "box": 1}
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def window_weights(kernel_size, std, mode):

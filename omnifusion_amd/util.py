@@ -35,8 +35,6 @@ Chamfer distance — mirror of util.py:201-257 (csrc/omni_chamfer.hip, DESIGN.md
 
 supervision.chamfer has the masked, bidirectional and mean forms and the nearest neighbours themselves.
 """
-import ctypes
-
 import torch
 
 from . import _lib

@@ -13,16 +13,75 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _declared():
+def _header():
     src = open(os.path.join(ROOT, "include", "omnifusion.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(omni_[a-z0-9_]+)\s*\(", src)))
+    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+
+
+def _declared():
+    return sorted(set(re.findall(r"\b(omni_[a-z0-9_]+)\s*\(", _header())))
+
+
+_SCALARS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "long long": ctypes.c_longlong, "int64_t": ctypes.c_int64,
+            "float": ctypes.c_float, "double": ctypes.c_double}
+
+
+def _ctype(c_type, ret=False):
+    """The binding rule of the Python boundary: every pointer and omni_stream_t -> c_void_p, const char* -> c_char_p, scalars -> their
+    exact ctypes type, a void return -> None.  Anything else is a KeyError: an unknown C type fails the test."""
+    t = " ".join(c_type.split())
+    if "*" in t:
+        return ctypes.c_char_p if t.replace(" ", "") == "constchar*" else ctypes.c_void_p
+    if t == "omni_stream_t":
+        return ctypes.c_void_p
+    if ret and t == "void":
+        return None
+    return _SCALARS[t]
+
+
+def _prototypes():
+    """name -> (restype, argtypes) of every `ret omni_name(args);` of the header"""
+    protos = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][A-Za-z0-9_ ]*?[\s*]+)(omni_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _header()):
+        assert name not in protos, f"{name} declared twice"
+        params = [] if args.strip() == "void" else [re.fullmatch(r"(.*?)[A-Za-z_][A-Za-z0-9_]*", a.strip(), flags=re.S) for a in args.split(",")]
+        assert all(params), f"{name}: a parameter without a name in ({args})"
+        protos[name] = (_ctype(ret, ret=True), tuple(_ctype(m.group(1)) for m in params))
+    return protos
+
+
+def test_signature_table_matches_header():
+    """_lib.SIGNATURES against include/omnifusion.h, type by type: same names, same return type, same parameter count, same types in
+    order — and the loaded library carries exactly these as restype / argtypes."""
+    from omnifusion_amd import _lib, build
+    build.build()
+    protos = _prototypes()
+    declared = _declared()
+    assert len(declared) >= 149 and sorted(protos) == declared, set(protos) ^ set(declared)      # the parser missed no prototype
+    assert list(_lib.SIGNATURES) == list(protos)                                                 # header order
+    for name, sig in protos.items():
+        assert _lib.SIGNATURES[name] == sig, f"{name}: table {_lib.SIGNATURES[name]}, header {sig}"
+    assert _lib.EXPORTS == list(_lib.SIGNATURES)
+    L = _lib.load()
+    for name, (restype, argtypes) in protos.items():
+        fn = getattr(L, name)
+        assert fn.restype is restype and tuple(fn.argtypes) == argtypes, name
+    # spot checks of the rule itself, read off the header by hand
+    vp, ci, cf, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
+    assert protos["omni_last_error"] == (ctypes.c_char_p, ())
+    assert protos["omni_get_option"] == (ci, (ctypes.c_char_p, vp))
+    assert protos["omni_geometry_destroy"] == (None, (vp,))
+    assert protos["omni_conv2d_splitk_plan"] == (ci, (ctypes.c_longlong, ci, ci))
+    assert protos["omni_up2_heads_scratch_bytes"] == (sz, (ci, ci))
+    assert protos["omni_layernorm512_sh"] == (ci, (vp, vp, vp, vp, ci, cf, vp))
+    assert protos["omni_semantic_step_f32"] == (ci, (vp, vp, ci, ci, sz, ctypes.c_int64, ci, vp, vp, vp, vp, vp))
+    assert protos["omni_batchnorm_fwd_f32"][1][8:13] == (ctypes.c_longlong, ci, ci, ctypes.c_double, ctypes.c_double)
+    assert protos["omni_png_decode_batch"] == (ci, (vp, vp, vp, ci, ci, ci, ci, ci))
 
 
 def test_header_symbols_exported_and_bound():
     from omnifusion_amd import _lib, build
     build.build()
-    lib = ctypes.CDLL(_lib.LIB_PATH) if False else None      # loading needs torch's HIP runtime first: go through _lib
     L = _lib.load()
     declared = _declared()
     assert len(declared) >= 20
