@@ -390,7 +390,7 @@ __global__ __launch_bounds__(256) void e2p_lds_kernel(E2PArgs a, int tiles_x, in
                 float* ge = gerp + ((size_t)fb_b * a.C + c) * img_plane;
 #pragma unroll
                 for (int k = 0; k < SPT; ++k) {
-                    if (!ok[k] || !(w00[k] == w00[k])) continue;              // outside a ragged tile / NaN sample (q4)
+                    if (!ok[k] || !(w00[k] == w00[k])) continue;              // outside a ragged tile (the weights of the q4 sample are finite: its clipped row coordinate is 0)
                     const float g = srcb[(size_t)c * plane + k * ostep];
                     const int g0 = y0[k] * W + x0[k], g1 = y1[k] * W + x0[k];
                     atomicAdd(ge + g0, g * w00[k]); atomicAdd(ge + g0 + s1[k], g * w01[k]);

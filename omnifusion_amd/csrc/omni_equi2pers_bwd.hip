@@ -20,7 +20,8 @@ __global__ __launch_bounds__(256) void e2p_bwd_kernel(E2PArgs a /* erp = g_erp (
     float ix, iy;
     if (a.ixy) { const float2 c = a.ixy[((size_t)n * a.ph + h) * a.pw + w]; ix = c.x; iy = c.y; }
     else e2p_sample_xy(a, n, h, w, ix, iy);
-    if (!(ix == ix) || !(iy == iy)) return;                       // q4: an odd x odd patch has a NaN centre sample
+    if (!(ix == ix) || !(iy == iy)) return;                       // (never taken: the clip of e2p_sample_xy has already sent the NaN row coordinate of the q4 centre
+                                                                  //  sample to 0, so its gradient goes to row 0, where the forward reads it: the exact transpose)
     const float fx = floorf(ix), fy = floorf(iy);
     const int x0 = (int)fx, y0 = (int)fy;
     const float tx = ix - fx, ty = iy - fy, ex = 1.0f - tx, ey = 1.0f - ty;
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(256) void e2p_sp_walk_kernel(E2PArgs a, int total, 
     const int pp = a.ph * a.pw, n = s / pp;
     const unsigned src = ((unsigned)n << 24) | (unsigned)(s - n * pp);
     const float2 c = a.ixy[s];
-    if (!(c.x == c.x) || !(c.y == c.y)) return;                   // q4: an odd x odd patch has a NaN centre sample
+    if (!(c.x == c.x) || !(c.y == c.y)) return;                   // (never taken, see e2p_bwd_kernel: the table holds the clipped coordinate, the q4 sample scatters into row 0)
     const float fx = floorf(c.x), fy = floorf(c.y);
     const int x0 = (int)fx, y0 = (int)fy;
     const float tx = c.x - fx, ty = c.y - fy, ex = 1.0f - tx, ey = 1.0f - ty;
