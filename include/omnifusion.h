@@ -745,6 +745,31 @@ int omni_stem_conv_bwd_weight_f32(const float* g, const float* x, float* dw, flo
 int omni_maxpool3x3s2_bwd_f32(const float* g, const float* x, float* dx, int M, int H, int W, int C, omni_stream_t stream);
 int omni_upsample_bilinear2x_bwd_f32(const float* g, float* dx, int M, int H, int W, int C, omni_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * The two depth heads in training mode (csrc/omni_heads_bwd.hip): pred and weight_pred of model/spherical_model.py:304-307,
+ * 3x3 convolutions 32 -> 1 with bias, then ReLU, sigmoid and the product.  fp32 FMAs; x contiguous NHWC [M,H,W,32] with ANY H, W >= 1;
+ * w [2][9][32] (pred, then weight_pred: omni_heads_f32's layout); bias [2] in DEVICE memory; every map planar [M,H,W], M.H.W < 2^31 (else
+ * UNSUPPORTED).  Nothing is allocated, nothing synchronises, nothing is read back; no atomics, every sum in a fixed order that depends on
+ * the shapes alone: the same bits on every run, and dx of an item is a function of that item.  Every rejection happens before a launch.
+ * omni_depth_heads_fwd_f32: p = conv(x, w[0]) + bias[0], q = conv(x, w[1]) + bias[1] (taps in (ky, kx, c) order, one fp32 chain each);
+ * out_a = relu(p) . (confidence ? sigmoid(q) : 1), out_c = sigmoid(q) (may be NULL); out_p / out_q receive the pre-activations (each may
+ * be NULL: pass them when a gradient is pending — the backward reads them instead of reading x a second time).
+ * omni_depth_heads_bwd_f32: s = sigmoid(q); gp = grad_a . s . [p > 0], gq = (grad_a . relu(p) + grad_c) . s (1 - s); with confidence = 0
+ * gp = grad_a . [p > 0], gq = grad_c . s (1 - s).  grad_a or grad_c may be NULL (zero), not both; q may be NULL when confidence = 0 and
+ * grad_c is NULL.  dx[m,y,x,c] = sum_tap gp[y-ky+1, x-kx+1] . w[0][tap][c] + gq[...] . w[1][tap][c], taps in (ky, kx) order, a tap
+ * outside the map never read; dw[h][tap][c] = sum over the pixels of g_h[pixel] . x[pixel + tap - 1][c] and dbias[h] = sum g_h: fp32
+ * FMAs over chunks of 16x16 tiles, the chunks' partials [578] added in double in a fixed order, one rounding.  Each of dx [M,H,W,32],
+ * dw [2][9][32], dbias [2] may be NULL (not computed), not all three; x is read for dw / dbias only.
+ * `workspace`: omni_depth_heads_bwd_workspace_bytes(M, H, W) = M.H.W . 8 (rounded up to 16) + nchunk . 578 . 4 bytes (0 outside the scope),
+ * with ntiles = M . ceil(H/16) . ceil(W/16), tpc = max(4, ceil(ntiles / 1024)) and nchunk = ceil(ntiles / tpc); any content, 16-byte
+ * aligned. */
+int omni_depth_heads_fwd_f32(const float* x, const float* w, const float* bias, float* out_a, float* out_c, float* out_p, float* out_q,
+                             int M, int H, int W, int confidence, omni_stream_t stream);
+size_t omni_depth_heads_bwd_workspace_bytes(int M, int H, int W);
+int omni_depth_heads_bwd_f32(const float* grad_a, const float* grad_c, const float* p, const float* q, const float* x, const float* w,
+                             float* dx, float* dw, float* dbias, int M, int H, int W, int confidence, void* workspace, size_t ws_bytes,
+                             omni_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

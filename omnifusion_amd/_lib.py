@@ -179,6 +179,9 @@ omni_stem_conv_bwd_workspace_bytes z i3
 omni_stem_conv_bwd_weight_f32 i p4i3pzp
 omni_maxpool3x3s2_bwd_f32 i p3i4p
 omni_upsample_bilinear2x_bwd_f32 i ppi4p
+omni_depth_heads_fwd_f32 i p7i4p
+omni_depth_heads_bwd_workspace_bytes z i3
+omni_depth_heads_bwd_f32 i p9i4pzp
 """
 
 

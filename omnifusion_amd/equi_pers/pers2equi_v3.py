@@ -93,13 +93,59 @@ def pers2equi(pers_img, fov, nrows, patch_size, erp_size, layer_name=None, layou
     return erp
 
 
+class _Pers2EquiConfFn(torch.autograd.Function):
+    """out = P(pred_w) / den, den = P(conf) + 1e-8 [P(conf) <= 1e-8], P = pers2equi: the forward is the fused kernel; the backward sends
+    g_A = g / den and g_C = -g out / den through ONE omni_pers2equi_bwd at C = 2.  The zero-weight indicator is a constant (the
+    reference detaches it, model/spherical_model.py:310).  den is recomputed from conf: the backward keeps conf and out."""
+
+    @staticmethod
+    def forward(ctx, pred_w, conf, fov, nrows, patch_size, erp_size, layout):
+        ctx.cfg = (fov, nrows, patch_size, erp_size, layout)
+        with torch.no_grad():
+            out = pers2equi_conf(pred_w.detach(), conf.detach(), fov, nrows, patch_size, erp_size, layout)
+        ctx.save_for_backward(conf.detach(), out)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_erp):
+        fov, nrows, patch_size, erp_size, layout = ctx.cfg
+        need_a, need_c = ctx.needs_input_grad[:2]
+        if not (need_a or need_c):
+            return (None,) * 7
+        conf, out = ctx.saved_tensors
+        lib = _lib.load()
+        ph, pw, fov_h, fov_w, H, W = _args(fov, patch_size, erp_size)
+        g = grad_erp.contiguous().float()
+        den = pers2equi(conf, fov, nrows, patch_size, erp_size, None, layout)
+        den = den + 1e-8 * (den <= 1e-8).to(torch.float32)
+        ga = g / den
+        g2 = torch.cat([ga, -(ga * out)], 1)                                   # [B,2,H,W]: (g_A, g_C)
+        B = g2.shape[0]
+        ax = {_lib.LAYOUT_BCHWN: 1, _lib.LAYOUT_BNCHW: 2, _lib.LAYOUT_BNHWC: 4}[layout]      # the channel axis of the patch tensor
+        shape = list(conf.shape)
+        shape[ax] = 2
+        grad_pers = torch.empty(shape, dtype=torch.float32, device=g.device)
+        with torch.cuda.device(g.device):
+            rc = lib.omni_pers2equi_bwd(_lib.ptr(g2), _lib.ptr(grad_pers), _lib.F32, B, 2, ph, pw, H, W, int(nrows), fov_h, fov_w, int(layout),
+                                        _lib.stream_of(g))
+        _lib.check(rc, "pers2equi_conf backward")
+        return (grad_pers.narrow(ax, 0, 1) if need_a else None, grad_pers.narrow(ax, 1, 1) if need_c else None) + (None,) * 5
+
+
 def pers2equi_conf(pred_w, conf, fov, nrows, patch_size, erp_size, layout=_lib.LAYOUT_BCHWN):
     """Fused confidence blend of model/spherical_model.py:307-311:
-    pers2equi(pred_w) / (pers2equi(conf) + 1e-8 * [pers2equi(conf) <= 1e-8]), one kernel."""
+    pers2equi(pred_w) / (pers2equi(conf) + 1e-8 * [pers2equi(conf) <= 1e-8]), one kernel.  Differentiable w.r.t. pred_w and conf
+    (float32): with an input that requires grad and grad enabled the same kernel runs under an autograd.Function (_Pers2EquiConfFn)."""
     _check_input(pred_w, "pred_w", 5)
     _check_input(conf, "conf", 5)
     if pred_w.shape != conf.shape or pred_w.dtype != conf.dtype:
         raise ValueError("pred_w and conf must have the same shape and dtype")
+    if torch.is_grad_enabled() and (pred_w.requires_grad or conf.requires_grad):
+        ph, pw = _args(fov, patch_size, erp_size)[:2]
+        if _patch_dims(pred_w, layout, ph, pw, nrows)[1] != 1:
+            raise ValueError("the confidence blend takes single-channel patch tensors")
+        return _Pers2EquiConfFn.apply(pred_w, conf, fov, nrows, patch_size, erp_size, layout)
     lib = _lib.load()
     ph, pw, fov_h, fov_w, H, W = _args(fov, patch_size, erp_size)
     B, C = _patch_dims(pred_w, layout, ph, pw, nrows)

@@ -1,0 +1,212 @@
+"""spherical_fusion (single pass) for TRAINING — the reference's model/spherical_model.py:190-314 assembled from the differentiable
+operators of omnifusion_amd.ops, so that `loss.backward()` of train_erp_depth.py:260-294 runs on the device:
+
+    from omnifusion_amd.model.trainable import spherical_fusion          # the one import train_erp_depth.py changes
+    net = spherical_fusion(nrows=4, npatches=18, patch_size=(128, 128), fov=(80, 80)).cuda()
+    net.load_state_dict(ckpt)                   # the reference's schema (5-D conv weights), 'module.' prefix optional
+    depth = net(rgb, confidence=True)           # rgb [B,3,H,W] float32 on the GPU -> [B,1,H,W], with a graph behind it
+    loss(depth, gt).backward(); optimiser.step()
+
+Parameters and buffers are exactly `weights.schema(npatches)` — the same keys, order and shapes (convolution weights keep the trailing 1
+of the reference's Conv3d, num_batches_tracked included) — so a checkpoint moves freely between this module, the reference and the
+inference module (model/spherical_model.py), whose load_state_dict takes this one's state_dict() with strict=True.  Constructed in
+training mode; `.eval()` runs the same operators from the running statistics and works under no_grad.
+
+The forward: equi2pers_patches (planar layout) -> ops.StemConv2d-style stem, ops.BatchNorm2d(act="relu"), ops.MaxPool2d -> the ResNet-34
+blocks of ops.conv2d and ops.BatchNorm2d(res=..., act="relu") -> `down` through ops.conv2d, ops.TransformerCascade -> per decoder stage
+ops.UpsampleBilinear2x and ops.conv2d(x2=skip) (the concat is never materialised) -> ops.depth_heads -> pers2equi_conf (pers2equi when
+confidence=False).  The statistics of the reference's BatchNorm3d over [B,C,P,P,N] are those of ops.BatchNorm2d over M = B.N patches.
+
+Run by torch operators with autograd (small; tools/train_bench.py reports their share of a step): the two 1x1 convolutions of mlp_points
+(5 -> 16 -> 64 channels on the reference's [N,5,P/4,P/4] tensor, so the batch statistics and the running-variance correction of its two
+ops.BatchNorm2d are the reference's; written as a product and a sum, whose bits repeat), the two broadcast additions
+`layer1 + point_feat` and `layer4 + tokens`, and the reshapes around the transformer.
+
+Not built: the iterative model, DataParallel / SyncBatchNorm / convert_model, fp16, an image gradient, a hand-written
+optimiser (torch.optim.AdamW steps the parameters), capture of a whole step in a graph.  fp32 CUDA input, one device.
+"""
+import ctypes
+
+import torch
+from torch import nn
+
+from .. import _lib, ops
+from ..equi_pers.equi2pers_v3 import equi2pers_patches, pair, _NPATCH
+from ..equi_pers.pers2equi_v3 import pers2equi, pers2equi_conf
+from ._engine import strip_module_prefix
+
+BN_EPS, BN_MOMENTUM = 1e-5, 0.1
+TOKEN_WIDTH = 512
+
+
+def _bn(c, act="none"):
+    return ops.BatchNorm2d(c, eps=BN_EPS, momentum=BN_MOMENTUM, act=act)
+
+
+class _Conv(nn.Module):
+    """A convolution that holds its weight as the reference's Conv3d does, [Cout,Cin,k,k,1]; forward is ops.conv2d on the 4-D view."""
+
+    def __init__(self, cin, cout, k, stride=1, padding=0, bias=False):
+        super().__init__()
+        self.stride, self.padding = stride, padding
+        self.weight = nn.Parameter(torch.empty(cout, cin, k, k, 1))
+        nn.init.kaiming_normal_(self.weight, mode="fan_out", nonlinearity="relu")
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(cout))
+        else:
+            self.register_parameter("bias", None)
+
+    def forward(self, x, x2=None, res=None):
+        return ops.conv2d(x, self.weight[..., 0], self.bias, x2=x2, res=res, stride=self.stride, padding=self.padding)
+
+
+class _Stem(_Conv):
+    def __init__(self):
+        super().__init__(3, 64, 7, stride=2, padding=3)
+
+    def forward(self, x):
+        return ops.stem_conv2d(x, self.weight[..., 0])
+
+
+class _Head(_Conv):
+    """pred / weight_pred: only the parameters [1,32,3,3,1] and [1]; ops.depth_heads runs the two together"""
+
+    def __init__(self):
+        super().__init__(32, 1, 3, padding=1, bias=True)
+
+
+class _PointConv(nn.Conv2d):
+    """mlp_points' 1x1 convolutions (5 -> 16 -> 64 channels, no bias) as a broadcast product and a sum over the input channels: torch
+    reductions with a fixed order, so the weight gradient has the same bits on every run (a library convolution or GEMM may split its
+    reduction with atomics).  The same parameter [Cout,Cin,1,1] under the same name."""
+
+    def forward(self, x):
+        return (x[:, None] * self.weight[None, :, :, :, :]).sum(2)
+
+
+class _BasicBlock(nn.Module):
+    def __init__(self, cin, cout, stride):
+        super().__init__()
+        self.conv1 = _Conv(cin, cout, 3, stride=stride, padding=1)
+        self.bn1 = _bn(cout, "relu")
+        self.conv2 = _Conv(cout, cout, 3, padding=1)
+        self.bn2 = _bn(cout, "relu")                                           # relu(bn2(.) + identity)
+        if stride != 1 or cin != cout:
+            self.downsample = nn.Sequential(_Conv(cin, cout, 1, stride=stride), _bn(cout))
+
+    def forward(self, x):
+        identity = self.downsample(x) if "downsample" in self._modules else x
+        return self.bn2(self.conv2(self.bn1(self.conv1(x))), res=identity)
+
+
+class _ConvBnReLU(nn.Module):
+    def __init__(self, cin, cout):
+        super().__init__()
+        self.conv = _Conv(cin, cout, 3, padding=1)
+        self.bn = _bn(cout, "relu")
+
+    def forward(self, x, x2=None):
+        return self.bn(self.conv(x, x2=x2))
+
+
+def _layer(cin, cout, blocks, stride):
+    return nn.Sequential(*[_BasicBlock(cin if b == 0 else cout, cout, stride if b == 0 else 1) for b in range(blocks)])
+
+
+class spherical_fusion(nn.Module):
+    def __init__(self, nrows=4, npatches=18, patch_size=(128, 128), fov=(80, 80)):
+        super().__init__()
+        self.nrows, self.npatches, self.patch_size, self.fov = nrows, npatches, patch_size, fov
+        ph, pw = (int(v) for v in pair(patch_size))
+        if ph != pw or 32 * (ph // 32) * (pw // 32) != TOKEN_WIDTH or ph % 32:
+            raise ValueError(f"patch size {(ph, pw)}: the token width is {TOKEN_WIDTH} = 32 channels x (P/32)^2 — the reference network "
+                             f"only exists at patch size 128")
+        if nrows not in _NPATCH:
+            raise ValueError(f"unsupported nrows={nrows!r}: presets are 3, 4, 5, 6")
+        if _NPATCH[nrows] != npatches:
+            raise ValueError(f"npatches does not match nrows: nrows={nrows} means {_NPATCH[nrows]} patches (got npatches={npatches})")
+        self.conv1 = _Stem()
+        self.bn1 = _bn(64, "relu")
+        self.layer1, self.layer2 = _layer(64, 64, 3, 1), _layer(64, 128, 4, 2)
+        self.layer3, self.layer4 = _layer(128, 256, 6, 2), _layer(256, 512, 3, 2)
+        self.down = _Conv(512, 512 // 16, 1, bias=True)
+        self.transformer = ops.TransformerCascade(TOKEN_WIDTH, npatches, depth=6, num_heads=4)      # encoder_norm: eps 1e-6, block norms 1e-5
+        self.de_conv0_0, self.de_conv0_1 = _ConvBnReLU(512, 256), _ConvBnReLU(256 + 256, 128)
+        self.de_conv1_0, self.de_conv1_1 = _ConvBnReLU(128, 128), _ConvBnReLU(128 + 128, 64)
+        self.de_conv2_0, self.de_conv2_1 = _ConvBnReLU(64, 64), _ConvBnReLU(64 + 64, 64)
+        self.de_conv3_0, self.de_conv3_1 = _ConvBnReLU(64, 64), _ConvBnReLU(64 + 64, 32)
+        self.de_conv4_0 = _ConvBnReLU(32, 32)
+        self.pred, self.weight_pred = _Head(), _Head()
+        self.mlp_points = nn.Sequential(
+            _PointConv(5, 16, kernel_size=1, stride=1, padding=0, bias=False), _bn(16, "relu"), nn.Identity(),          # (2, 5: the ReLUs,
+            _PointConv(16, 64, kernel_size=1, stride=1, padding=0, bias=False), _bn(64, "relu"), nn.Identity())        # fused into 1, 4)
+        self._pool, self._up = ops.MaxPool2d(3, 2, 1), ops.UpsampleBilinear2x()
+        cp = (ctypes.c_float * (2 * npatches))()
+        if _lib.load().omni_patch_centers(int(nrows), 0, cp) != _lib.OMNI_OK:
+            raise ValueError(f"unsupported nrows={nrows!r}")
+        self._centers = [float(v) for v in cp]                                 # the patch centres (model/spherical_model.py:244): constants
+        self.__dict__["_points_in"] = {}                                       # device -> mlp_points' input; not a buffer: not in the state dict
+
+    def load_state_dict(self, state_dict, strict=True, assign=False):
+        sd = strip_module_prefix(state_dict)                                   # train_erp_depth.py:307 saves through DataParallel
+        sd = {k: v for k, v in sd.items() if not k.endswith("total_ops") and not k.endswith("total_params")}   # thop residue
+        return super().load_state_dict(sd, strict=strict, assign=assign)
+
+    def _check(self, rgb):
+        if not isinstance(rgb, torch.Tensor) or rgb.dim() != 4 or rgb.shape[1] != 3:
+            raise ValueError("expected an RGB panorama batch [B,3,H,W]")
+        if not rgb.is_cuda:
+            raise ValueError("the model runs on an MI355X only (got a CPU tensor); there is no CPU path")
+        if rgb.dtype != torch.float32:
+            raise ValueError("float32 input expected")
+        if rgb.requires_grad and torch.is_grad_enabled():
+            raise ValueError("rgb requires a gradient, but the image gradient is not built; pass rgb.detach()")
+        dev = self.conv1.weight.device
+        if dev != rgb.device:
+            raise ValueError(f"weights are on {dev}, input on {rgb.device}: one device (move the model with .cuda())")
+
+    def point_input(self, device):
+        """mlp_points' input [N,5,P/4,P/4]: (cx, cy, 1, cx, cy) of each patch, broadcast over the map (model/spherical_model.py:245-250)"""
+        key = str(device)
+        if key not in self._points_in:
+            P4 = int(pair(self.patch_size)[0]) // 4
+            c = torch.tensor(self._centers, dtype=torch.float32).reshape(self.npatches, 2)
+            x = torch.cat([c, torch.ones(self.npatches, 1), c], 1)
+            self._points_in[key] = x[:, :, None, None].repeat(1, 1, P4, P4).to(device)
+        return self._points_in[key]
+
+    def forward(self, rgb, confidence=True):
+        self._check(rgb)
+        bs, _, H, W = rgb.shape
+        with torch.cuda.device(rgb.device):
+            patches = equi2pers_patches(rgb, self.fov, self.nrows, self.patch_size, layout=_lib.LAYOUT_BNCHW)              # :243
+            point_feat = self.mlp_points(self.point_input(rgb.device))                                                    # :250-251
+            a, c = self.network(patches, point_feat, confidence)                                                          # :254-306
+            P = tuple(int(v) for v in pair(self.patch_size))
+            if confidence:                                                                                                # :307-311
+                return pers2equi_conf(a, c, self.fov, self.nrows, P, (H, W), layout=_lib.LAYOUT_BNCHW)
+            return pers2equi(a, self.fov, self.nrows, P, (H, W), None, layout=_lib.LAYOUT_BNCHW)                          # :313
+
+    def network(self, patches, point_feat, confidence=True):
+        """planar patches [bs,N,3,P,P], point_feat [N,64,P/4,P/4] -> (pred . conf, conf) planes [bs,N,1,P,P] ((pred, None) without
+        confidence): the part of forward between the two resamplers"""
+        bs, N, _, P, _ = patches.shape
+        M = bs * N
+        conv1 = self.bn1(self.conv1(patches.reshape(M, 3, P, P)))                                                         # :254
+        layer1 = self.layer1(self._pool(conv1))                                                                           # :255-257
+        pf = point_feat.contiguous(memory_format=torch.channels_last)
+        layer1 = (layer1.reshape(bs, N, *layer1.shape[1:]) + pf[None]).reshape(layer1.shape)                              # :258
+        layer2 = self.layer2(layer1)
+        layer3 = self.layer3(layer2)
+        layer4 = self.layer4(layer3)
+        tok = self.down(layer4).reshape(bs, N, TOKEN_WIDTH)                    # token element = c . 16 + h . 4 + w       # :263-264
+        tok = self.transformer(tok)                                                                                       # :266
+        layer4 = layer4 + tok.reshape(M, TOKEN_WIDTH, 1, 1)                                                               # :267-268
+        x = self.de_conv0_1(self.de_conv0_0(self._up(layer4)), x2=layer3)                                                 # :271-276
+        x = self.de_conv1_1(self.de_conv1_0(self._up(x)), x2=layer2)                                                      # :279-283
+        x = self.de_conv2_1(self.de_conv2_0(self._up(x)), x2=layer1)                                                      # :286-290
+        x = self.de_conv3_1(self.de_conv3_0(self._up(x)), x2=conv1)                                                       # :293-297
+        x = self.de_conv4_0(self._up(x))                                                                                  # :300-302
+        a, c = ops.depth_heads(x, self.pred.weight[..., 0], self.pred.bias, self.weight_pred.weight[..., 0], self.weight_pred.bias,
+                               confidence=confidence)                                                                     # :304-307
+        return a.reshape(bs, N, 1, P, P), c.reshape(bs, N, 1, P, P) if c is not None else None

@@ -52,6 +52,16 @@ rejected: the image gradient is not built.  max_pool2d and upsample_bilinear2x a
 the pool recomputes each window's winner from x (the first greatest element in scan order, torch's rule; no index map), the up-sampling
 adds its at most 4 x 4 taps with constant weights.  The same rules: fp32, no atomics, no host synchronisation, only the gradients
 autograd asks for, channels-last tensors without a copy (the stem's x is planar, its 37-KiB filter bank is transposed every step).
+
+The two depth heads behind the decoder (csrc/omni_heads_bwd.hip):
+
+    a, c = depth_heads(x, w_pred, b_pred, w_conf, b_conf, *, confidence=True)   # x [M,32,H,W]; w_* [1,32,3,3]; b_* [1]; a, c [M,1,H,W]
+    DepthHeads()                                              # holds .pred and .weight_pred as nn.Conv2d(32, 1, 3, padding=1)
+
+a = relu(pred(x)) . sigmoid(weight_pred(x)), c = sigmoid(weight_pred(x)); confidence=False returns (relu(pred(x)), None).  Any H, W; the
+biases stay on the device (nothing is read back, the operator can be captured in a graph).  Differentiable w.r.t. x, both weights and
+both biases: fp32 FMAs, the weight gradient as per-chunk partial sums added in double in a fixed order.  This backward DOES keep two
+planes of its forward, the pre-activations (8 B per pixel): recomputing them would read the 128 B per pixel of x a second time.
 """
 import torch
 
@@ -803,6 +813,104 @@ def upsample_bilinear2x(x):
 class UpsampleBilinear2x(torch.nn.Module):
     def forward(self, x):
         return upsample_bilinear2x(x)
+
+
+# ------------------------------------------------------------------------------------------------ the depth heads
+HEADS_C = 32
+
+
+def _check_heads_args(x, w_pred, b_pred, w_conf, b_conf):
+    """Every rejection of depth_heads, raised before anything is launched."""
+    _check_f32_dev((("x", x), ("w_pred", w_pred), ("b_pred", b_pred), ("w_conf", w_conf), ("b_conf", b_conf)))
+    if len({t.device for t in (x, w_pred, b_pred, w_conf, b_conf)}) != 1:
+        raise ValueError("depth_heads: x, the weights and the biases must be on one device")
+    if x.dim() != 4 or x.numel() == 0 or x.shape[1] != HEADS_C:
+        raise ValueError(f"depth_heads: x must be a non-empty [M,{HEADS_C},H,W] tensor (got {tuple(x.shape)})")
+    for t, name in ((w_pred, "w_pred"), (w_conf, "w_conf")):
+        if tuple(t.shape) != (1, HEADS_C, 3, 3):
+            raise ValueError(f"depth_heads: {name} must be [1,{HEADS_C},3,3]: a 3x3 convolution from {HEADS_C} channels to 1 with padding 1 "
+                             f"is the only geometry built (got {tuple(t.shape)})")
+    for t, name in ((b_pred, "b_pred"), (b_conf, "b_conf")):
+        if tuple(t.shape) != (1,):
+            raise ValueError(f"depth_heads: {name} must be [1] (got {tuple(t.shape)})")
+    if x.shape[0] * x.shape[2] * x.shape[3] >= 1 << 31:
+        raise ValueError(f"depth_heads: x of shape {tuple(x.shape)} has 2^31 pixels or more")
+
+
+class _DepthHeads(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w_pred, b_pred, w_conf, b_conf, confidence):
+        lib = _lib.load()
+        xn = _nhwc(x)
+        M, H, W, _ = xn.shape
+        dev = xn.device
+        new = lambda shape: _empty(shape, dtype=torch.float32, device=dev)
+        w, bias = new((2, 3, 3, HEADS_C)), new((2,))                          # [2][9][32] and the two biases, packed on the device (2.3 KB)
+        w[0:1].copy_(w_pred.detach().permute(0, 2, 3, 1)); w[1:2].copy_(w_conf.detach().permute(0, 2, 3, 1))
+        bias[0:1].copy_(b_pred.detach()); bias[1:2].copy_(b_conf.detach())
+        pending = any(ctx.needs_input_grad[:5])
+        a, c = new((M, 1, H, W)), new((M, 1, H, W)) if confidence else None
+        p, q = (new((M, H, W)), new((M, H, W))) if pending else (None, None)
+        with torch.cuda.device(dev):
+            _lib.check(lib.omni_depth_heads_fwd_f32(_p(xn), _p(w), _p(bias), _p(a), _p(c), _p(p), _p(q), M, H, W, int(confidence),
+                                                    _lib.stream_of(xn)), "depth_heads")
+        ctx.confidence = confidence
+        ctx.set_materialize_grads(False)
+        if pending:
+            ctx.save_for_backward(xn, w, p, q)                                 # p and q are kept: 8 B per pixel against 128 B of x
+        return (a, c) if confidence else a
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_a, grad_c=None):
+        need = ctx.needs_input_grad
+        conf = ctx.confidence
+        need_x, need_w, need_b = need[0], need[1] or (conf and need[3]), need[2] or (conf and need[4])
+        if (grad_a is None and grad_c is None) or not (need_x or need_w or need_b):
+            return (None,) * 6
+        lib = _lib.load()
+        xn, w, p, q = ctx.saved_tensors
+        M, H, W, _ = xn.shape
+        dev = xn.device
+        new = lambda shape: _empty(shape, dtype=torch.float32, device=dev)
+        ga = grad_a.to(torch.float32).contiguous() if grad_a is not None else None
+        gc = grad_c.to(torch.float32).contiguous() if grad_c is not None else None
+        nbytes = lib.omni_depth_heads_bwd_workspace_bytes(M, H, W)
+        if nbytes == 0:
+            raise ValueError(f"depth_heads backward: x of shape {(M, HEADS_C, H, W)} is outside the operator's scope")
+        ws = new((nbytes // 4,))
+        dx = new((M, H, W, HEADS_C)) if need_x else None
+        dw = new((2, 3, 3, HEADS_C)) if need_w else None
+        db = new((2,)) if need_b else None
+        with torch.cuda.device(dev):
+            _lib.check(lib.omni_depth_heads_bwd_f32(_p(ga), _p(gc), _p(p), _p(q), _p(xn), _p(w), _p(dx), _p(dw), _p(db), M, H, W, int(conf),
+                                                    _p(ws), nbytes, _lib.stream_of(xn)), "depth_heads_bwd")
+        live = conf or gc is not None                                          # without the product and without grad_c nothing reaches weight_pred
+        return (_nchw(dx), dw[0:1].permute(0, 3, 1, 2) if need[1] else None, db[0:1] if need[2] else None,
+                dw[1:2].permute(0, 3, 1, 2) if need[3] and live else None, db[1:2] if need[4] and live else None, None)
+
+
+def depth_heads(x, w_pred, b_pred, w_conf, b_conf, *, confidence=True):
+    """The two heads of spherical_fusion: p = conv3x3(x, w_pred) + b_pred, q = conv3x3(x, w_conf) + b_conf (padding 1) on x [M,32,H,W], any
+    H, W; returns (a, c) [M,1,H,W] with a = relu(p) . sigmoid(q), c = sigmoid(q), or (relu(p), None) with confidence=False.
+    Differentiable w.r.t. x, both weights [1,32,3,3] and both biases [1], which stay on the device."""
+    _check_heads_args(x, w_pred, b_pred, w_conf, b_conf)
+    if confidence:
+        return _DepthHeads.apply(x, w_pred, b_pred, w_conf, b_conf, True)
+    return _DepthHeads.apply(x, w_pred, b_pred, w_conf, b_conf, False), None
+
+
+class DepthHeads(torch.nn.Module):
+    """The heads under the reference's parameter names: .pred and .weight_pred, each an nn.Conv2d(32, 1, 3, padding=1) that holds the
+    parameters; forward(x, confidence=True) is depth_heads."""
+
+    def __init__(self):
+        super().__init__()
+        self.pred = torch.nn.Conv2d(HEADS_C, 1, 3, padding=1)
+        self.weight_pred = torch.nn.Conv2d(HEADS_C, 1, 3, padding=1)
+
+    def forward(self, x, confidence=True):
+        return depth_heads(x, self.pred.weight, self.pred.bias, self.weight_pred.weight, self.weight_pred.bias, confidence=confidence)
 
 
 def _conv_in_scope(m):
