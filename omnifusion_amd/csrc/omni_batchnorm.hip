@@ -13,12 +13,12 @@
 // Sums: every thread adds its rows in order, in double (x is fp32, so x . x is exact there: a channel whose mean is large against its
 // spread keeps its variance, which fp32 sums of x and x^2 do not).  The row lanes of a wave are added with the butterfly of omni_reduce.h
 // stopped at offset QW (lanes that differ in a bit >= QW hold the same quad), the four waves as (w0 + w1) + (w2 + w3): block_sum's order,
-// spelled out here because block_sum reduces all 64 lanes.  The finish kernels add a channel's partials thread t taking slabs t, t + 256,
-// ... in order, then block_sum.  No atomics, nothing allocated, nothing synchronised, nothing read back: the same bits on every run.
+// spelled out here because block_sum reduces all 64 lanes.  The finish kernels add a channel's slab partials by the column finish of
+// omni_partials.h.  No atomics, nothing allocated, nothing synchronised, nothing read back: the same bits on every run.
 #include <cmath>
 
 #include "omni_internal.h"
-#include "omni_reduce.h"
+#include "omni_partials.h"
 
 namespace {
 
@@ -40,14 +40,7 @@ bool bn_plan(long long rows, int C, BnPlan& p)
     while (p.qw < c4 && p.qw < 64) { p.qw <<= 1; ++p.qshift; }
     p.rl = 256 / p.qw;
     p.ncol = (c4 + p.qw - 1) / p.qw;
-    const long long per = (rows + BN_MAX_SLABS - 1) / BN_MAX_SLABS;
-    long long iters = (per + p.rl - 1) / p.rl;
-    if (iters < BN_MIN_ITERS) iters = BN_MIN_ITERS;
-    const long long slab = iters * p.rl;
-    if (slab >= (1ll << 31)) return false;
-    p.slab = (int)slab;
-    p.nslab = (int)((rows + slab - 1) / slab);
-    return true;
+    return partials_plan(rows, p.rl, BN_MIN_ITERS, BN_MAX_SLABS, p.slab, p.nslab);
 }
 
 size_t bn_part_bytes(const BnPlan& p, int C) { return (size_t)p.nslab * 2 * C * sizeof(double); }
@@ -106,12 +99,8 @@ __global__ __launch_bounds__(256) void bn_stats_finish_kernel(const double* __re
 {
     __shared__ double red[2][4];
     const int t = threadIdx.x, c = blockIdx.x;
-    double v[2] = {0.0, 0.0};
-    for (int b = t; b < nslab; b += 256) {
-        v[0] += part[(size_t)b * 2 * C + c];
-        v[1] += part[(size_t)b * 2 * C + C + c];
-    }
-    block_sum<2>(v, red);
+    double v[2];
+    column_sums<2>(part + c, nslab, (size_t)2 * C, C, v, red);
     if (t == 0) {
         const double mean = v[0] / n;
         double var = v[1] / n - mean * mean;
@@ -213,12 +202,8 @@ __global__ __launch_bounds__(256) void bn_bwd_finish_kernel(const double* __rest
 {
     __shared__ double red[2][4];
     const int t = threadIdx.x, c = blockIdx.x;
-    double v[2] = {0.0, 0.0};
-    for (int b = t; b < nslab; b += 256) {
-        v[0] += part[(size_t)b * 2 * C + c];
-        v[1] += part[(size_t)b * 2 * C + C + c];
-    }
-    block_sum<2>(v, red);
+    double v[2];
+    column_sums<2>(part + c, nslab, (size_t)2 * C, C, v, red);
     if (t == 0) {
         sums[c] = (float)v[0];
         sums[C + c] = (float)v[1];

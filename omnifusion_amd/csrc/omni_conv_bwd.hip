@@ -13,14 +13,14 @@
 // BEFORE it is split (in the loaders of both kernels) and the accumulator by 1 / scale in the epilogue: both are powers of two, so the scaling
 // itself is exact and grad_out . 2^n gives every gradient . 2^n bit for bit.
 //
-// Determinism: no floating-point atomics.  The bias sums are two fixed-order stages (8 x 8 rows per block, then omni_reduce.h's block sum over
-// the blocks); wgrad cuts the rows into chunks of `conv_wgrad_rows` rows (option; 0 = the library's plan), every chunk writes raw partial sums
+// Determinism: no floating-point atomics.  The bias sums are two fixed-order stages (8 x 8 rows per block, then the column finish of
+// omni_partials.h over the blocks); wgrad cuts the rows into chunks of `conv_wgrad_rows` rows (option; 0 = the library's plan), every chunk writes raw partial sums
 // and a second pass adds them in chunk order: a result is a function of the inputs and the chunk length only.
 //
 // A tap that does not apply (outside the image; at stride 2 the wrong parity) is never read: its lanes get an out-of-range buffer offset,
 // for which the buffer unit returns zeros — a NaN in dZ reaches exactly the elements whose sum contains it.
 #include "omni_internal.h"
-#include "omni_reduce.h"
+#include "omni_partials.h"
 
 namespace {
 
@@ -94,8 +94,8 @@ __global__ __launch_bounds__(256) void conv_bwd_epilogue_kernel(const float* __r
     if (t == 0) pmax[blockIdx.x] = max(max(mred[0], mred[1]), max(mred[2], mred[3]));
 }
 
-// Stage 2: block j < Cout adds channel j's partial sums over the blocks (thread t takes blocks t, t + 256, ... in order, then block_sum), in
-// double, rounded once; block Cout takes the maximum and writes scale[0] = 2^s, scale[1] = 2^-s with s = 8 - floor(log2 max|dZ|) clamped to
+// Stage 2: block j < Cout adds channel j's partial sums over the blocks (the column finish, N = 1 over float partials), in double, rounded
+// once; block Cout takes the maximum and writes scale[0] = 2^s, scale[1] = 2^-s with s = 8 - floor(log2 max|dZ|) clamped to
 // [-126, 126] (both stay normal numbers).  max = 0 or not finite: s = 0.
 __global__ __launch_bounds__(256) void conv_bwd_epilogue_finish_kernel(const float* __restrict__ part, const int* __restrict__ pmax, int nblk,
                                                                        int Cout, float* __restrict__ grad_bias, float* __restrict__ scale)
@@ -104,9 +104,8 @@ __global__ __launch_bounds__(256) void conv_bwd_epilogue_finish_kernel(const flo
     __shared__ int mred[4];
     const int t = threadIdx.x;
     if ((int)blockIdx.x < Cout) {
-        double v[1] = {0.0};
-        for (int b = t; b < nblk; b += 256) v[0] += (double)part[(size_t)b * Cout + blockIdx.x];
-        block_sum<1>(v, red);
+        double v[1];
+        column_sums<1>(part + blockIdx.x, nblk, Cout, 0, v, red);
         if (t == 0) grad_bias[blockIdx.x] = (float)v[0];
     } else {
         int mx = 0;

@@ -20,10 +20,10 @@
 //          thread (quad, pixel group) reads 16 bytes of x per pixel and feeds 72 FMAs against the 9 (gp, gq) neighbours in LDS, 72
 //          accumulators in registers.  At the end the 8 pixel groups of a wave are added by xor-shuffles (8, 16, 32), the four waves in
 //          order through LDS, and the block writes ONE partial [578] (dw [2][9][32], then db [2]).  The finish kernel adds the chunks'
-//          partials in double, lane l taking chunks l, l + 16, ... in order and the sixteen lanes added in order (the stem's weight
-//          gradient, omni_stem_conv.hip).  No atomics, nothing synchronised, the same bits on every run; dx of an item depends on that
-//          item alone.
+//          partials in double by the chunk finish of omni_partials.h, as the stem's does.  No atomics, nothing
+//          synchronised, the same bits on every run; dx of an item depends on that item alone.
 #include "omni_internal.h"
+#include "omni_partials.h"
 
 namespace {
 
@@ -46,10 +46,7 @@ bool heads_plan(int M, int H, int W, HeadsPlan& p)
     if (p.n >= (1ll << 31)) return false;                              // (int pixel and tile indices)
     p.ty = (H + DH_T - 1) / DH_T; p.tx = (W + DH_T - 1) / DH_T;
     p.ntiles = (int)((long long)M * p.ty * p.tx);                      // <= n
-    p.tpc = (p.ntiles + DH_MAX_CHUNKS - 1) / DH_MAX_CHUNKS;
-    if (p.tpc < DH_MIN_TILES) p.tpc = DH_MIN_TILES;
-    p.nchunk = (p.ntiles + p.tpc - 1) / p.tpc;
-    return true;
+    return partials_plan(p.ntiles, 1, DH_MIN_TILES, DH_MAX_CHUNKS, p.tpc, p.nchunk);
 }
 
 size_t heads_gpq_bytes(const HeadsPlan& p) { return ((size_t)p.n * 2 * sizeof(float) + 15) / 16 * 16; }
@@ -262,23 +259,7 @@ __global__ __launch_bounds__(256) void dheads_wgrad_kernel(const f2v* __restrict
 __global__ __launch_bounds__(256) void dheads_wgrad_finish_kernel(const float* __restrict__ part, int nchunk, float* __restrict__ dw,
                                                                   float* __restrict__ db)
 {
-    __shared__ double red[16][16];
-    const int t = threadIdx.x, e = t & 15, lane = t >> 4;
-    const int idx = blockIdx.x * 16 + e;
-    double s = 0.0;
-    if (idx < DH_PART) {
-#pragma unroll 4
-        for (int b = lane; b < nchunk; b += 16) s += (double)part[(size_t)b * DH_PART + idx];
-    }
-    red[lane][e] = s;
-    __syncthreads();
-    if (t < 16 && idx < DH_PART) {
-        double v = red[0][t];
-#pragma unroll
-        for (int l = 1; l < 16; ++l) v += red[l][t];
-        if (idx < DH_NW) { if (dw) dw[idx] = (float)v; }
-        else if (db) db[idx - DH_NW] = (float)v;
-    }
+    chunk_sums<DH_PART, DH_NW>(part, nchunk, dw, db);
 }
 
 }  // namespace

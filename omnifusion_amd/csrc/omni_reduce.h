@@ -3,7 +3,7 @@
 // Wave level: the xor butterfly over the 64 lanes, offsets 32, 16, ..., 1, operand order v = op(v, shuffled); every lane ends with the result.
 // Block level (256 threads = 4 waves): lane 0 of each wave stores its wave's value, one barrier, then (r0 + r1) + (r2 + r3) in every thread.
 // The bits of a floating-point sum depend on exactly this order (the library is built with -ffp-contract=off), so a kernel that reduces by
-// other means says why.
+// other means says why.  The order ACROSS blocks (partials per slab or chunk, added by a finish kernel) is stated in omni_partials.h.
 //
 // The kernels of the network and the resamplers (omni_net, omni_conv_sh, omni_gemm_rows, omni_spgather, omni_e2p_tables, omni_p2e_tables, the
 // max passes of omni_dibr and omni_freeview_bwd) and block_reduce below still spell the same butterfly out.  Their machine code is pinned

@@ -18,9 +18,10 @@
 // contiguous bytes of g (each address shared by four lanes) and the four tap groups four patch addresses (broadcast): no bank conflicts.
 // Taps 147 .. 159 do not exist: their threads read patch offset 0 and drop the result, except that the thread group kg = 15 (no real tap
 // at all) multiplies by 1 in its first row and so sums g itself: the bias gradient, out of the same pass.
-// The block's partial sums go to the workspace; the finish kernel adds the chunks' partials in double, thread lane l taking chunks l,
-// l + 16, ... in order and the sixteen lanes added in order.  No atomics, nothing synchronised, the same bits on every run.
+// The block's partial sums go to the workspace; the finish kernel adds the chunks' partials in double by the chunk finish of
+// omni_partials.h.  No atomics, nothing synchronised, the same bits on every run.
 #include "omni_internal.h"
+#include "omni_partials.h"
 
 namespace {
 
@@ -46,10 +47,7 @@ bool stem_plan(int M, int H, int W, StemPlan& p)
     const long long nt = (long long)M * p.ty * p.tx;
     if (nt > 0x7fffffffll - (1 << 22)) return false;                   // (int tile indices, stepped by a chunk of up to 2^21 tiles)
     p.ntiles = (int)nt;
-    p.tpc = (p.ntiles + ST_MAX_CHUNKS - 1) / ST_MAX_CHUNKS;
-    if (p.tpc < ST_MIN_TILES) p.tpc = ST_MIN_TILES;
-    p.nchunk = (p.ntiles + p.tpc - 1) / p.tpc;
-    return true;
+    return partials_plan(p.ntiles, 1, ST_MIN_TILES, ST_MAX_CHUNKS, p.tpc, p.nchunk);
 }
 
 size_t stem_ws_bytes(const StemPlan& p) { return (size_t)p.nchunk * ST_PART * sizeof(float); }
@@ -177,21 +175,7 @@ __global__ __launch_bounds__(256) void stem_conv_wgrad_kernel(const float* __res
 __global__ __launch_bounds__(256) void stem_conv_wgrad_finish_kernel(const float* __restrict__ part, int nchunk, float* __restrict__ dw,
                                                                      float* __restrict__ dbias)
 {
-    __shared__ double red[16][16];
-    const int t = threadIdx.x, e = t & 15, lane = t >> 4;
-    const int idx = blockIdx.x * 16 + e;
-    double s = 0.0;
-#pragma unroll 4
-    for (int b = lane; b < nchunk; b += 16) s += (double)part[(size_t)b * ST_PART + idx];
-    red[lane][e] = s;
-    __syncthreads();
-    if (t < 16) {
-        double v = red[0][t];
-#pragma unroll
-        for (int l = 1; l < 16; ++l) v += red[l][t];
-        if (idx < ST_K * ST_CO) { if (dw) dw[idx] = (float)v; }
-        else if (dbias) dbias[idx - ST_K * ST_CO] = (float)v;
-    }
+    chunk_sums<ST_PART, ST_K * ST_CO>(part, nchunk, dw, dbias);
 }
 
 }  // namespace

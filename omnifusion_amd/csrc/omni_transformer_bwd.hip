@@ -8,13 +8,13 @@
 // Sums.  Within a row of a layer norm: every lane adds its quads in ascending order, pairs first ((x + y) + (z + w)), then the butterfly of
 // omni_reduce.h — layernorm512_kernel's order, so that C = 512 gives its bits.  dgamma / dbeta: a thread owns a channel quad and adds the
 // rows of its slab in ascending order in double (no lane ever adds another lane's value), the finish kernel adds a channel's slab partials
-// thread t taking slabs t, t + 256, ... in order, then block_sum; one rounding to fp32.  Attention: the softmax sums are the forward's wave
+// by the column finish of omni_partials.h; one rounding to fp32.  Attention: the softmax sums are the forward's wave
 // sums; delta_i, dq_i (over the keys j) and dk_j, dv_j (over the queries i) are added serially in ascending index order.  Nothing is
 // allocated, nothing synchronises, nothing is read back, no read-modify-write of global memory: the same bits on every run.
 #include <cmath>
 
 #include "omni_internal.h"
-#include "omni_reduce.h"
+#include "omni_partials.h"
 
 namespace {
 
@@ -30,11 +30,7 @@ struct LnPlan { int slab, nslab; };
 bool ln_plan(long long rows, int C, LnPlan& p)
 {
     if (rows <= 0 || rows > 0x7fffffffll - 1024 || C < 4 || C > LN_MAX_C || C % 4) return false;
-    long long slab = (rows + LN_MAX_SLABS - 1) / LN_MAX_SLABS;
-    if (slab < LN_SLAB_ROWS) slab = LN_SLAB_ROWS;
-    p.slab = (int)slab;
-    p.nslab = (int)((rows + slab - 1) / slab);
-    return true;
+    return partials_plan(rows, 1, LN_SLAB_ROWS, LN_MAX_SLABS, p.slab, p.nslab);
 }
 
 size_t ln_part_bytes(const LnPlan& p, int C) { return (size_t)p.nslab * 2 * C * sizeof(double); }
@@ -152,18 +148,14 @@ __global__ __launch_bounds__(256) void ln_bwd_reduce_kernel(const float* __restr
     for (int e = 0; e < 4; ++e) { p0[e] = s[e]; p0[C + e] = sx[e]; }
 }
 
-// Block c: channel c; thread t adds the slabs t, t + 256, ... in order, then block_sum; rounded once.
+// Block c: channel c; the column finish over the slab partials, rounded once.
 __global__ __launch_bounds__(256) void ln_bwd_finish_kernel(const double* __restrict__ part, int nslab, int C, float* __restrict__ dgamma,
                                                             float* __restrict__ dbeta)
 {
     __shared__ double red[2][4];
     const int t = threadIdx.x, c = blockIdx.x;
-    double v[2] = {0.0, 0.0};
-    for (int b = t; b < nslab; b += 256) {
-        v[0] += part[(size_t)b * 2 * C + c];
-        v[1] += part[(size_t)b * 2 * C + C + c];
-    }
-    block_sum<2>(v, red);
+    double v[2];
+    column_sums<2>(part + c, nslab, (size_t)2 * C, C, v, red);
     if (t == 0) {
         if (dbeta) dbeta[c] = (float)v[0];
         if (dgamma) dgamma[c] = (float)v[1];

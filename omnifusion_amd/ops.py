@@ -81,15 +81,31 @@ def _nchw(t):
     return None if t is None else t.permute(0, 3, 1, 2)
 
 
-def _check_args(x, weight, bias, x2, res, stride, padding, act):
-    """Every rejection of conv2d, raised before anything is launched.  Returns (k, Ho, Wo)."""
-    for t, name, opt in ((x, "x", False), (weight, "weight", False), (bias, "bias", True), (x2, "x2", True), (res, "res", True)):
-        if t is None and opt:
+def _new(shape, dev):
+    return _empty(shape, dtype=torch.float32, device=dev)
+
+
+def _workspace(query, who, *shape, dev):
+    """-> (the workspace `query(*shape)` asks for, its bytes); `who` opens the rejection of a shape outside the library's plans"""
+    nbytes = query(*shape)
+    if nbytes == 0:
+        raise ValueError(f"{who} outside the operator's scope")
+    return _new((nbytes // 4,), dev), nbytes
+
+
+def _check_f32_dev(named, optional=()):
+    for name, t in named:
+        if t is None and name in optional:
             continue
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
             raise ValueError(f"{name} must be a tensor on an MI355X device; there is no CPU path")
         if t.dtype != torch.float32:
             raise ValueError(f"{name} must be float32 (got {t.dtype})")
+
+
+def _check_args(x, weight, bias, x2, res, stride, padding, act):
+    """Every rejection of conv2d, raised before anything is launched.  Returns (k, Ho, Wo)."""
+    _check_f32_dev((("x", x), ("weight", weight), ("bias", bias), ("x2", x2), ("res", res)), optional=("bias", "x2", "res"))
     if act not in ACTS:
         if act == "gelu":
             raise ValueError("act='gelu' is not supported: the convolution's backward covers 'none' and 'relu' only (the forward does not "
@@ -148,10 +164,7 @@ def _backward_nhwc(g, y, x1, x2, w, stride, pad, act, need_x1, need_x2, need_w):
     Cout, k = w.shape[0], w.shape[1]
     dev = x1.device
     shape = (M, H, W, C1, C2, Cout, k, k, stride, pad)
-    nbytes = lib.omni_conv2d_bwd_workspace_bytes(*shape)
-    if nbytes == 0:
-        raise ValueError(f"conv2d backward: shape {shape} is outside the operator's scope")
-    ws = _empty(nbytes // 4, dtype=torch.float32, device=dev)
+    ws, nbytes = _workspace(lib.omni_conv2d_bwd_workspace_bytes, f"conv2d backward: shape {shape} is", *shape, dev=dev)
     scale = _empty(2, dtype=torch.float32, device=dev)
     dbias = _empty(Cout, dtype=torch.float32, device=dev)
     relu = act == "relu"
@@ -222,14 +235,8 @@ class Conv2d(torch.nn.Conv2d):
 # ------------------------------------------------------------------------------------------------ batch normalisation
 def _check_bn_args(x, weight, bias, running_mean, running_var, res, training, momentum, eps, act):
     """Every rejection of batch_norm, raised before anything is launched."""
-    for t, name, opt in ((x, "x", False), (weight, "weight", True), (bias, "bias", True), (running_mean, "running_mean", True),
-                         (running_var, "running_var", True), (res, "res", True)):
-        if t is None and opt:
-            continue
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError(f"{name} must be a tensor on an MI355X device; there is no CPU path")
-        if t.dtype != torch.float32:
-            raise ValueError(f"{name} must be float32 (got {t.dtype})")
+    _check_f32_dev((("x", x), ("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var), ("res", res)),
+                   optional=("weight", "bias", "running_mean", "running_var", "res"))
     if act not in ACTS:
         if act == "gelu":
             raise ValueError("act='gelu' is not supported: the batch normalisation's backward covers 'none' and 'relu' only (the forward "
@@ -263,10 +270,7 @@ def _check_bn_args(x, weight, bias, running_mean, running_var, res, training, mo
 
 
 def _bn_workspace(lib, rows, C, dev):
-    nbytes = lib.omni_batchnorm_workspace_bytes(rows, C)
-    if nbytes == 0:
-        raise ValueError(f"batch_norm: {rows} rows of {C} channels are outside the operator's scope")
-    return _empty(nbytes // 4, dtype=torch.float32, device=dev), nbytes
+    return _workspace(lib.omni_batchnorm_workspace_bytes, f"batch_norm: {rows} rows of {C} channels are", rows, C, dev=dev)
 
 
 class _BatchNorm(torch.autograd.Function):
@@ -300,10 +304,9 @@ class _BatchNorm(torch.autograd.Function):
         g = _nhwc(grad_out.to(torch.float32))
         M, H, W, C = xn.shape
         rows, dev = M * H * W, xn.device
-        new = lambda shape: _empty(shape, dtype=torch.float32, device=dev)
-        dx = new((M, H, W, C)) if need_x else None
-        dres = new((M, H, W, C)) if need_res and relu else None
-        dgamma, dbeta = new((C,)) if need_w else None, new((C,)) if need_b else None
+        dx = _new((M, H, W, C), dev) if need_x else None
+        dres = _new((M, H, W, C), dev) if need_res and relu else None
+        dgamma, dbeta = _new((C,), dev) if need_w else None, _new((C,), dev) if need_b else None
         if dx is not None or dres is not None or dgamma is not None or dbeta is not None:
             reduce = need_w or need_b or (training and need_x)
             ws, nbytes = _bn_workspace(lib, rows, C, dev) if reduce else (None, 0)
@@ -349,16 +352,6 @@ class BatchNorm2d(torch.nn.BatchNorm2d):
 # ------------------------------------------------------------------------------------------------ the transformer
 LN_MAX_C = 1024                # one wave per row, four quads per lane
 ATT_DIM, ATT_HEADS, ATT_MAX_N = 512, 4, 64
-
-
-def _check_f32_dev(named, optional=()):
-    for name, t in named:
-        if t is None and name in optional:
-            continue
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError(f"{name} must be a tensor on an MI355X device; there is no CPU path")
-        if t.dtype != torch.float32:
-            raise ValueError(f"{name} must be float32 (got {t.dtype})")
 
 
 def _check_ln_width(who, C):
@@ -408,15 +401,11 @@ class _LayerNorm(torch.autograd.Function):
         if not (need_x or need_w or need_b):
             return None, None, None, None
         g = grad_out.to(torch.float32).contiguous().view(rows, C)
-        new = lambda shape: _empty(shape, dtype=torch.float32, device=dev)
-        dx = new((rows, C)) if need_x else None
-        dgamma, dbeta = new((C,)) if need_w else None, new((C,)) if need_b else None
+        dx = _new((rows, C), dev) if need_x else None
+        dgamma, dbeta = _new((C,), dev) if need_w else None, _new((C,), dev) if need_b else None
         ws, nbytes = None, 0
         if need_w or need_b:
-            nbytes = lib.omni_layernorm_bwd_workspace_bytes(rows, C)
-            if nbytes == 0:
-                raise ValueError(f"layer_norm: {rows} rows of {C} values are outside the operator's scope")
-            ws = new((nbytes // 4,))
+            ws, nbytes = _workspace(lib.omni_layernorm_bwd_workspace_bytes, f"layer_norm: {rows} rows of {C} values are", rows, C, dev=dev)
         with torch.cuda.device(dev):
             _lib.check(lib.omni_layernorm_bwd_f32(_p(g), _p(xc), _p(w), _p(dx), _p(dgamma), _p(dbeta), rows, C, ctx.eps, _p(ws), nbytes,
                                                   _lib.stream_of(xc)), "layer_norm_bwd")
@@ -526,10 +515,7 @@ class _Attention(torch.autograd.Function):
         dkv = _empty((batch * N, 2 * ATT_DIM), dtype=torch.float32, device=dev) if need_kv else None
         ws, nbytes = None, 0
         if need_kv:
-            nbytes = lib.omni_attention_bwd_workspace_bytes(batch, N)
-            if nbytes == 0:
-                raise ValueError(f"attention: {batch} items of {N} tokens are outside the operator's scope")
-            ws = _empty((nbytes // 4,), dtype=torch.float32, device=dev)
+            ws, nbytes = _workspace(lib.omni_attention_bwd_workspace_bytes, f"attention: {batch} items of {N} tokens are", batch, N, dev=dev)
         with torch.cuda.device(dev):
             _lib.check(lib.omni_attention_bwd_f32(_p(qc), _p(kvc), _p(g), _p(dq), _p(dkv), batch, N, _p(ws), nbytes, _lib.stream_of(qc)),
                        "attention_bwd")
@@ -676,10 +662,8 @@ class _StemConv2d(torch.autograd.Function):
         M, _, H, W = xc.shape
         dev = xc.device
         g = _nhwc(grad_out.to(torch.float32))
-        nbytes = lib.omni_stem_conv_bwd_workspace_bytes(M, H, W)
-        if nbytes == 0:
-            raise ValueError(f"stem_conv2d backward: x of shape {tuple(xc.shape)} is outside the operator's scope")
-        ws = _empty(nbytes // 4, dtype=torch.float32, device=dev)
+        ws, nbytes = _workspace(lib.omni_stem_conv_bwd_workspace_bytes, f"stem_conv2d backward: x of shape {tuple(xc.shape)} is", M, H, W,
+                                dev=dev)
         dw = _empty((7, 7, 3, 64), dtype=torch.float32, device=dev) if need_w else None
         db = _empty(64, dtype=torch.float32, device=dev) if need_b else None
         with torch.cuda.device(dev):
@@ -844,13 +828,12 @@ class _DepthHeads(torch.autograd.Function):
         xn = _nhwc(x)
         M, H, W, _ = xn.shape
         dev = xn.device
-        new = lambda shape: _empty(shape, dtype=torch.float32, device=dev)
-        w, bias = new((2, 3, 3, HEADS_C)), new((2,))                          # [2][9][32] and the two biases, packed on the device (2.3 KB)
+        w, bias = _new((2, 3, 3, HEADS_C), dev), _new((2,), dev)              # [2][9][32] and the two biases, packed on the device (2.3 KB)
         w[0:1].copy_(w_pred.detach().permute(0, 2, 3, 1)); w[1:2].copy_(w_conf.detach().permute(0, 2, 3, 1))
         bias[0:1].copy_(b_pred.detach()); bias[1:2].copy_(b_conf.detach())
         pending = any(ctx.needs_input_grad[:5])
-        a, c = new((M, 1, H, W)), new((M, 1, H, W)) if confidence else None
-        p, q = (new((M, H, W)), new((M, H, W))) if pending else (None, None)
+        a, c = _new((M, 1, H, W), dev), _new((M, 1, H, W), dev) if confidence else None
+        p, q = (_new((M, H, W), dev), _new((M, H, W), dev)) if pending else (None, None)
         with torch.cuda.device(dev):
             _lib.check(lib.omni_depth_heads_fwd_f32(_p(xn), _p(w), _p(bias), _p(a), _p(c), _p(p), _p(q), M, H, W, int(confidence),
                                                     _lib.stream_of(xn)), "depth_heads")
@@ -872,16 +855,13 @@ class _DepthHeads(torch.autograd.Function):
         xn, w, p, q = ctx.saved_tensors
         M, H, W, _ = xn.shape
         dev = xn.device
-        new = lambda shape: _empty(shape, dtype=torch.float32, device=dev)
         ga = grad_a.to(torch.float32).contiguous() if grad_a is not None else None
         gc = grad_c.to(torch.float32).contiguous() if grad_c is not None else None
-        nbytes = lib.omni_depth_heads_bwd_workspace_bytes(M, H, W)
-        if nbytes == 0:
-            raise ValueError(f"depth_heads backward: x of shape {(M, HEADS_C, H, W)} is outside the operator's scope")
-        ws = new((nbytes // 4,))
-        dx = new((M, H, W, HEADS_C)) if need_x else None
-        dw = new((2, 3, 3, HEADS_C)) if need_w else None
-        db = new((2,)) if need_b else None
+        ws, nbytes = _workspace(lib.omni_depth_heads_bwd_workspace_bytes, f"depth_heads backward: x of shape {(M, HEADS_C, H, W)} is", M, H, W,
+                                dev=dev)
+        dx = _new((M, H, W, HEADS_C), dev) if need_x else None
+        dw = _new((2, 3, 3, HEADS_C), dev) if need_w else None
+        db = _new((2,), dev) if need_b else None
         with torch.cuda.device(dev):
             _lib.check(lib.omni_depth_heads_bwd_f32(_p(ga), _p(gc), _p(p), _p(q), _p(xn), _p(w), _p(dx), _p(dw), _p(db), M, H, W, int(conf),
                                                     _p(ws), nbytes, _lib.stream_of(xn)), "depth_heads_bwd")

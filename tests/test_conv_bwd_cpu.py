@@ -45,7 +45,8 @@ def test_symbols_declared_exported_and_bound():
 
 def test_no_getenv_and_no_guarded_kernel_name_in_the_unit():
     from omnifusion_amd import isa
-    src = open(os.path.join(os.path.dirname(HEADER), "..", "omnifusion_amd", "csrc", "omni_conv_bwd.hip")).read()
+    csrc = os.path.join(os.path.dirname(HEADER), "..", "omnifusion_amd", "csrc")
+    src = open(os.path.join(csrc, "omni_conv_bwd.hip")).read() + open(os.path.join(csrc, "omni_partials.h")).read()    # (the finish order it includes)
     assert "getenv" not in src and "atomic" not in src.replace("no floating-point atomics", "").replace("no atomics", "")
     kernels = re.findall(r"void\s+(\w+_kernel)\s*\(", src)
     assert {"conv_dgrad_kernel", "conv_wgrad_kernel"} <= set(kernels)

@@ -33,8 +33,9 @@ CASES = {
     "c96_160":    (2, 4, 4, 96, 0, 160, 3, 1, 1, "none", False),     # multiples of 32 but not of 64
     "linear":     (18, 1, 1, 512, 0, 2048, 1, 1, 0, "none", False),  # fewer rows than one MFMA tile
     "rows10240":  (40, 16, 16, 32, 0, 32, 3, 1, 1, "relu", True),    # many wgrad chunks, many blocks
+    "rows16641":  (1, 129, 129, 32, 0, 32, 3, 1, 1, "relu", True),   # 261 epilogue blocks of 64 rows: the finish kernel's threads 0 .. 4 add two partials
 }
-SEEDS = {"plain": 0, "odd105": 1, "s2even": 2, "s2odd": 3, "ds1x1": 4, "concat": 5, "c96_160": 6, "linear": 7, "rows10240": 448}
+SEEDS = {"plain": 0, "odd105": 1, "s2even": 2, "s2odd": 3, "ds1x1": 4, "concat": 5, "c96_160": 6, "linear": 7, "rows10240": 448, "rows16641": 19}
 KINDS = ("x", "x2", "w", "b", "res")
 
 
