@@ -770,6 +770,28 @@ int omni_depth_heads_bwd_f32(const float* grad_a, const float* grad_c, const flo
                              float* dx, float* dw, float* dbias, int M, int H, int W, int confidence, void* workspace, size_t ws_bytes,
                              omni_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * The 1x1 convolutions of the point-feature MLPs in training mode (csrc/omni_point_conv.hip): mlp_points1 / mlp_points2 of
+ * model/spherical_model_iterative.py:290-305, 387-393 and mlp_points of model/spherical_model.py:228-235.  fp32 FMAs, no bias:
+ *     y[m,hw,o] = sum_c w[o][c] . (x[m mod Mx, c, hw] . (scale ? scale[m,hw] : 1)),  c ascending, the product x . scale rounded first.
+ * Exactly three forms (anything else UNSUPPORTED): Cin -> Cout = 3 -> 16 with x planar [Mx,3,HW], M a multiple of Mx (x is broadcast over
+ * the M / Mx repeats) and an optional scale [M,HW]; 5 -> 16 with x planar [M,5,HW]; 16 -> 64 with x NHWC [M,HW,16]; the last two with
+ * Mx = M and scale NULL.  w [Cout][Cin] (the parameter's storage); y and gy contiguous NHWC [M,HW,Cout]; M.HW < 2^31 (else UNSUPPORTED);
+ * every pointer 16-byte aligned.  Nothing is allocated, nothing synchronises, no atomics, every sum in an order that depends on the
+ * shapes alone: the same bits on every run, and dx / dscale of an item are functions of that item.  Every rejection happens before a launch.
+ * omni_point_conv_bwd_f32: each of dx, dw, dscale may be NULL (not computed, its kernel not launched), not all three.
+ *   dscale [M,HW] (3 -> 16 with a scale only) = sum_c x[m mod Mx,c,hw] . (sum_o w[o][c] . gy[m,hw,o]), o then c ascending;
+ *   dx [M,HW,16] (16 -> 64 only; UNSUPPORTED for the planar forms) = sum_o w[o][c] . gy[m,hw,o], o ascending;
+ *   dw [Cout][Cin] = sum over the rows of gy[row][o] . (x . scale)[row][c]: fp32 FMAs over chunks of `per` rows, the chunks' partials
+ *   [Cout.Cin] added in double in a fixed order, one rounding.  x is read for dw and dscale only.
+ * `workspace` (dw only): omni_point_conv_bwd_workspace_bytes(M, HW, Cin, Cout) = nchunk . Cout . Cin . 4 bytes (0 outside the scope), with
+ * per = 64 . max(5, ceil(ceil(M.HW / 1024) / 64)) rows and nchunk = ceil(M.HW / per); any content, 16-byte aligned. */
+int omni_point_conv_fwd_f32(const float* x, const float* w, const float* scale, float* y, int Mx, int M, int HW, int Cin, int Cout,
+                            omni_stream_t stream);
+size_t omni_point_conv_bwd_workspace_bytes(int M, int HW, int Cin, int Cout);
+int omni_point_conv_bwd_f32(const float* gy, const float* x, const float* w, const float* scale, float* dx, float* dw, float* dscale,
+                            int Mx, int M, int HW, int Cin, int Cout, void* workspace, size_t ws_bytes, omni_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,9 @@ omni_upsample_bilinear2x_bwd_f32 i ppi4p
 omni_depth_heads_fwd_f32 i p7i4p
 omni_depth_heads_bwd_workspace_bytes z i3
 omni_depth_heads_bwd_f32 i p9i4pzp
+omni_point_conv_fwd_f32 i p4i5p
+omni_point_conv_bwd_workspace_bytes z i4
+omni_point_conv_bwd_f32 i p7i5pzp
 """
 
 

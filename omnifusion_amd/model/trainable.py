@@ -22,8 +22,9 @@ Run by torch operators with autograd (small; tools/train_bench.py reports their 
 ops.BatchNorm2d are the reference's; written as a product and a sum, whose bits repeat), the two broadcast additions
 `layer1 + point_feat` and `layer4 + tokens`, and the reshapes around the transformer.
 
-Not built: the iterative model, DataParallel / SyncBatchNorm / convert_model, fp16, an image gradient, a hand-written
-optimiser (torch.optim.AdamW steps the parameters), capture of a whole step in a graph.  fp32 CUDA input, one device.
+The iterative model is model/trainable_iterative.py, a subclass.  Not built: DataParallel /
+SyncBatchNorm / convert_model, fp16, an image gradient, a hand-written optimiser (torch.optim.AdamW steps the parameters), capture of a
+whole step in a graph.  fp32 CUDA input, one device.
 """
 import ctypes
 
@@ -114,6 +115,8 @@ def _layer(cin, cout, blocks, stride):
 
 
 class spherical_fusion(nn.Module):
+    _DOWN = "down"                                                             # the token projection's name (trainable_iterative.py: "down1")
+
     def __init__(self, nrows=4, npatches=18, patch_size=(128, 128), fov=(80, 80)):
         super().__init__()
         self.nrows, self.npatches, self.patch_size, self.fov = nrows, npatches, patch_size, fov
@@ -129,7 +132,7 @@ class spherical_fusion(nn.Module):
         self.bn1 = _bn(64, "relu")
         self.layer1, self.layer2 = _layer(64, 64, 3, 1), _layer(64, 128, 4, 2)
         self.layer3, self.layer4 = _layer(128, 256, 6, 2), _layer(256, 512, 3, 2)
-        self.down = _Conv(512, 512 // 16, 1, bias=True)
+        setattr(self, self._DOWN, _Conv(512, 512 // 16, 1, bias=True))
         self.transformer = ops.TransformerCascade(TOKEN_WIDTH, npatches, depth=6, num_heads=4)      # encoder_norm: eps 1e-6, block norms 1e-5
         self.de_conv0_0, self.de_conv0_1 = _ConvBnReLU(512, 256), _ConvBnReLU(256 + 256, 128)
         self.de_conv1_0, self.de_conv1_1 = _ConvBnReLU(128, 128), _ConvBnReLU(128 + 128, 64)
@@ -137,15 +140,19 @@ class spherical_fusion(nn.Module):
         self.de_conv3_0, self.de_conv3_1 = _ConvBnReLU(64, 64), _ConvBnReLU(64 + 64, 32)
         self.de_conv4_0 = _ConvBnReLU(32, 32)
         self.pred, self.weight_pred = _Head(), _Head()
-        self.mlp_points = nn.Sequential(
-            _PointConv(5, 16, kernel_size=1, stride=1, padding=0, bias=False), _bn(16, "relu"), nn.Identity(),          # (2, 5: the ReLUs,
-            _PointConv(16, 64, kernel_size=1, stride=1, padding=0, bias=False), _bn(64, "relu"), nn.Identity())        # fused into 1, 4)
+        self._add_point_mlps()
         self._pool, self._up = ops.MaxPool2d(3, 2, 1), ops.UpsampleBilinear2x()
         cp = (ctypes.c_float * (2 * npatches))()
         if _lib.load().omni_patch_centers(int(nrows), 0, cp) != _lib.OMNI_OK:
             raise ValueError(f"unsupported nrows={nrows!r}")
         self._centers = [float(v) for v in cp]                                 # the patch centres (model/spherical_model.py:244): constants
         self.__dict__["_points_in"] = {}                                       # device -> mlp_points' input; not a buffer: not in the state dict
+
+    def _add_point_mlps(self):
+        """registers the point-feature MLPs, the last entries of the state dict"""
+        self.mlp_points = nn.Sequential(
+            _PointConv(5, 16, kernel_size=1, stride=1, padding=0, bias=False), _bn(16, "relu"), nn.Identity(),          # (2, 5: the ReLUs,
+            _PointConv(16, 64, kernel_size=1, stride=1, padding=0, bias=False), _bn(64, "relu"), nn.Identity())        # fused into 1, 4)
 
     def load_state_dict(self, state_dict, strict=True, assign=False):
         sd = strip_module_prefix(state_dict)                                   # train_erp_depth.py:307 saves through DataParallel
@@ -188,18 +195,21 @@ class spherical_fusion(nn.Module):
             return pers2equi(a, self.fov, self.nrows, P, (H, W), None, layout=_lib.LAYOUT_BNCHW)                          # :313
 
     def network(self, patches, point_feat, confidence=True):
-        """planar patches [bs,N,3,P,P], point_feat [N,64,P/4,P/4] -> (pred . conf, conf) planes [bs,N,1,P,P] ((pred, None) without
-        confidence): the part of forward between the two resamplers"""
+        """planar patches [bs,N,3,P,P], point_feat [N,64,P/4,P/4] (broadcast over the batch) or [bs.N,64,P/4,P/4] -> (pred . conf, conf)
+        planes [bs,N,1,P,P] ((pred, None) without confidence): the part of forward between the two resamplers"""
         bs, N, _, P, _ = patches.shape
         M = bs * N
         conv1 = self.bn1(self.conv1(patches.reshape(M, 3, P, P)))                                                         # :254
         layer1 = self.layer1(self._pool(conv1))                                                                           # :255-257
         pf = point_feat.contiguous(memory_format=torch.channels_last)
-        layer1 = (layer1.reshape(bs, N, *layer1.shape[1:]) + pf[None]).reshape(layer1.shape)                              # :258
+        if pf.shape[0] == N:
+            layer1 = (layer1.reshape(bs, N, *layer1.shape[1:]) + pf[None]).reshape(layer1.shape)                          # :258
+        else:
+            layer1 = layer1 + pf                                               # one map per item: the iterative model's later passes
         layer2 = self.layer2(layer1)
         layer3 = self.layer3(layer2)
         layer4 = self.layer4(layer3)
-        tok = self.down(layer4).reshape(bs, N, TOKEN_WIDTH)                    # token element = c . 16 + h . 4 + w       # :263-264
+        tok = getattr(self, self._DOWN)(layer4).reshape(bs, N, TOKEN_WIDTH)    # token element = c . 16 + h . 4 + w       # :263-264
         tok = self.transformer(tok)                                                                                       # :266
         layer4 = layer4 + tok.reshape(M, TOKEN_WIDTH, 1, 1)                                                               # :267-268
         x = self.de_conv0_1(self.de_conv0_0(self._up(layer4)), x2=layer3)                                                 # :271-276

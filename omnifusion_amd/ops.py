@@ -62,6 +62,17 @@ a = relu(pred(x)) . sigmoid(weight_pred(x)), c = sigmoid(weight_pred(x)); confid
 biases stay on the device (nothing is read back, the operator can be captured in a graph).  Differentiable w.r.t. x, both weights and
 both biases: fp32 FMAs, the weight gradient as per-chunk partial sums added in double in a fixed order.  This backward DOES keep two
 planes of its forward, the pre-activations (8 B per pixel): recomputing them would read the 128 B per pixel of x a second time.
+
+The 1x1 convolutions of the point-feature MLPs (csrc/omni_point_conv.hip):
+
+    y = point_conv(x, weight, *, scale=None)                  # weight [16,3,1,1] | [16,5,1,1] | [64,16,1,1], no bias; y [M,Cout,h,w]
+    PointConv2d(3 | 5, 16, 1, bias=False), PointConv2d(16, 64, 1, bias=False)      # nn.Conv2d's parameter; forward(x, scale=None)
+
+y = conv2d(x . scale, weight) in fp32 FMAs, three forms and no other: 3 -> 16 on a planar x [Mx,3,h,w] that is repeated M / Mx times
+under an optional scale [M,1,h,w] (the unit rays times the re-projected depth of the iterative model: the product is never written),
+5 -> 16 on a planar x, 16 -> 64 on a channels-last x.  Differentiable w.r.t. weight (per-chunk partial sums added in double in a fixed
+order), scale (a gather per pixel) and, 16 -> 64 only, x; a planar x that requires a gradient raises NotImplementedError.  The same rules:
+no atomics, no host synchronisation, only what autograd asks for, nothing kept but the inputs.
 """
 import torch
 
@@ -891,6 +902,112 @@ class DepthHeads(torch.nn.Module):
 
     def forward(self, x, confidence=True):
         return depth_heads(x, self.pred.weight, self.pred.bias, self.weight_pred.weight, self.weight_pred.bias, confidence=confidence)
+
+
+# ------------------------------------------------------------------------------------------------ the point-feature MLPs
+POINT_FORMS = {(3, 16): "planar", (5, 16): "planar", (16, 64): "channels_last"}      # (Cin, Cout) -> the layout of x the kernel reads
+
+
+def _check_point_args(x, weight, scale):
+    """Every rejection of point_conv, raised before anything is launched: shapes first, then gradients, dtypes and devices.  Returns
+    (Mx, M, h, w, Cin, Cout)."""
+    for name, t in (("x", x), ("weight", weight)) + ((("scale", scale),) if scale is not None else ()):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"point_conv: {name} must be a tensor")
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (1, 1) or tuple(weight.shape[1::-1]) not in POINT_FORMS:
+        raise ValueError(f"point_conv: weight must be [16,3,1,1], [16,5,1,1] or [64,16,1,1]: 1x1 convolutions from 3 or 5 to 16 and from 16 to 64 "
+                         f"channels are the only ones built (got {tuple(weight.shape)})")
+    Cout, Cin = weight.shape[:2]
+    if x.dim() != 4 or x.numel() == 0 or x.shape[1] != Cin:
+        raise ValueError(f"point_conv: x must be a non-empty [Mx,{Cin},h,w] tensor for a weight {tuple(weight.shape)} (got {tuple(x.shape)})")
+    Mx, _, h, w = x.shape
+    M = Mx
+    if scale is not None:
+        if Cin != 3:
+            raise ValueError(f"point_conv: only the 3 -> 16 form takes a scale (weight {tuple(weight.shape)})")
+        if scale.dim() != 4 or scale.shape[1] != 1 or tuple(scale.shape[2:]) != (h, w) or scale.shape[0] == 0 or scale.shape[0] % Mx:
+            raise ValueError(f"point_conv: scale must be [M,1,{h},{w}] with M a multiple of x's {Mx} items (got {tuple(scale.shape)})")
+        M = scale.shape[0]
+    if M * h * w >= 1 << 31:
+        raise ValueError(f"point_conv: {M} maps of {h} x {w} have 2^31 pixels or more")
+    if x.requires_grad and torch.is_grad_enabled() and POINT_FORMS[(Cin, Cout)] == "planar":
+        raise NotImplementedError(f"point_conv: x requires a gradient, but the planar (broadcast) {Cin} -> {Cout} form has none w.r.t. x — the "
+                                  f"rays and the patch centres are constants; pass x.detach()")
+    for name, t in (("x", x), ("weight", weight), ("scale", scale)):
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError(f"point_conv: {name} must be float32 (got {t.dtype})")
+    _check_f32_dev((("x", x), ("weight", weight), ("scale", scale)), optional=("scale",))
+    if len({t.device for t in (x, weight, scale) if t is not None}) != 1:
+        raise ValueError("point_conv: x, weight and scale must be on one device")
+    return Mx, M, h, w, Cin, Cout
+
+
+class _PointConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, scale):
+        lib = _lib.load()
+        Cout, Cin = weight.shape[:2]
+        xs = _nhwc(x) if POINT_FORMS[(Cin, Cout)] == "channels_last" else x.contiguous()      # the storage the form reads: no copy where x has it
+        wc = weight.detach().contiguous()                                      # [Cout,Cin,1,1]: the library's [Cout][Cin]
+        sc = scale.contiguous() if scale is not None else None
+        Mx, h, w = x.shape[0], x.shape[2], x.shape[3]
+        M = sc.shape[0] if sc is not None else Mx
+        dev = x.device
+        y = _new((M, h, w, Cout), dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.omni_point_conv_fwd_f32(_p(xs), _p(wc), _p(sc), _p(y), Mx, M, h * w, Cin, Cout, _lib.stream_of(y)), "point_conv")
+        ctx.dims = (Mx, M, h, w, Cin, Cout)
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(xs, wc, sc)                                  # the inputs, nothing of the forward
+        return _nchw(y)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        need_x, need_w, need_s = ctx.needs_input_grad
+        if not (need_x or need_w or need_s):
+            return None, None, None
+        lib = _lib.load()
+        xs, wc, sc = ctx.saved_tensors
+        Mx, M, h, w, Cin, Cout = ctx.dims
+        dev = xs.device
+        g = _nhwc(grad_out.to(torch.float32))
+        dx = _new((M, h, w, Cin), dev) if need_x else None
+        dw = _new((Cout, Cin, 1, 1), dev) if need_w else None
+        ds = _new((M, 1, h, w), dev) if need_s else None
+        ws, nbytes = (None, 0)
+        if need_w:
+            ws, nbytes = _workspace(lib.omni_point_conv_bwd_workspace_bytes, f"point_conv backward: {M} maps of {h} x {w} are", M, h * w, Cin, Cout,
+                                    dev=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.omni_point_conv_bwd_f32(_p(g), _p(xs), _p(wc), _p(sc), _p(dx), _p(dw), _p(ds), Mx, M, h * w, Cin, Cout, _p(ws), nbytes,
+                                                   _lib.stream_of(g)), "point_conv_bwd")
+        return _nchw(dx), dw, ds
+
+
+def point_conv(x, weight, *, scale=None):
+    """A 1x1 convolution of the point-feature MLPs without bias: y = conv2d(x . scale, weight), in three forms and no other.
+    weight [16,3,1,1]: x [Mx,3,h,w] planar, repeated M / Mx times under an optional scale [M,1,h,w] (the unit rays times the depth of
+    model/spherical_model_iterative.py:387-393); weight [16,5,1,1]: x [M,5,h,w] planar; weight [64,16,1,1]: x [M,16,h,w] channels-last.
+    y [M,Cout,h,w] is channels-last, the layout batch_norm takes without a copy.  Differentiable w.r.t. weight, scale and — the 16 -> 64
+    form only — x; a planar x that requires a gradient raises NotImplementedError."""
+    _check_point_args(x, weight, scale)
+    return _PointConv.apply(x, weight, scale)
+
+
+class PointConv2d(torch.nn.Conv2d):
+    """nn.Conv2d(3 | 5, 16, 1, bias=False) or nn.Conv2d(16, 64, 1, bias=False) — the same Parameter [Cout,Cin,1,1] under the same name —
+    whose forward(x, scale=None) is point_conv."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=1, stride=1, padding=0, bias=False, **kw):
+        if (in_channels, out_channels) not in POINT_FORMS or bias or tuple(_pair(kernel_size)) != (1, 1) \
+                or tuple(_pair(stride)) != (1, 1) or tuple(_pair(padding)) != (0, 0):
+            raise ValueError("ops.PointConv2d: 1x1 convolutions from 3 or 5 to 16 and from 16 to 64 channels, stride 1, no padding, no bias, are "
+                             "the only ones built")
+        super().__init__(in_channels, out_channels, 1, bias=False, **kw)
+
+    def forward(self, x, scale=None):
+        return point_conv(x, self.weight, scale=scale)
 
 
 def _conv_in_scope(m):
