@@ -287,6 +287,15 @@ int omni_upsample_bilinear_sh(const void* src, void* dst, int M, int H, int W, i
  * Cout % 32 != 0, Hl * Wl > 64 or another activation: OMNI_ERR_UNSUPPORTED (omni_upsample_bilinear_sh + omni_conv2d_sh_f16x3_ws compute the
  * same convolution); null tensors or an empty shape: OMNI_ERR_INVALID. */
 int omni_up2_tapsum_sh(const float* y, const float* bias, void* dst, int M, int Hl, int Wl, int Cout, int act, omni_stream_t stream);
+/* The same identity in ONE launch, for the 64 -> 64 decoder stages: the nine tap products are formed on the matrix cores (f16x3), parked in LDS as fp32 and
+ * summed into register accumulators with omni_up2_tapsum_sh's arithmetic and fixed order — they never reach memory.  src SH [M][Hl][Wl][64]; wt16t: the
+ * tap-major f16x3 weights [9*Cout][64], row t*Cout + co = W[co][t][:] (the operand of the two-launch form); bias fp32 [Cout] or NULL; dst SH [M][2Hl][2Wl][Cout];
+ * fmt 1 (SH result; bit 2 accepted and ignored: one form for every batch).  Deterministic; an image's bits do not depend on M.  Values are saturated to the
+ * SH range (omni_sh_overflow reports it).  Serves C == Cout == 64 with Wl == 32 and Hl % 8 == 0, or Hl == Wl == 16, no activation or ReLU; anything else
+ * (f16x1, an fp32 result included): OMNI_ERR_UNSUPPORTED before any launch (omni_conv3x3_up2_sh_f16x3 computes the same convolution); null tensors, an empty
+ * shape, channels that are no multiple of 32 or tensors not 16-byte aligned: OMNI_ERR_INVALID. */
+int omni_conv3x3_up2_taps_sh_f16x3(const void* src, const void* wt16t, const float* bias, void* dst, int fmt,
+                                   int M, int Hl, int Wl, int C, int Cout, int act, omni_stream_t stream);
 int omni_add_hw_sh(void* x, const float* y, int M, int HW, int C, omni_stream_t stream);
 int omni_add_period_sh(void* x, const float* y, size_t total, size_t period, omni_stream_t stream);
 /* nn.LayerNorm(512) with an SH result, and the attention core on a fused q|k|v projection [B*N, 1536] (q at column 0,

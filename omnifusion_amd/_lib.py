@@ -80,6 +80,7 @@ omni_stem_sh_f16x1 i p4iip
 omni_maxpool3x3s2_sh i ppi4p
 omni_upsample_bilinear_sh i ppi6p
 omni_up2_tapsum_sh i p3i5p
+omni_conv3x3_up2_taps_sh_f16x3 i p4i7p
 omni_add_hw_sh i ppi3p
 omni_add_period_sh i ppzzp
 omni_layernorm512_sh i p4ifp

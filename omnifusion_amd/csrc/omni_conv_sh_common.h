@@ -298,6 +298,7 @@ int omni_sh_overflow_pm(unsigned* out, int reset);
 // iw 0: W % 32 == 0 and H % 8 == 0 | iw 16: H == W == 16 and rows % 256 == 0) on `grid` blocks of 256 threads
 int omni_halo2_launch(const void* args, int iw, bool x1, unsigned grid, hipStream_t s);
 int omni_sh_overflow_halo2(unsigned* out, int reset);
+int omni_sh_overflow_up2_taps(unsigned* out, int reset);  // omni_conv_up2_taps.hip's (up2_taps_fused_kernel; its entry point lives in that unit)
 // the sticky range flag of omni_sh.h, one copy per translation unit whose kernels write SH: omni_sh_overflow (omni_conv_sh.hip) reads them all
 int omni_sh_overflow_halo(unsigned* out, int reset);
 int omni_sh_overflow_up2(unsigned* out, int reset);

@@ -1,0 +1,257 @@
+// omni_conv_up2_taps.hip — up2_taps_fused_kernel and its entry point omni_conv3x3_up2_taps_sh_f16x3: conv3x3(upsample2x(x)) of the 64 -> 64 decoder stages
+// (de_conv3_0, de_conv2_0) as nine 1x1 TAP PRODUCTS on the low-resolution map, summed through LDS.  Both operators are linear, so
+//   out[q] = bias + sum_t [q + t - 1 inside the 2Hl x 2Wl map] * up2(W_t . x)[q + t - 1]                       (t = ky*3 + kx)
+// — a quarter of the matrix instructions of the up-sampling halo kernel (conv3x3_halo_sh_kernel<64, 4, true, 0>), which convolves at full resolution.  The
+// two-launch form of the identity (omni_conv2d_sh_f16x3_ws on the tap-major weights + omni_up2_tapsum_sh, Engine.taps_first) moves the fp32 tap products
+// through memory: 340 MB for de_conv3_0 at 144 patches.  Here they never leave the CU.
+//
+// A block owns ROWS low-resolution rows of one image at full width (WL) — 8 rows + one halo row each side at WL = 32 ("bands": 320 pixels; left and right
+// need no halo, the clamp of the up-sampling addresses the same column), or a whole 16 x 16 image (256 pixels, no halo) — and 32 output channels:
+//   * the block's nine taps of weights (9 x 32 rows x 256 B = 72 KiB, tap-major f16x3 rows as `<key>.taps.w16`) go to LDS by LDS-DMA, once, in tap order;
+//     tap t is waited for just before its products (hand-counted s_waitcnt vmcnt);
+//   * a wave keeps the SH fragments of its pixels (32-pixel fragments w, w + 4, w + 8; K = 64: hi and lo of four 16-channel chunks) in registers for all nine taps;
+//   * per tap: 12 matrix instructions per fragment (the f16x3 three-term product, acc_join) -> the fp32 products of the tap, [pixel][32 channels], parked in
+//     one of two LDS chunks (40 KiB) -> ONE barrier -> every thread adds the tap to its output accumulators: thread = (low-res column j, channel quad),
+//     eight 2 x 2 output cells (rows 2i, 2i+1 x columns 2j, 2j+1 for eight rows i) x 4 channels = 128 registers.  A cell reads each live (row, column)
+//     neighbour once (49 of the 81 (tap, neighbour) pairs);
+//   * outputs leave through act_store4<true> (saturation, sticky range flag).
+// Arithmetic of up2_tapsum_sh_kernel (omni_net.hip): the same bilinear weights (0.25 / 0.75 are exact, so the table below holds the values its index
+// arithmetic yields), source rows / columns clamped to the map, taps in the order ky, kx and per tap the neighbours 00, 01, 10, 11.  A tap outside the
+// up-sampled map gets weight zero instead of being skipped.  No atomics, no dependence on block placement: an image's bits do not depend on M.
+// LDS: 72 KiB + 2 x 40 KiB = 152 KiB, one block of four waves per CU with up to 512 registers per lane.
+#include <stdint.h>
+#include "omni_conv_sh_common.h"
+
+namespace {
+
+struct TapsArgs {
+    const void* src;                         // SH [M, Hl, Wl, 64]
+    const void* wt;                          // halfs [9 * Cout][2][hi32|lo32], row t*Cout + co
+    const float* bias;                       // [Cout] or null
+    void* dst;                               // SH [M, 2Hl, 2Wl, Cout]
+    int M, Hl, Cout, act;
+};
+
+constexpr int TAP_BYTES = 32 * 256;          // one tap of a block's weights: 32 output channels x (2 groups x 128 B)
+
+// s_waitcnt vmcnt(n) for the even counts the tap loop needs (n is a constant after unrolling)
+__device__ __forceinline__ void wait_taps_in_flight(int n)
+{
+    if (n >= 16) wait_vm<16>();
+    else if (n == 14) wait_vm<14>();
+    else if (n == 12) wait_vm<12>();
+    else if (n == 10) wait_vm<10>();
+    else if (n == 8) wait_vm<8>();
+    else if (n == 6) wait_vm<6>();
+    else if (n == 4) wait_vm<4>();
+    else if (n == 2) wait_vm<2>();
+    else wait_vm<0>();
+}
+
+template <int WL, int ROWS, int HALO>
+__global__ __launch_bounds__(256, 1) void up2_taps_fused_kernel(TapsArgs a)
+{
+    static_assert((WL == 32 && ROWS == 8 && HALO == 1) || (WL == 16 && ROWS == 16 && HALO == 0), "bands of 8 rows of 32-wide maps, or whole 16 x 16 maps");
+    constexpr int SROWS = ROWS + 2 * HALO, P = SROWS * WL, NF = P / 32, NFW = (NF + 3) / 4;
+    constexpr int W_BYTES = 9 * TAP_BYTES, CH_BYTES = P * 128, ROW_BYTES = WL * 128;
+    static_assert(P % 32 == 0 && ROWS * WL == 256, "whole fragments; one (column, channel quad) thread per eight rows");
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[W_BYTES + 2 * CH_BYTES];
+    static_assert(sizeof(lds) <= 160 * 1024, "one block per CU");
+
+    const int t = threadIdx.x, lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);     // wave-uniform: LDS-DMA bases stay in scalar registers
+    const int ntn = a.Cout >> 5, nb = a.Hl / ROWS;
+    int bid = blockIdx.x;
+    const int tile_n = bid % ntn; bid /= ntn;
+    const int band = bid % nb; const int m = bid / nb;
+    const int r0 = band * ROWS, col0 = tile_n * 32, sbase = r0 - HALO;       // sbase: image row of LDS slot row 0
+    const int Hl = a.Hl;
+
+    // The wave's fragments w, w + 4, w + 8.  Ten fragments on four waves: waves 2 and 3 repeat their fragment w + 4 (the same values to the same addresses) while
+    // waves 0 and 1 do fragments 8 and 9 — they would wait at the barrier for as long, and the kernel stays ONE basic block: with a branch here the compiler sinks
+    // the whole tap sum below the last tap and keeps every value it read from the chunks alive until then (4.5 KB of scratch).
+    auto frag = [&](int fi) { const int f = wave + 4 * fi; return f < NF ? f : wave + 4; };
+    // ---- the wave's pixel fragments: fragment f = slot pixels 32 f .. 32 f + 31, lane -> pixel lane & 31, 16-byte piece lane >> 5 of every 16-channel chunk
+    h8v xh[NFW][4], xl[NFW][4];
+#pragma unroll
+    for (int fi = 0; fi < NFW; ++fi) {
+        const int f = frag(fi);
+        {
+            const int p = f * 32 + (lane & 31), sr = p / WL, cx = p - sr * WL;
+            const int row = min(max(sbase + sr, 0), Hl - 1);     // (the halo row above the first / below the last band is never read by the tap sum)
+            const unsigned char* sp = (const unsigned char*)a.src + ((size_t)(m * Hl + row) * WL + cx) * 256 + (lane >> 5) * 16;
+#pragma unroll
+            for (int kc = 0; kc < 4; ++kc) {
+                xh[fi][kc] = *reinterpret_cast<const h8v*>(sp + (kc >> 1) * 128 + (kc & 1) * 32);
+                xl[fi][kc] = *reinterpret_cast<const h8v*>(sp + (kc >> 1) * 128 + 64 + (kc & 1) * 32);
+            }
+        }
+    }
+    // ---- all nine taps of weights, two DMA instructions per wave and tap.  An instruction deposits four 256-byte rows; the 16 pieces of row r are permuted
+    // with r & 15 (slot s holds piece s ^ (r & 15)): the fragment reads below (32 rows, one piece each) then touch 16 distinct 16-byte bank groups
+    {
+        const rsrc_t rsw = make_rsrc(a.wt, (size_t)9 * a.Cout * 256);
+#pragma unroll
+        for (int tp = 0; tp < 9; ++tp)
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int i = wave + 4 * k, row = 4 * i + (lane >> 4), piece = (lane & 15) ^ (row & 15);
+                dma16(rsw, lds + tp * TAP_BYTES + i * 1024, ((tp * a.Cout + col0 + row) * 16 + piece) * 16, 0);
+            }
+    }
+    // weight fragment of row lane & 31: piece K | h (K = 8 group + 4 lo + 2 chunk, h = lane >> 5) sits in slot (K | h) ^ (row & 15) = K ^ (h ^ (row & 15))
+    const int wfo = (lane & 31) * 256 + (((lane >> 5) ^ (lane & 15)) * 16);
+
+    // ---- tap sum geometry: thread = (low-res column j, channel quad), rows i = r0 + ib + it, it = 0 .. 7
+    const int quad = t & 7, j = (t >> 3) & (WL - 1);
+    const int ib = WL == 32 ? 0 : 8 * (wave >> 1);
+    int coff[3];                                                  // byte offset of columns clamp(j - 1 + c) in a chunk row, the lane's channel quad (chunk pieces are permuted with (pixel >> 1) & 3)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int col = min(max(j - 1 + c, 0), WL - 1);
+        coff[c] = col * 128 + ((quad ^ ((col >> 1) & 3)) * 16);
+    }
+    // bilinear weights of up-sampled column 2j + u - 1, u = 0 .. 3, on the column pair (c, c + 1), c = u >> 1: (1 - l, l) with l = frac(max(0.5 (p + 0.5) - 0.5, 0)),
+    // zero where the column is outside the map
+    float hx[4], lx[4];
+    hx[0] = j > 0 ? 0.75f : 0.0f;      lx[0] = j > 0 ? 0.25f : 0.0f;
+    hx[1] = j > 0 ? 0.25f : 1.0f;      lx[1] = j > 0 ? 0.75f : 0.0f;
+    hx[2] = 0.75f;                     lx[2] = 0.25f;
+    hx[3] = j < WL - 1 ? 0.25f : 0.0f; lx[3] = j < WL - 1 ? 0.75f : 0.0f;
+
+    f4v out[8][2][2];
+#pragma unroll
+    for (int it = 0; it < 8; ++it)
+#pragma unroll
+        for (int ab = 0; ab < 4; ++ab) out[it][ab >> 1][ab & 1] = (f4v)(0.0f);
+
+    wait_taps_in_flight(16);                                      // my pieces of tap 0 have landed (the pixel fragments were issued before them)
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+
+    auto tap = [&]<int tp>() {                                    // (a template, called nine times: `#pragma unroll` gives up on a body of this size)
+        constexpr int ky = tp / 3, kx = tp - 3 * ky;
+        unsigned char* chunk = lds + W_BYTES + (tp & 1) * CH_BYTES;
+        // ---- the tap's products of my fragments -> chunk
+        {
+            const unsigned char* wb = lds + tp * TAP_BYTES;
+            h8v wh[4], wl[4];
+#pragma unroll
+            for (int kc = 0; kc < 4; ++kc) {
+                const int K = 8 * (kc >> 1) + 2 * (kc & 1);
+                wh[kc] = *reinterpret_cast<const h8v*>(wb + (wfo ^ (K * 16)));
+                wl[kc] = *reinterpret_cast<const h8v*>(wb + (wfo ^ ((K + 4) * 16)));
+            }
+#pragma unroll
+            for (int fi = 0; fi < NFW; ++fi) {
+                const int f = frag(fi);
+                {
+                    f16v acc = (f16v)(0.0f), acc1 = (f16v)(0.0f);
+#pragma unroll
+                    for (int kc = 0; kc < 4; ++kc) {
+                        acc  = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[kc], xh[fi][kc], acc, 0, 0, 0);
+                        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[kc], xh[fi][kc], acc1, 0, 0, 0);
+                        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[kc], xl[fi][kc], acc1, 0, 0, 0);
+                    }
+                    const int px = f * 32 + (lane & 31);
+                    unsigned char* cp = chunk + px * 128;
+                    const int sw = (px >> 1) & 3;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {                 // channels 8q + 4 (lane >> 5) .. + 3 of pixel px
+                        f4v v;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[e] = acc_join<false>(acc1[4 * q + e], acc[4 * q + e]);
+                        *reinterpret_cast<f4v*>(cp + (((2 * q + (lane >> 5)) ^ sw) * 16)) = v;
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        if (tp < 8) wait_taps_in_flight(2 * (7 - tp));            // my pieces of tap tp + 1 have landed
+        wait_lds_reads();                                         // my products are in the chunk (and my reads of the weights have returned)
+        __builtin_amdgcn_s_barrier();                             // everybody's are; everybody is done reading the OTHER chunk (tap tp - 1)
+        asm volatile("" ::: "memory");
+        // ---- out += the tap
+#pragma unroll
+        for (int it = 0; it < 8; ++it) {
+            const int i = r0 + ib + it;
+            // weights of up-sampled row 2i + u - 1 on the row pair (r, r + 1), r = u >> 1, as for the columns (rows 1 .. 6 of a thread are never the map's edge)
+            float hy[4], ly[4];
+            const bool top = it == 0 && i == 0, bot = it == 7 && i == Hl - 1;
+            hy[0] = top ? 0.0f : 0.75f; ly[0] = top ? 0.0f : 0.25f;
+            hy[1] = top ? 1.0f : 0.25f; ly[1] = top ? 0.0f : 0.75f;
+            hy[2] = 0.75f;              ly[2] = 0.25f;
+            hy[3] = bot ? 0.0f : 0.25f; ly[3] = bot ? 0.0f : 0.75f;
+            f4v v[3][3];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                if (r < (ky >> 1) || r > ((ky + 1) >> 1) + 1) continue;
+                const unsigned char* rp = chunk + (min(max(i - 1 + r, 0), Hl - 1) - sbase) * ROW_BYTES;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    if (c < (kx >> 1) || c > ((kx + 1) >> 1) + 1) continue;
+                    v[r][c] = *reinterpret_cast<const f4v*>(rp + coff[c]);
+                }
+            }
+#pragma unroll
+            for (int ay = 0; ay < 2; ++ay)
+#pragma unroll
+                for (int bx = 0; bx < 2; ++bx) {
+                    const int uy = ay + ky, ux = bx + kx, r = uy >> 1, c = ux >> 1;
+                    const float w00 = hy[uy] * hx[ux], w01 = hy[uy] * lx[ux], w10 = ly[uy] * hx[ux], w11 = ly[uy] * lx[ux];
+                    f4v o = out[it][ay][bx];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        o[e] = fmaf(w11, v[r + 1][c + 1][e], fmaf(w10, v[r + 1][c][e], fmaf(w01, v[r][c + 1][e], fmaf(w00, v[r][c][e], o[e]))));
+                    asm volatile("" : "+v"(o));                   // pins the sum HERE: the compiler otherwise sinks all nine taps' arithmetic below the last barrier,
+                    out[it][ay][bx] = o;                          // next to the stores, and spills everything it read from the chunks meanwhile
+                }
+            __builtin_amdgcn_sched_barrier(0);                    // one cell's neighbours in flight at a time: the scheduler would hoist all eight cells' reads and spill
+        }
+    };
+    tap.template operator()<0>(); tap.template operator()<1>(); tap.template operator()<2>();
+    tap.template operator()<3>(); tap.template operator()<4>(); tap.template operator()<5>();
+    tap.template operator()<6>(); tap.template operator()<7>(); tap.template operator()<8>();
+
+    // ---- bias, activation, SH store
+    f4v bv = (f4v)(0.0f);
+    if (a.bias) bv = *reinterpret_cast<const f4v*>(a.bias + col0 + quad * 4);
+    const int Ho = 2 * Hl, Wo = 2 * WL;
+#pragma unroll
+    for (int it = 0; it < 8; ++it)
+#pragma unroll
+        for (int ay = 0; ay < 2; ++ay)
+#pragma unroll
+            for (int bx = 0; bx < 2; ++bx) {
+                f4v o = out[it][ay][bx] + bv;
+                if (a.act == OMNI_ACT_RELU) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
+                const int oy = 2 * (r0 + ib + it) + ay, ox = 2 * j + bx;
+                act_store4<true>(a.dst, (((size_t)m * Ho + oy) * Wo + ox) * a.Cout + col0 + quad * 4, o);
+            }
+}
+
+}  // namespace
+
+OMNI_SH_OVERFLOW_ACCESSOR(omni_sh_overflow_up2_taps)      // this translation unit's copy of the sticky range flag
+
+// dst = act(conv3x3(pad 1)(bilinear 2x up-sampling of src) + bias) from the nine 1x1 tap products on the low-resolution map, one launch (see the head of this file).
+// src SH [M, Hl, Wl, 64]; wt16t: the tap-major f16x3 weights [9 * Cout][64] (row t*Cout + co = W[co][t][:]); dst SH [M, 2Hl, 2Wl, Cout]; fmt: 1 (SH result, f16x3;
+// bit 2, the latency plan of a lone panorama, is accepted and ignored: one form for every batch).
+extern "C" int omni_conv3x3_up2_taps_sh_f16x3(const void* src, const void* wt16t, const float* bias, void* dst, int fmt,
+                                              int M, int Hl, int Wl, int C, int Cout, int act, omni_stream_t stream)
+{
+    if (!src || !wt16t || !dst) OMNI_FAIL(OMNI_ERR_INVALID, "omni_conv3x3_up2_taps_sh: null pointer");
+    if (M <= 0 || Hl <= 0 || Wl <= 0 || C <= 0 || C % 32 || Cout <= 0 || Cout % 32) OMNI_FAIL(OMNI_ERR_INVALID, "omni_conv3x3_up2_taps_sh: bad shape (channels must be multiples of 32)");
+    if ((uintptr_t)src % 16 || (uintptr_t)wt16t % 16 || (uintptr_t)bias % 16 || (uintptr_t)dst % 16) OMNI_FAIL(OMNI_ERR_INVALID, "omni_conv3x3_up2_taps_sh: tensors must be 16-byte aligned");
+    const bool bands = Wl == 32 && Hl % 8 == 0, image = Wl == 16 && Hl == 16;
+    if ((fmt & ~4) != 1 || C != 64 || Cout != 64 || !(bands || image) || (act != OMNI_ACT_NONE && act != OMNI_ACT_RELU))
+        OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_conv3x3_up2_taps_sh: serves f16x3 with an SH result, 64 -> 64 channels, Wl = 32 with Hl % 8 == 0 or 16 x 16 maps, no activation or ReLU");
+    if ((long long)M * Hl * Wl * 4 >= (1ll << 31)) OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_conv3x3_up2_taps_sh: tensor too large for 32-bit indices");
+    TapsArgs a;
+    a.src = src; a.wt = wt16t; a.bias = bias; a.dst = dst; a.M = M; a.Hl = Hl; a.Cout = Cout; a.act = act;
+    const unsigned ntn = (unsigned)(Cout / 32);
+    if (bands) hipLaunchKernelGGL((up2_taps_fused_kernel<32, 8, 1>), dim3((unsigned)M * (unsigned)(Hl / 8) * ntn), dim3(256), 0, (hipStream_t)stream, a);
+    else       hipLaunchKernelGGL((up2_taps_fused_kernel<16, 16, 0>), dim3((unsigned)M * ntn), dim3(256), 0, (hipStream_t)stream, a);
+    OMNI_HIP(hipGetLastError());
+    return OMNI_OK;
+}

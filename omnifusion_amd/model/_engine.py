@@ -121,9 +121,11 @@ class Engine:
         for name in ("de_conv0_0", "de_conv0_1", "de_conv1_0", "de_conv1_1", "de_conv2_0", "de_conv2_1",
                      "de_conv3_0", "de_conv3_1", "de_conv4_0"):
             convbn(name, name + ".conv", name + ".bn")
-        for name in ("de_conv0_0", "de_conv1_0"):               # the same folded weights tap-major, [9*Cout][Cin] with row t*Cout + co = W[co][t][:]: the
-            w, _ = self._fold(sd, name + ".conv", name + ".bn")   # operand of the nine 1x1 tap products on the low-resolution map (_up_conv_taps)
-            W[name + ".taps.w16"] = split_weights_f16x3(w.permute(2, 3, 0, 1).reshape(9 * w.shape[0], w.shape[1]).to(torch.float32)).to(dev)
+        for name, op in (("de_conv0_0", ".taps.w16"), ("de_conv1_0", ".taps.w16"), ("de_conv2_0", ".tapsf.w16"), ("de_conv3_0", ".tapsf.w16")):
+            # the same folded weights tap-major, [9*Cout][Cin] with row t*Cout + co = W[co][t][:]: the operand of the nine 1x1 tap products on the
+            # low-resolution map — `.taps.w16` for the two-launch stages (_up_conv_taps), `.tapsf.w16` for the one-launch stages (_up_conv with taps_fused)
+            w, _ = self._fold(sd, name + ".conv", name + ".bn")
+            W[name + op] = split_weights_f16x3(w.permute(2, 3, 0, 1).reshape(9 * w.shape[0], w.shape[1]).to(torch.float32)).to(dev)
         down = "down1" if self.iterative else "down"
         W["down.w"] = f(sd[down + ".weight"].reshape(32, 512)); W["down.b"] = f(sd[down + ".bias"])
         W["down.w16"] = split_weights_f16x3(sd[down + ".weight"].reshape(32, 512)).to(dev)
@@ -351,6 +353,13 @@ class Engine:
         """conv3x3(upsample2x(x)) — `F.interpolate` + the stage's first ConvBnReLU (:279-301); one kernel when the output is a
         multiple of 4 x 32 pixels (same bits as the two-kernel form)."""
         Ho, Wo = 2 * H, 2 * Wd
+        if (key in self.taps_fused and self.sh and self.terms == 3 and not out_f32 and C == 64 and Cout == 64
+                and ((Wd == 32 and H % 8 == 0) or (H == 16 and Wd == 16))):
+            if out is None:
+                out = torch.empty((M, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
+            _lib.check(_lib.load().omni_conv3x3_up2_taps_sh_f16x3(_p(x), _p(self.w[key + ".tapsf.w16"]), _p(self.w[key + ".b"]), _p(out), 1,
+                                                                  M, H, Wd, C, Cout, act, self._s), "up+conv (tap products) " + key)
+            return out
         if self.sh and self.fuse_up and Wo % 32 == 0 and Ho % 4 == 0:
             if out is None:
                 out = torch.empty((M, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
@@ -366,7 +375,16 @@ class Engine:
     # de_conv0_0 3980 -> 4050 panoramas/s, every round above every round without; de_conv1_0 3980 -> 3975, its 42 MB of fp32 tap products
     # cost what the matrix work saves, so it stays on the up-sampling path (profiles/EXPERIMENTS.md, r13a).  f16x3 only (the other modes'
     # pinned accuracy figures stay); never a function of the batch size.  Results equal the two-kernel form to rounding (< 1e-5 m of depth).
+    # (The wider stages de_conv2_0 / de_conv3_0 would write 85 / 340 MB of tap products: they take the one-launch form, `taps_fused` below.)
     taps_first = frozenset(("de_conv0_0",))
+    # The 64 -> 64 stages de_conv2_0 (16 x 16 -> 32 x 32) and de_conv3_0 (32 x 32 -> 64 x 64) take the same identity in ONE launch (omni_conv3x3_up2_taps_sh_f16x3,
+    # csrc/omni_conv_up2_taps.hip): the tap products are formed, parked in LDS and summed inside a block, so their fp32 values — 85 MB and 340 MB at 144 patches —
+    # never reach memory.  The set of layer keys that take this path in `_up_conv`; the operands `<key>.tapsf.w16` (packed like `.taps.w16`) exist for both stages.  f16x3 with an SH result
+    # only; never a function of the batch size or of the latency plan.  tools/taps_fused_ab.py, three forwards of 8 panoramas in
+    # flight: none 4218, de_conv3_0 4261, de_conv2_0 4236, both 4278 panoramas/s, every round of each case above every round without — although either launch
+    # ALONE is no faster than the halo kernel (174 -> 178 us, 53 -> 61 us): the region runs at the power cap and the stages issue 0.375x / 0.25x the matrix
+    # instructions (profiles/EXPERIMENTS.md, r25a).
+    taps_fused = frozenset(("de_conv2_0", "de_conv3_0"))
 
     def _up_conv_taps(self, x, key, M, H, Wd, C, Cout, act):
         """conv3x3(upsample2x(x)) for the stages in `taps_first`: tap GEMM on the low-resolution map + omni_up2_tapsum_sh; every other
