@@ -5,6 +5,9 @@ Everything numeric runs in the HIP library; PyTorch only owns the device buffers
 allocator), the stream and — once per `load_state_dict` — the constant folding of the weights
 (BatchNorm -> conv, the input-independent `mlp_points` branch of the single-pass model).
 
+`Engine` holds what outlives a forward: packed weights, switches, the split-K workspace and `last`.  A forward's stream, batch size and what
+follows from them live in a `_Forward`, made at the top of `Engine.network` / `Engine.transformer`; the launching helpers are its methods.
+
 Reference: model/spherical_model.py:238-314 (single pass), model/spherical_model_iterative.py:308-456.
 """
 import ctypes
@@ -18,7 +21,7 @@ from ..equi_pers.equi2pers_v3 import equi2pers_patches, equi2pers_aux, pair, _NP
 from ..equi_pers.pers2equi_v3 import pers2equi, pers2equi_conf
 
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
-_LAYERS = [("layer1", 3, 1), ("layer2", 4, 2), ("layer3", 6, 2), ("layer4", 3, 2)]
+_LAYERS = [("layer1", 3, 1, 64), ("layer2", 4, 2, 128), ("layer3", 6, 2, 256), ("layer4", 3, 2, 512)]     # name, blocks, stride of the first, width
 _BN_EPS = 1e-5
 PRECISIONS = ("f16x3", "f16x1", "fp32")
 
@@ -44,6 +47,41 @@ def strip_module_prefix(sd):
 
 
 class Engine:
+    # ------------------------------------------------------------------ switches (class attributes: tests, tools and bench.py set them on the class)
+    NOMINAL_BATCH = 8
+    SINGLE_BATCH = 4           # the batch a lone panorama plans its split-K factors for (latency_plan)
+    latency_plan = True
+    rows_gemm = True           # ... and its transformer GEMMs (18 rows) take the register-streaming kernel
+    fuse_fc2_ln = os.environ.get("OMNI_FUSE_FC2_LN", "1") != "0"   # fc2's split-K second pass also applies the LayerNorm that follows (one launch fewer per layer, same bits)
+    fc2_slices = int(os.environ.get("OMNI_FC2_SLICES", "4"))       # a lone panorama: fc2 in this many K slices (1: off) — 16 blocks stream its 4 MB of weights otherwise
+    fuse_ln = os.environ.get("OMNI_FUSE_LN", "1") != "0"   # a lone panorama: LayerNorm inside the following rows GEMM (one launch instead of two, same bits)
+    fold_point_feat = True     # `layer1 + point_feat` inside layer1's last convolution (one rounding to the SH format instead of two: results move by ~1e-7)
+    fuse_up = True             # decoder: up-sampling computed inside the following convolution's halo fill where the shape allows
+    # Decoder stages that multiply BEFORE up-sampling: conv3x3(up2(x)) = tap sum of up2(W_t . x), nine 1x1 products on a quarter of the pixels
+    # (a quarter of the stage's matrix instructions; the up-sampled tensor never exists).  The set of layer keys that take this path; the
+    # operands exist for de_conv0_0 (K = 512) and de_conv1_0 (K = 128).  tools/taps_ab.py, three forwards of 8 panoramas in flight:
+    # de_conv0_0 3980 -> 4050 panoramas/s, every round above every round without; de_conv1_0 3980 -> 3975, its 42 MB of fp32 tap products
+    # cost what the matrix work saves, so it stays on the up-sampling path (profiles/EXPERIMENTS.md, r13a).  f16x3 only (the other modes'
+    # pinned accuracy figures stay); never a function of the batch size.  Results equal the two-kernel form to rounding (< 1e-5 m of depth).
+    # (The wider stages de_conv2_0 / de_conv3_0 would write 85 / 340 MB of tap products: they take the one-launch form, `taps_fused` below.)
+    taps_first = frozenset(("de_conv0_0",))
+    # The 64 -> 64 stages de_conv2_0 (16 x 16 -> 32 x 32) and de_conv3_0 (32 x 32 -> 64 x 64) take the same identity in ONE launch (omni_conv3x3_up2_taps_sh_f16x3,
+    # csrc/omni_conv_up2_taps.hip): the tap products are formed, parked in LDS and summed inside a block, so their fp32 values — 85 MB and 340 MB at 144 patches —
+    # never reach memory.  The set of layer keys that take this path in `_Forward.up_conv`; the operands `<key>.tapsf.w16` (packed like `.taps.w16`) exist for both stages.  f16x3 with an SH result
+    # only; never a function of the batch size or of the latency plan.  tools/taps_fused_ab.py, three forwards of 8 panoramas in
+    # flight: none 4218, de_conv3_0 4261, de_conv2_0 4236, both 4278 panoramas/s, every round of each case above every round without — although either launch
+    # ALONE is no faster than the halo kernel (174 -> 178 us, 53 -> 61 us): the region runs at the power cap and the stages issue 0.375x / 0.25x the matrix
+    # instructions (profiles/EXPERIMENTS.md, r25a).
+    taps_fused = frozenset(("de_conv2_0", "de_conv3_0"))
+    # de_conv4_0 and the two heads in one pass (omni_conv3x3_up2_heads_sh_f16x3): the decoder's last feature map is never written.  False: the two
+    # kernels (fp32 heads; `Engine.last["de_conv4_0"]` then holds that map — the G6 check-point test reads it).  The outputs agree to ~1e-6 relative.
+    fuse_heads = os.environ.get("OMNI_FUSE_HEADS", "1") != "0"
+    # Passes of a few panoramas through the widest stages (same kernels, same bits) were worth +1.3 % with three forwards in flight while the
+    # up-sampled tensors still went through HBM; since the up-sampling is computed inside the convolution (fuse_up) they change nothing
+    # (tools/chunk_ab.py: 3515 vs 3517 panoramas/s), so the default is the whole batch at once.
+    tail_chunk = 0             # panoramas per pass through the decoder's two widest stages (0: the whole batch at once)
+    front_chunk = 0            # ... and through stem -> max-pool
+
     def __init__(self, nrows, npatches, patch_size, fov, iterative, precision=None):
         self.nrows, self.npatches, self.iterative = nrows, npatches, iterative
         self.patch_size = pair(patch_size)
@@ -52,6 +90,7 @@ class Engine:
             raise ValueError("square patches only")
         self.w = None          # packed weights (device tensors)
         self.device = None
+        self._ws, self._ws_retired = None, []      # the split-K workspace (`_workspace`)
         # "f16x3": conv products on the fp16 matrix cores with split operands (fp32-class accuracy, 3/16 of the MFMA time),
         # activations between the convolutions in the split-half layout; "f16x1": the same layout and weights, but every convolution
         # of the encoder / decoder multiplies the hi halves only (one MFMA per product block, ~1e-3 relative; the transformer's
@@ -75,8 +114,8 @@ class Engine:
         return 8 if self.terms == 1 else 0
 
     def lane(self):
-        """A second execution context over the SAME packed weights (own split-K workspace and per-call state): the model
-        runs the two halves of a batch on two streams so that one half's kernel tails overlap the other half's work."""
+        """A second execution context over the SAME packed weights (own split-K workspace): the model runs the two halves
+        of a batch on two streams so that one half's kernel tails overlap the other half's work."""
         e = Engine(self.nrows, self.npatches, self.patch_size, self.fov, self.iterative, precision=self.precision)
         e.w, e.device, e.head_bias = self.w, self.device, getattr(self, "head_bias", None)
         return e
@@ -111,7 +150,7 @@ class Engine:
             wg = self._gemm_layout(w).to(torch.float32)
             W[key + ".w"] = f(wg); W[key + ".b"] = f(b)
             W[key + ".w16"] = split_weights_f16x3(wg).to(dev)
-        for lname, nblk, _ in _LAYERS:
+        for lname, nblk, _, _ in _LAYERS:
             for i in range(nblk):
                 p = f"{lname}.{i}"
                 convbn(p + ".c1", p + ".conv1", p + ".bn1")
@@ -123,7 +162,7 @@ class Engine:
             convbn(name, name + ".conv", name + ".bn")
         for name, op in (("de_conv0_0", ".taps.w16"), ("de_conv1_0", ".taps.w16"), ("de_conv2_0", ".tapsf.w16"), ("de_conv3_0", ".tapsf.w16")):
             # the same folded weights tap-major, [9*Cout][Cin] with row t*Cout + co = W[co][t][:]: the operand of the nine 1x1 tap products on the
-            # low-resolution map — `.taps.w16` for the two-launch stages (_up_conv_taps), `.tapsf.w16` for the one-launch stages (_up_conv with taps_fused)
+            # low-resolution map — `.taps.w16` for the two-launch stages (taps_first), `.tapsf.w16` for the one-launch stages (taps_fused) of `_Forward.up_conv`
             w, _ = self._fold(sd, name + ".conv", name + ".bn")
             W[name + op] = split_weights_f16x3(w.permute(2, 3, 0, 1).reshape(9 * w.shape[0], w.shape[1]).to(torch.float32)).to(dev)
         down = "down1" if self.iterative else "down"
@@ -181,331 +220,76 @@ class Engine:
             _lib.check(_lib.load().omni_sh_overflow(ctypes.byref(flag), 1 if reset else 0), "sh_overflow")
         return bool(flag.value)
 
-    # ------------------------------------------------------------------ operator shims
-    def _conv(self, x, key, M, H, Wd, C1, Cout, k, stride, pad, act, x2=None, C2=0, res=None, bias=True, out_f32=False, out=None, post=None):
-        """One convolution (+ folded BN, bias, residual, activation).  In the f16x3 mode the activations x, x2, res and
-        the result are split-half (SH) tensors (csrc/omni_sh.h) unless out_f32 asks for a plain fp32 NHWC result."""
-        lib = _lib.load()
-        Ho = (H + 2 * pad - k) // stride + 1
-        Wo = (Wd + 2 * pad - k) // stride + 1
-        if out is None:
-            out = torch.empty((M, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
-        S, ws, nb = self._splitk(M * Ho * Wo, Cout, k * k * (C1 + C2) // 32, x.device, shape=(k, k, stride, pad, H, Wd))
-        b = _p(self.w[key + ".b"]) if bias else None
-        late_post = None
-        if post is not None and (S > 1 or not self.sh or out_f32):
-            # the fused `+ post` epilogue exists for un-split SH launches only (omni_conv2d_sh_f16x3_post_ws rejects splitk > 1): a shape
-            # whose plan splits K (few rows: small patches, nrows = 3, a lone panorama) adds it as a pass of its own instead
-            late_post, post = post, None
-        if self.sh and post is not None:                            # `+ post` after the activation, inside the epilogue (SH mode, never split)
-            rc = lib.omni_conv2d_sh_f16x3_post_ws(_p(x), _p(x2), _p(self.w[key + ".w16"]), b, _p(res), _p(out), (0 if out_f32 else 1) | self._x1,
-                                                  M, H, Wd, C1, C2, Cout, k, k, stride, pad, act, S, _p(ws), nb,
-                                                  _p(post), post.numel(), self._s)
-        elif self.sh:
-            lat = 4 if (self._bs == 1 and self.latency_plan) else 0     # fmt bit 2: a lone panorama keeps the im2col tiles for 16-wide images
-            rc = lib.omni_conv2d_sh_f16x3_ws(_p(x), _p(x2), _p(self.w[key + ".w16"]), b, _p(res), _p(out), (0 if out_f32 else 1) | lat | self._x1,
-                                             M, H, Wd, C1, C2, Cout, k, k, stride, pad, act, S, _p(ws), nb, self._s)
-        else:
-            rc = lib.omni_conv2d_nhwc_f32_ws(_p(x), _p(x2), _p(self.w[key + ".w"]), b, _p(res), _p(out), M, H, Wd, C1, C2, Cout,
-                                             k, k, stride, pad, act, S, _p(ws), nb, self._s)
-        _lib.check(rc, "conv2d " + key)
-        if late_post is not None:
-            _lib.check((lib.omni_add_period_f32 if (out_f32 or not self.sh) else lib.omni_add_period_sh)(   # an fp32 NHWC output is never split-half
-                _p(out), _p(late_post), out.numel(), late_post.numel(), self._s), "add post " + key)
-        return out
-
-    NOMINAL_BATCH = 8
-    SINGLE_BATCH = 4           # the batch a lone panorama plans its split-K factors for (latency_plan)
-    latency_plan = True
-    rows_gemm = True           # ... and its transformer GEMMs (18 rows) take the register-streaming kernel
-
-    def _splitk(self, rows, Cout, ksteps, device, shape=None):
-        """Split factor planned for a NOMINAL batch (not the actual one), so that the K summation order — and with it
-        every output bit — is the same whether a panorama is processed inside a batch of 2 or of 64 (image-sharded
-        multi-GPU runs reproduce single-GPU results bit for bit).  A LONE panorama (BASELINE cfg 2) is latency-bound —
-        every layer is one round of at most one block per CU and costs the length of its K loop — and plans for
-        SINGLE_BATCH instead: deeper splits on layer3/layer4/decoder, 1.28 -> 1.13 ms per forward, results equal to the
-        batched ones to 2e-5 abs instead of bit for bit (`Engine.latency_plan = False` restores the one plan for all)."""
-        plan_batch = self.SINGLE_BATCH if (self._bs == 1 and self.latency_plan) else self.NOMINAL_BATCH
-        rows_plan = rows // self._bs * plan_batch
-        lib = _lib.load()
-        S = int(lib.omni_conv2d_splitk_plan(rows_plan, Cout, ksteps))
-        if S <= 1:
-            return 1, None, 0
-        ws, nb = self._workspace(S * rows * Cout * 4, device)
-        return S, ws, nb
-
     def _workspace(self, nbytes, device):
         """split-K scratch: one buffer reused by every launch of the stream (launches are stream-ordered)"""
         nbytes = int(nbytes)
         if nbytes == 0:
             return None, 0
-        ws = getattr(self, "_ws", None)
+        ws = self._ws
         if ws is None or ws.numel() * 4 < nbytes or ws.device != device:
             if ws is not None:                   # a hipGraph captured earlier (graphed()) still replays into the old buffer:
-                self._ws_retired = getattr(self, "_ws_retired", []) + [ws]       # keep it alive for the engine's lifetime
+                self._ws_retired.append(ws)      # keep it alive for the engine's lifetime
             self._ws = ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device)
         return ws, ws.numel() * 4
 
-    def _gemm(self, x, wkey, bkey, rows, K, Nout, act=ACT_NONE, res=None):
-        lib = _lib.load()
-        out = torch.empty((rows, Nout), dtype=torch.float32, device=x.device)
-        S, ws, nb = self._splitk(rows, Nout, K // 32, x.device)
-        rc = lib.omni_conv2d_nhwc_f32_ws(_p(x), None, _p(self.w[wkey]), _p(self.w[bkey]) if bkey else None, _p(res), _p(out),
-                                         rows, 1, 1, K, 0, Nout, 1, 1, 1, 0, act, S, _p(ws), nb, self._s)
-        _lib.check(rc, "gemm " + wkey)
-        return out
-
-    def _rows_weights(self, w16key, Nout, K):
-        """the transformer matrix `w16key` in the fragment order of omni_gemm_rows_sh_f16x3 (made on first use: only single-panorama
-        forwards need the second copy, 75 MB for the six layers)"""
-        key = w16key + ".rows"
-        w = self.w.get(key)
-        if w is None:
-            src = self.w[w16key]
-            w = torch.empty_like(src)
-            _lib.check(_lib.load().omni_gemm_rows_pack(_p(src), _p(w), Nout, K, self._s), "gemm_rows_pack")
-            if not torch.cuda.is_current_stream_capturing():     # engines on other streams share the dict: hand over a finished tensor
-                torch.cuda.current_stream(src.device).synchronize()
-            self.w[key] = w
-        return w
-
-    def _gemm_sh(self, x, w16key, bkey, rows, K, Nout, act=ACT_NONE, res=None, out_sh=False):
-        """f16x3 GEMM on an SH activation matrix x [rows, K]; res (fp32) and bias optional; result fp32 or SH"""
-        lib = _lib.load()
-        out = torch.empty((rows, Nout), dtype=torch.float32, device=x.device)
-        if self._bs == 1 and self.latency_plan and self.rows_gemm and rows <= 32 and K in (512, 2048):      # a lone panorama: the register-streaming form
-            _lib.check(lib.omni_gemm_rows_sh_f16x3(_p(x), _p(self._rows_weights(w16key, Nout, K)), _p(self.w[bkey]) if bkey else None, _p(res), _p(out),
-                                                   1 if out_sh else 0, rows, K, Nout, act, self._s), "gemm " + w16key)
-            return out
-        S, ws, nb = (1, None, 0) if K <= 512 else self._splitk(rows, Nout, K // 32, x.device)
-        rc = lib.omni_conv2d_sh_f16x3_ws(_p(x), None, _p(self.w[w16key]), _p(self.w[bkey]) if bkey else None, _p(res), _p(out),
-                                         (1 if out_sh else 0) | 2, rows, 1, 1, K, 0, Nout, 1, 1, 1, 0, act, S, _p(ws), nb, self._s)
-        _lib.check(rc, "gemm " + w16key)
-        return out
-
-    fuse_fc2_ln = os.environ.get("OMNI_FUSE_FC2_LN", "1") != "0"   # fc2's split-K second pass also applies the LayerNorm that follows (one launch fewer per layer, same bits)
-
-    fc2_slices = int(os.environ.get("OMNI_FC2_SLICES", "4"))       # a lone panorama: fc2 in this many K slices (1: off) — 16 blocks stream its 4 MB of weights otherwise
-
-    def _fc2_ln(self, h, w16key, bkey, rows, tok, nxt):
-        """tok + fc2(h).  Batches: where fc2 runs split-K, the LayerNorm `nxt` = (weight key, bias key, eps, SH result?) of the result in the same second
-        pass (omni_gemm_sh_f16x3_ln512_ws).  A lone panorama: fc2 as K slices whose sum the NEXT kernel forms (omni_gemm_rows_slices_sh_f16x3).
-        Returns (new tok or None, LayerNorm(new tok) or None, pending K slices or None)."""
-        lone = self._bs == 1 and self.latency_plan and self.rows_gemm and rows <= 32
-        if lone and self.fc2_slices > 1 and self.fuse_ln:
-            S = self.fc2_slices
-            parts = torch.empty((S, rows, 512), dtype=torch.float32, device=h.device)
-            _lib.check(_lib.load().omni_gemm_rows_slices_sh_f16x3(_p(h), _p(self._rows_weights(w16key, 512, 2048)), _p(parts), rows, 2048, 512, S, self._s), "gemm slices " + w16key)
-            return None, None, (parts, S, bkey, tok)
-        S, ws, nb = (1, None, 0) if lone else self._splitk(rows, 512, 2048 // 32, h.device)
-        if lone or S <= 1 or not self.fuse_fc2_ln:
-            return self._gemm_sh(h, w16key, bkey, rows, 2048, 512, res=tok), None, None
-        wk, bk, eps, out_sh = nxt
-        out, y = torch.empty((rows, 512), dtype=torch.float32, device=h.device), torch.empty((rows, 512), dtype=torch.float32, device=h.device)
-        rc = _lib.load().omni_gemm_sh_f16x3_ln512_ws(_p(h), _p(self.w[w16key]), _p(self.w[bkey]), _p(tok), _p(out), _p(self.w[wk]), _p(self.w[bk]), eps,
-                                                     _p(y), 1 if out_sh else 0, rows, 2048, S, _p(ws), nb, self._s)
-        _lib.check(rc, "gemm+ln " + w16key)
-        return out, y, None
-
-    def _ln_gemm_parts(self, pending, lnw, lnb, eps, w16key, rows, Nout):
-        """the next block's norm1 + qkv on a token matrix that still is fc2's K slices: (tok, qkv)"""
-        parts, S, bkey, res_tok = pending
-        tok = torch.empty((rows, 512), dtype=torch.float32, device=parts.device)
-        out = torch.empty((rows, Nout), dtype=torch.float32, device=parts.device)
-        rc = _lib.load().omni_gemm_rows_ln_parts_sh_f16x3(_p(parts), S, _p(self.w[bkey]), _p(res_tok), _p(tok), _p(self.w[lnw]), _p(self.w[lnb]), eps,
-                                                          _p(self._rows_weights(w16key, Nout, 512)), None, _p(out), 0, rows, Nout, ACT_NONE, self._s)
-        _lib.check(rc, "ln+gemm (slices) " + w16key)
-        return tok, out
-
-    fuse_ln = os.environ.get("OMNI_FUSE_LN", "1") != "0"   # a lone panorama: LayerNorm inside the following rows GEMM (one launch instead of two, same bits)
-
-    def _ln_gemm_sh(self, x, lnw, lnb, eps, w16key, bkey, rows, Nout, act=ACT_NONE, out_sh=False):
-        """LayerNorm(512) + GEMM (K = 512) on the fp32 token matrix x [rows, 512]: one launch for a lone panorama, else the two kernels"""
-        if self._bs == 1 and self.latency_plan and self.rows_gemm and self.fuse_ln and rows <= 32:
-            lib = _lib.load()
-            out = torch.empty((rows, Nout), dtype=torch.float32, device=x.device)
-            _lib.check(lib.omni_gemm_rows_ln_sh_f16x3(_p(x), _p(self.w[lnw]), _p(self.w[lnb]), eps, _p(self._rows_weights(w16key, Nout, 512)),
-                                                      _p(self.w[bkey]) if bkey else None, None, _p(out), 1 if out_sh else 0, rows, Nout, act, self._s), "ln+gemm " + w16key)
-            return out
-        return self._gemm_sh(self._ln_sh(x, lnw, lnb, rows, eps), w16key, bkey, rows, 512, Nout, act=act, out_sh=out_sh)
-
-    def _ln_sh(self, x, wk, bk, rows, eps):
-        y = torch.empty_like(x)
-        _lib.check(_lib.load().omni_layernorm512_sh(_p(x), _p(self.w[wk]), _p(self.w[bk]), _p(y), rows, eps, self._s), "layernorm")
-        return y
-
-    def _ln(self, x, wk, bk, rows, eps):
-        y = torch.empty_like(x)
-        _lib.check(_lib.load().omni_layernorm512_f32(_p(x), _p(self.w[wk]), _p(self.w[bk]), _p(y), rows, eps, self._s), "layernorm")
-        return y
-
-    def _up(self, x, M, H, Wd, C, Ho, Wo):
-        y = torch.empty((M, Ho, Wo, C), dtype=torch.float32, device=x.device)
-        fn = _lib.load().omni_upsample_bilinear_sh if self.sh else _lib.load().omni_upsample_bilinear_f32
-        _lib.check(fn(_p(x), _p(y), M, H, Wd, C, Ho, Wo, self._s), "upsample")
-        return y
-
-    fold_point_feat = True     # `layer1 + point_feat` inside layer1's last convolution (one rounding to the SH format instead of two: results move by ~1e-7)
-    fuse_up = True             # decoder: up-sampling computed inside the following convolution's halo fill where the shape allows
-
-    def _up_conv(self, x, key, M, H, Wd, C, Cout, act, out_f32=False, out=None):
-        """conv3x3(upsample2x(x)) — `F.interpolate` + the stage's first ConvBnReLU (:279-301); one kernel when the output is a
-        multiple of 4 x 32 pixels (same bits as the two-kernel form)."""
-        Ho, Wo = 2 * H, 2 * Wd
-        if (key in self.taps_fused and self.sh and self.terms == 3 and not out_f32 and C == 64 and Cout == 64
-                and ((Wd == 32 and H % 8 == 0) or (H == 16 and Wd == 16))):
-            if out is None:
-                out = torch.empty((M, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
-            _lib.check(_lib.load().omni_conv3x3_up2_taps_sh_f16x3(_p(x), _p(self.w[key + ".tapsf.w16"]), _p(self.w[key + ".b"]), _p(out), 1,
-                                                                  M, H, Wd, C, Cout, act, self._s), "up+conv (tap products) " + key)
-            return out
-        if self.sh and self.fuse_up and Wo % 32 == 0 and Ho % 4 == 0:
-            if out is None:
-                out = torch.empty((M, Ho, Wo, Cout), dtype=torch.float32, device=x.device)
-            _lib.check(_lib.load().omni_conv3x3_up2_sh_f16x3(_p(x), _p(self.w[key + ".w16"]), _p(self.w[key + ".b"]), _p(out),
-                                                             (0 if out_f32 else 1) | (4 if (self._bs == 1 and self.latency_plan) else 0) | self._x1,
-                                                             M, H, Wd, C, Cout, act, self._s), "up+conv " + key)
-            return out
-        return self._conv(self._up(x, M, H, Wd, C, Ho, Wo), key, M, Ho, Wo, C, Cout, 3, 1, 1, act, out_f32=out_f32, out=out)
-
-    # Decoder stages that multiply BEFORE up-sampling: conv3x3(up2(x)) = tap sum of up2(W_t . x), nine 1x1 products on a quarter of the pixels
-    # (a quarter of the stage's matrix instructions; the up-sampled tensor never exists).  The set of layer keys that take this path; the
-    # operands exist for de_conv0_0 (K = 512) and de_conv1_0 (K = 128).  tools/taps_ab.py, three forwards of 8 panoramas in flight:
-    # de_conv0_0 3980 -> 4050 panoramas/s, every round above every round without; de_conv1_0 3980 -> 3975, its 42 MB of fp32 tap products
-    # cost what the matrix work saves, so it stays on the up-sampling path (profiles/EXPERIMENTS.md, r13a).  f16x3 only (the other modes'
-    # pinned accuracy figures stay); never a function of the batch size.  Results equal the two-kernel form to rounding (< 1e-5 m of depth).
-    # (The wider stages de_conv2_0 / de_conv3_0 would write 85 / 340 MB of tap products: they take the one-launch form, `taps_fused` below.)
-    taps_first = frozenset(("de_conv0_0",))
-    # The 64 -> 64 stages de_conv2_0 (16 x 16 -> 32 x 32) and de_conv3_0 (32 x 32 -> 64 x 64) take the same identity in ONE launch (omni_conv3x3_up2_taps_sh_f16x3,
-    # csrc/omni_conv_up2_taps.hip): the tap products are formed, parked in LDS and summed inside a block, so their fp32 values — 85 MB and 340 MB at 144 patches —
-    # never reach memory.  The set of layer keys that take this path in `_up_conv`; the operands `<key>.tapsf.w16` (packed like `.taps.w16`) exist for both stages.  f16x3 with an SH result
-    # only; never a function of the batch size or of the latency plan.  tools/taps_fused_ab.py, three forwards of 8 panoramas in
-    # flight: none 4218, de_conv3_0 4261, de_conv2_0 4236, both 4278 panoramas/s, every round of each case above every round without — although either launch
-    # ALONE is no faster than the halo kernel (174 -> 178 us, 53 -> 61 us): the region runs at the power cap and the stages issue 0.375x / 0.25x the matrix
-    # instructions (profiles/EXPERIMENTS.md, r25a).
-    taps_fused = frozenset(("de_conv2_0", "de_conv3_0"))
-
-    def _up_conv_taps(self, x, key, M, H, Wd, C, Cout, act):
-        """conv3x3(upsample2x(x)) for the stages in `taps_first`: tap GEMM on the low-resolution map + omni_up2_tapsum_sh; every other
-        case (mode, shape the tap-sum kernel does not serve) is the up-sampling kernel followed by the convolution."""
-        if key in self.taps_first and self.sh and self.terms == 3 and Cout % 32 == 0 and H * Wd <= 64:
-            y = self._conv(x, key + ".taps", M, H, Wd, C, 9 * Cout, 1, 1, 0, ACT_NONE, bias=False, out_f32=True)
-            out = torch.empty((M, 2 * H, 2 * Wd, Cout), dtype=torch.float32, device=x.device)
-            _lib.check(_lib.load().omni_up2_tapsum_sh(_p(y), _p(self.w[key + ".b"]), _p(out), M, H, Wd, Cout, act, self._s), "tap sum " + key)
-            return out
-        return self._conv(self._up(x, M, H, Wd, C, 2 * H, 2 * Wd), key, M, 2 * H, 2 * Wd, C, Cout, 3, 1, 1, act)
-
+    # ------------------------------------------------------------------ the two entry points of a forward
     def transformer(self, d, bs):
         """The transformer over the N tokens of each panorama (:263-268): position embedding, six blocks, encoder_norm.
         d: fp32 [bs*N, P/32, P/32, 32] (the `down` projection of layer4).  Returns the fp32 token matrix [bs*N, 512]."""
-        lib = _lib.load()
-        dev = d.device
-        self._s = _lib.stream_of(d)
-        self._bs = bs
-        N, P32 = self.npatches, self.patch_size[0] // 32
-        M = bs * N
-        sh = self.sh
-        new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-        tok = new(M, 512)
-        _lib.check(lib.omni_token_pack_f32(_p(d), _p(self.w["pos"]), _p(tok), M, N, P32 * P32, 32, self._s), "token_pack")
-        normed = None                                                # LayerNorm(tok) for the NEXT consumer, when fc2's second pass has already made it
-        pending = None                                               # a lone panorama: fc2's K slices (parts, slices, bias key, residual) — the next consumer adds them up
-        for i in range(6):
-            t = f"t{i}."
-            if sh:                                                   # LN / attention emit SH, the GEMMs run f16x3 from it
-                if pending is not None:
-                    tok, qkv = self._ln_gemm_parts(pending, t + "norm1.weight", t + "norm1.bias", 1e-5, t + "attn.qkv.w16", M, 1536)
-                    pending = None
-                elif normed is not None:
-                    qkv = self._gemm_sh(normed, t + "attn.qkv.w16", None, M, 512, 1536)
-                else:
-                    qkv = self._ln_gemm_sh(tok, t + "norm1.weight", t + "norm1.bias", 1e-5, t + "attn.qkv.w16", None, M, 1536)
-                att = new(M, 512)
-                _lib.check(lib.omni_attention_qkv_sh(_p(qkv), _p(att), bs, N, self._s), "attention")
-                tok = self._gemm_sh(att, t + "attn.proj.w16", t + "attn.proj.bias", M, 512, 512, res=tok)
-                h = self._ln_gemm_sh(tok, t + "norm2.weight", t + "norm2.bias", 1e-5, t + "mlp.fc1.w16", t + "mlp.fc1.bias", M, 2048, act=ACT_GELU, out_sh=True)
-                nxt = (f"t{i + 1}.norm1.weight", f"t{i + 1}.norm1.bias", 1e-5, True) if i < 5 else ("enc_norm.w", "enc_norm.b", 1e-6, False)
-                tok, normed, pending = self._fc2_ln(h, t + "mlp.fc2.w16", t + "mlp.fc2.bias", M, tok, nxt)
-                continue
-            y = self._ln(tok, t + "norm1.weight", t + "norm1.bias", M, 1e-5)
-            q = self._gemm(y, t + "attn.q.weight", None, M, 512, 512)
-            kv = self._gemm(y, t + "attn.kv.weight", None, M, 512, 1024)
-            att = new(M, 512)
-            _lib.check(lib.omni_attention_f32(_p(q), _p(kv), _p(att), bs, N, self._s), "attention")
-            tok = self._gemm(att, t + "attn.proj.weight", t + "attn.proj.bias", M, 512, 512, res=tok)
-            y = self._ln(tok, t + "norm2.weight", t + "norm2.bias", M, 1e-5)
-            h = self._gemm(y, t + "mlp.fc1.weight", t + "mlp.fc1.bias", M, 512, 2048, act=ACT_GELU)
-            tok = self._gemm(h, t + "mlp.fc2.weight", t + "mlp.fc2.bias", M, 2048, 512, res=tok)
-        if sh and pending is not None:                                 # the last fc2's K slices: sum + bias + residual + encoder_norm in one kernel
-            parts, S, bkey, res_tok = pending
-            tok_sum, tok = new(M, 512), new(M, 512)
-            _lib.check(lib.omni_splitk_reduce_ln512(_p(parts), S, _p(self.w[bkey]), _p(res_tok), _p(tok_sum), _p(self.w["enc_norm.w"]), _p(self.w["enc_norm.b"]),
-                                                    1e-6, _p(tok), 0, M, self._s), "reduce+ln")
-        else:
-            tok = normed if (sh and normed is not None) else self._ln(tok, "enc_norm.w", "enc_norm.b", M, 1e-6)
-        return tok
+        return _Forward(self, bs, d).transformer(d)
 
-    # ------------------------------------------------------------------ network over the patch batch
     def network(self, patches, point_feat, bs, confidence, out=None):
         """patches: planar [bs, N, 3, P, P]; point_feat: NHWC [N or bs*N, P/4, P/4, 64].
         Returns (a, c) planar [bs, N, 1, P, P]: a = relu(pred) (* conf), c = sigmoid(weight) or None."""
-        lib = _lib.load()
-        dev = patches.device
-        self._s = _lib.stream_of(patches)
+        f = _Forward(self, bs, patches)
+        new, sh, wp = f.new, f.sh, f.wp                             # sh: activations between the convolutions are SH, else fp32 NHWC
         N, P = self.npatches, self.patch_size[0]
         M = bs * N
-        self._bs = bs
         P2, P4, P8, P16, P32 = P // 2, P // 4, P // 8, P // 16, P // 32
-        new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
         conv1 = new(M, P2, P2, 64)
-        sh = self.sh                                                # activations between the convolutions: SH or fp32 NHWC
         x = new(M, P4, P4, 64)
         pat = patches.view(M, 3, P, P)
+        if self.terms == 1 and P % 32:
+            raise ValueError(f"precision f16x1 needs a patch size that is a multiple of 32 (got {P})")
+        if sh and P % 32 == 0:
+            stem, stem_w = ("omni_stem_sh_f16x1" if f.x1 else "omni_stem_sh_f16x3"), "stem.w16"
+        else:
+            stem, stem_w = ("omni_stem_sh" if sh else "omni_stem_f32"), "stem.w"
         for m0, m1 in self._chunks(bs, N, self.front_chunk):        # stem -> maxpool per chunk: conv1 is re-read while still cached
-            Mc = m1 - m0
-            if self.terms == 1 and P % 32:
-                raise ValueError(f"precision f16x1 needs a patch size that is a multiple of 32 (got {P})")
-            if sh and P % 32 == 0:
-                _lib.check((lib.omni_stem_sh_f16x1 if self._x1 else lib.omni_stem_sh_f16x3)(_p(pat[m0:m1]), _p(self.w["stem.w16"]), _p(self.w["stem.b"]), _p(conv1[m0:m1]), Mc, P, self._s), "stem")
-            else:
-                _lib.check((lib.omni_stem_sh if sh else lib.omni_stem_f32)(_p(pat[m0:m1]), _p(self.w["stem.w"]), _p(self.w["stem.b"]),
-                                                                            _p(conv1[m0:m1]), Mc, P, self._s), "stem")
-            _lib.check((lib.omni_maxpool3x3s2_sh if sh else lib.omni_maxpool3x3s2_f32)(_p(conv1[m0:m1]), _p(x[m0:m1]), Mc, P2, P2, 64, self._s), "maxpool")
+            f.run(stem, "stem", _p(pat[m0:m1]), wp(stem_w), wp("stem.b"), _p(conv1[m0:m1]), m1 - m0, P)
+            f.run("omni_maxpool3x3s2_sh" if sh else "omni_maxpool3x3s2_f32", "maxpool", _p(conv1[m0:m1]), _p(x[m0:m1]), m1 - m0, P2, P2, 64)
         feats = {}
         cin, size = 64, P4
-        for lname, nblk, stride in _LAYERS:
-            cout = {"layer1": 64, "layer2": 128, "layer3": 256, "layer4": 512}[lname]
+        fold = sh and self.fold_point_feat                          # layer1 + point_feat (:258) in the epilogue of layer1's last convolution ...
+        for lname, nblk, stride, cout in _LAYERS:
             for i in range(nblk):
                 p = f"{lname}.{i}"
                 s = stride if i == 0 else 1
                 ident = x
                 if (p + ".ds.w") in self.w:
-                    ident = self._conv(x, p + ".ds", M, size, size, cin, cout, 1, s, 0, ACT_NONE)
-                y = self._conv(x, p + ".c1", M, size, size, cin, cout, 3, s, 1, ACT_RELU)
+                    ident = f.conv(x, p + ".ds", M, size, size, cin, cout, 1, s, 0, ACT_NONE)
+                y = f.conv(x, p + ".c1", M, size, size, cin, cout, 3, s, 1, ACT_RELU)
                 size = (size + 2 - 3) // s + 1
-                fold = sh and self.fold_point_feat and lname == "layer1" and i == nblk - 1     # layer1 + point_feat (:258) in the block's last epilogue
-                x = self._conv(y, p + ".c2", M, size, size, cout, cout, 3, 1, 1, ACT_RELU, res=ident, post=point_feat if fold else None)
+                post = point_feat if (fold and lname == "layer1" and i == nblk - 1) else None
+                x = f.conv(y, p + ".c2", M, size, size, cout, cout, 3, 1, 1, ACT_RELU, res=ident, post=post)
                 cin = cout
-            if lname == "layer1" and not (sh and self.fold_point_feat):                          # ... or as a pass of its own
-                _lib.check((lib.omni_add_period_sh if sh else lib.omni_add_period_f32)(
-                    _p(x), _p(point_feat), x.numel(), point_feat.numel(), self._s), "add point_feat")
+            if lname == "layer1" and not fold:                      # ... or as a pass of its own
+                f.run("omni_add_period_sh" if sh else "omni_add_period_f32", "add point_feat", _p(x), _p(point_feat), x.numel(), point_feat.numel())
             feats[lname] = x
         layer1, layer2, layer3, layer4 = (feats[k] for k in ("layer1", "layer2", "layer3", "layer4"))
         # ---- transformer over the N tokens of each panorama (:263-268)
         if 32 * P32 * P32 != 512:
             raise RuntimeError(f"patch size {P}: token dim {32 * P32 * P32} != 512 — the reference network only exists at "
                                "patch size 128 (SURVEY.md finding 0.1)")
-        d = self._conv(layer4, "down", M, P32, P32, 512, 32, 1, 1, 0, ACT_NONE, out_f32=True)
-        tok = self.transformer(d, bs)
-        _lib.check((lib.omni_add_hw_sh if sh else lib.omni_add_hw_f32)(_p(layer4), _p(tok), M, P32 * P32, 512, self._s), "token bias")
+        tok = f.transformer(f.conv(layer4, "down", M, P32, P32, 512, 32, 1, 1, 0, ACT_NONE, out_f32=True))
+        f.run("omni_add_hw_sh" if sh else "omni_add_hw_f32", "token bias", _p(layer4), _p(tok), M, P32 * P32, 512)
         # ---- decoder (:270-302); torch.cat is the two-source form of the conv
-        x = self._up_conv_taps(layer4, "de_conv0_0", M, P32, P32, 512, 256, ACT_RELU)
-        x = self._conv(x, "de_conv0_1", M, P16, P16, 256, 128, 3, 1, 1, ACT_RELU, x2=layer3, C2=256)
-        x = self._up_conv_taps(x, "de_conv1_0", M, P16, P16, 128, 128, ACT_RELU)
-        x = self._conv(x, "de_conv1_1", M, P8, P8, 128, 64, 3, 1, 1, ACT_RELU, x2=layer2, C2=128)
-        x = self._up_conv(x, "de_conv2_0", M, P8, P8, 64, 64, ACT_RELU)
-        x = self._conv(x, "de_conv2_1", M, P4, P4, 64, 64, 3, 1, 1, ACT_RELU, x2=layer1, C2=64)
+        x = f.up_conv(layer4, "de_conv0_0", M, P32, P32, 512, 256, ACT_RELU)
+        x = f.conv(x, "de_conv0_1", M, P16, P16, 256, 128, 3, 1, 1, ACT_RELU, x2=layer3, C2=256)
+        x = f.up_conv(x, "de_conv1_0", M, P16, P16, 128, 128, ACT_RELU)
+        x = f.conv(x, "de_conv1_1", M, P8, P8, 128, 64, 3, 1, 1, ACT_RELU, x2=layer2, C2=128)
+        x = f.up_conv(x, "de_conv2_0", M, P8, P8, 64, 64, ACT_RELU)
+        x = f.conv(x, "de_conv2_1", M, P4, P4, 64, 64, 3, 1, 1, ACT_RELU, x2=layer1, C2=64)
         # the two widest stages, optionally a few panoramas at a time (Engine.tail_chunk; no operator here mixes patches)
         a, c = out if out is not None else (new(bs, N, 1, P, P), new(bs, N, 1, P, P) if confidence else None)
         av, cv = a.view(M, P, P), c.view(M, P, P) if c is not None else None
@@ -513,30 +297,19 @@ class Engine:
         x_in, de4 = x, (None if fused else new(M, P, P, 32))
         for m0, m1 in self._chunks(bs, N, self.tail_chunk):
             Mc = m1 - m0
-            x = self._up_conv(x_in[m0:m1], "de_conv3_0", Mc, P4, P4, 64, 64, ACT_RELU)
-            x = self._conv(x, "de_conv3_1", Mc, P2, P2, 64, 32, 3, 1, 1, ACT_RELU, x2=conv1[m0:m1], C2=64)
+            x = f.up_conv(x_in[m0:m1], "de_conv3_0", Mc, P4, P4, 64, 64, ACT_RELU)
+            x = f.conv(x, "de_conv3_1", Mc, P2, P2, 64, 32, 3, 1, 1, ACT_RELU, x2=conv1[m0:m1], C2=64)
+            planes = (_p(av[m0:m1]), _p(cv[m0:m1]) if cv is not None else None, Mc, P, 1 if confidence else 0)
             if fused:                                                # de_conv4_0 + pred / weight_pred in one pass: its 302-MB output (8 panoramas) never exists
-                nb = int(lib.omni_up2_heads_scratch_bytes(Mc, P))
+                nb = int(f.lib.omni_up2_heads_scratch_bytes(Mc, P))
                 hs = new((nb + 3) // 4)
-                _lib.check((lib.omni_conv3x3_up2_heads_sh_f16x1 if self._x1 else lib.omni_conv3x3_up2_heads_sh_f16x3)(_p(x), _p(self.w["de_conv4_0.w16"]), _p(self.w["de_conv4_0.b"]), _p(self.w["heads.w16f"]),
-                                                               self.head_bias[0], self.head_bias[1], _p(hs), nb,
-                                                               _p(av[m0:m1]), _p(cv[m0:m1]) if cv is not None else None, Mc, P, 1 if confidence else 0, self._s), "up+conv+heads")
+                f.run("omni_conv3x3_up2_heads_sh_f16x1" if f.x1 else "omni_conv3x3_up2_heads_sh_f16x3", "up+conv+heads",
+                      _p(x), wp("de_conv4_0.w16"), wp("de_conv4_0.b"), wp("heads.w16f"), *self.head_bias, _p(hs), nb, *planes)
                 continue
-            self._up_conv(x, "de_conv4_0", Mc, P2, P2, 32, 32, ACT_RELU, out_f32=True, out=de4[m0:m1])
-            _lib.check(lib.omni_heads_f32(_p(de4[m0:m1]), _p(self.w["heads.w"]), self.head_bias[0], self.head_bias[1],
-                                          _p(av[m0:m1]), _p(cv[m0:m1]) if cv is not None else None, Mc, P, 1 if confidence else 0, self._s), "heads")
+            f.up_conv(x, "de_conv4_0", Mc, P2, P2, 32, 32, ACT_RELU, out_f32=True, out=de4[m0:m1])
+            f.run("omni_heads_f32", "heads", _p(de4[m0:m1]), wp("heads.w"), *self.head_bias, *planes)
         self.last = {"de_conv4_0": de4, "layer4": layer4}
         return a, c
-
-    # de_conv4_0 and the two heads in one pass (omni_conv3x3_up2_heads_sh_f16x3): the decoder's last feature map is never written.  False: the two
-    # kernels (fp32 heads; `Engine.last["de_conv4_0"]` then holds that map — the G6 check-point test reads it).  The outputs agree to ~1e-6 relative.
-    fuse_heads = os.environ.get("OMNI_FUSE_HEADS", "1") != "0"
-
-    # Passes of a few panoramas through the widest stages (same kernels, same bits) were worth +1.3 % with three forwards in flight while the
-    # up-sampled tensors still went through HBM; since the up-sampling is computed inside the convolution (fuse_up) they change nothing
-    # (tools/chunk_ab.py: 3515 vs 3517 panoramas/s), so the default is the whole batch at once.
-    tail_chunk = 0             # panoramas per pass through the decoder's two widest stages (0: the whole batch at once)
-    front_chunk = 0            # ... and through stem -> max-pool
 
     @staticmethod
     def _chunks(bs, N, per):
@@ -568,3 +341,226 @@ class Engine:
             raise ValueError("float32 input expected")
         if _NPATCH[self.nrows] != self.npatches:
             raise ValueError("npatches does not match nrows")
+
+
+class _Tokens:
+    """The token matrix between two transformer blocks of the SH path, in one of three states: plain (`tok`); with the LayerNorm its next
+    consumer needs already made by fc2's second pass (`normed`); or not summed yet (a lone panorama) — fc2's K slices `parts`, to which the
+    next kernel adds the bias `bkey` and the residual `tok`.  `_Forward.next_norm` is the one consumer."""
+    __slots__ = ("tok", "normed", "parts", "bkey")
+
+    def __init__(self, tok, normed=None, parts=None, bkey=None):
+        self.tok, self.normed, self.parts, self.bkey = tok, normed, parts, bkey
+
+
+class _Forward:
+    """What one call of Engine.network / Engine.transformer needs beside the engine: the stream and device of its input, the batch size, and
+    what follows from them.  Made at the top of the entry point and dropped at its end; the launching helpers are its methods, so none of
+    them can meet another forward's stream or batch."""
+
+    def __init__(self, engine, bs, like):
+        self.e, self.w, self.lib = engine, engine.w, _lib.load()
+        self.bs, self.M, self.stream, self.device = bs, bs * engine.npatches, _lib.stream_of(like), like.device
+        self.sh, self.x1 = engine.sh, engine._x1
+        # A LONE panorama (BASELINE cfg 2) is latency-bound — every layer is one round of at most one block per CU and costs the length of its
+        # K loop.  This is the one statement of that rule; everything a lone panorama does differently follows from the four names below.
+        self.lone = bs == 1 and engine.latency_plan
+        self.lat = 4 if self.lone else 0                            # fmt bit 2 of the SH convolutions: keep the im2col tiles for 16-wide images
+        self.rows_form = self.lone and engine.rows_gemm and self.M <= 32      # its transformer GEMMs (at most 32 rows) in the register-streaming kernels
+        self.plan_batch = engine.SINGLE_BATCH if self.lone else engine.NOMINAL_BATCH        # the batch `splitk` plans for
+
+    def run(self, name, label, *args):
+        """one library call on this forward's stream"""
+        _lib.check(getattr(self.lib, name)(*args, self.stream), label)
+
+    def new(self, *shape):
+        return torch.empty(shape, dtype=torch.float32, device=self.device)
+
+    def wp(self, key):
+        """pointer of a packed weight (None for no key)"""
+        return _p(self.w[key]) if key else None
+
+    # ------------------------------------------------------------------ convolutions
+    def splitk(self, rows, Cout, ksteps):
+        """Split factor planned for a NOMINAL batch (not the actual one), so that the K summation order — and with it
+        every output bit — is the same whether a panorama is processed inside a batch of 2 or of 64 (image-sharded
+        multi-GPU runs reproduce single-GPU results bit for bit).  A lone panorama plans for SINGLE_BATCH instead:
+        deeper splits on layer3/layer4/decoder, 1.28 -> 1.13 ms per forward, results equal to the batched ones to 2e-5 abs
+        instead of bit for bit (`Engine.latency_plan = False` restores the one plan for all)."""
+        S = int(self.lib.omni_conv2d_splitk_plan(rows // self.bs * self.plan_batch, Cout, ksteps))
+        if S <= 1:
+            return 1, None, 0
+        return (S,) + self.e._workspace(S * rows * Cout * 4, self.device)
+
+    def conv(self, x, key, M, H, Wd, C1, Cout, k, stride, pad, act, x2=None, C2=0, res=None, bias=True, out_f32=False, out=None, post=None):
+        """One convolution (+ folded BN, bias, residual, activation).  In the f16x3 mode the activations x, x2, res and
+        the result are split-half (SH) tensors (csrc/omni_sh.h) unless out_f32 asks for a plain fp32 NHWC result."""
+        Ho = (H + 2 * pad - k) // stride + 1
+        Wo = (Wd + 2 * pad - k) // stride + 1
+        if out is None:
+            out = self.new(M, Ho, Wo, Cout)
+        S, ws, nb = self.splitk(M * Ho * Wo, Cout, k * k * (C1 + C2) // 32)
+        late_post = None
+        if post is not None and (S > 1 or not self.sh or out_f32):
+            # the fused `+ post` epilogue exists for un-split SH launches only (omni_conv2d_sh_f16x3_post_ws rejects splitk > 1): a shape
+            # whose plan splits K (few rows: small patches, nrows = 3, a lone panorama) adds it as a pass of its own instead
+            late_post, post = post, None
+        tensors = (_p(x), _p(x2), self.wp(key + (".w16" if self.sh else ".w")), self.wp(key + ".b") if bias else None, _p(res), _p(out))
+        shape = (M, H, Wd, C1, C2, Cout, k, k, stride, pad, act, S, _p(ws), nb)
+        fmt = (0 if out_f32 else 1) | self.x1
+        if not self.sh:
+            self.run("omni_conv2d_nhwc_f32_ws", "conv2d " + key, *tensors, *shape)
+        elif post is not None:                                      # `+ post` after the activation, inside the epilogue (SH mode, never split)
+            self.run("omni_conv2d_sh_f16x3_post_ws", "conv2d " + key, *tensors, fmt, *shape, _p(post), post.numel())
+        else:
+            self.run("omni_conv2d_sh_f16x3_ws", "conv2d " + key, *tensors, fmt | self.lat, *shape)
+        if late_post is not None:                                   # (an fp32 NHWC output is never split-half)
+            self.run("omni_add_period_f32" if (out_f32 or not self.sh) else "omni_add_period_sh", "add post " + key,
+                     _p(out), _p(late_post), out.numel(), late_post.numel())
+        return out
+
+    def up_conv(self, x, key, M, H, Wd, C, Cout, act, out_f32=False, out=None):
+        """conv3x3(upsample2x(x)) — `F.interpolate` + a decoder stage's first ConvBnReLU (:279-301), in the first form of four that serves the
+        stage.  The two tap-product forms are chosen by the layer key, the arithmetic mode and the shape alone.  (de_conv0_0 and de_conv1_0 are
+        never offered form 3: at patch size 128, the only one the network exists at, their 8 x 8 and 16 x 16 outputs are no shapes of the halo
+        kernel, so outside `taps_first` they up-sample and convolve in two launches.)"""
+        e, Ho, Wo = self.e, 2 * H, 2 * Wd
+        result = lambda: self.new(M, Ho, Wo, Cout) if out is None else out        # made AFTER a form's intermediate tensor: a forward allocates in the order it always did
+        taps = self.sh and e.terms == 3 and not out_f32
+        if key in e.taps_first and taps and Cout % 32 == 0 and H * Wd <= 64:      # 1. tap products on the low-resolution map (a GEMM), then their sum
+            y = self.conv(x, key + ".taps", M, H, Wd, C, 9 * Cout, 1, 1, 0, ACT_NONE, bias=False, out_f32=True)
+            out = result()
+            self.run("omni_up2_tapsum_sh", "tap sum " + key, _p(y), self.wp(key + ".b"), _p(out), M, H, Wd, Cout, act)
+        elif key in e.taps_fused and taps and C == 64 and Cout == 64 and ((Wd == 32 and H % 8 == 0) or (H == 16 and Wd == 16)):     # 2. ... in one launch
+            out = result()
+            self.run("omni_conv3x3_up2_taps_sh_f16x3", "up+conv (tap products) " + key, _p(x), self.wp(key + ".tapsf.w16"), self.wp(key + ".b"), _p(out), 1,
+                     M, H, Wd, C, Cout, act)
+        elif self.sh and e.fuse_up and Wo % 32 == 0 and Ho % 4 == 0:      # 3. up-sampling inside the convolution's halo fill (same bits as 4.)
+            out = result()
+            self.run("omni_conv3x3_up2_sh_f16x3", "up+conv " + key, _p(x), self.wp(key + ".w16"), self.wp(key + ".b"), _p(out),
+                     (0 if out_f32 else 1) | self.lat | self.x1, M, H, Wd, C, Cout, act)
+        else:                                                       # 4. up-sample, then convolve
+            y = self.new(M, Ho, Wo, C)
+            self.run("omni_upsample_bilinear_sh" if self.sh else "omni_upsample_bilinear_f32", "upsample", _p(x), _p(y), M, H, Wd, C, Ho, Wo)
+            out = self.conv(y, key, M, Ho, Wo, C, Cout, 3, 1, 1, act, out_f32=out_f32, out=out)
+        return out
+
+    # ------------------------------------------------------------------ transformer
+    def transformer(self, d):
+        """position embedding, six blocks, encoder_norm: fp32 [M, P/32, P/32, 32] -> fp32 [M, 512]"""
+        tok = self.new(self.M, 512)
+        self.run("omni_token_pack_f32", "token_pack", _p(d), self.wp("pos"), _p(tok), self.M, self.e.npatches, d.shape[1] * d.shape[2], 32)
+        return self.blocks_sh(tok) if self.sh else self.blocks_f32(tok)
+
+    def blocks_f32(self, tok):
+        for i in range(6):
+            t = f"t{i}."
+            y = self.ln_f32(tok, t + "norm1.weight", t + "norm1.bias", 1e-5)
+            q = self.gemm_f32(y, t + "attn.q.weight", None, 512, 512)
+            kv = self.gemm_f32(y, t + "attn.kv.weight", None, 512, 1024)
+            att = self.new(self.M, 512)
+            self.run("omni_attention_f32", "attention", _p(q), _p(kv), _p(att), self.bs, self.e.npatches)
+            tok = self.gemm_f32(att, t + "attn.proj.weight", t + "attn.proj.bias", 512, 512, res=tok)
+            y = self.ln_f32(tok, t + "norm2.weight", t + "norm2.bias", 1e-5)
+            h = self.gemm_f32(y, t + "mlp.fc1.weight", t + "mlp.fc1.bias", 512, 2048, act=ACT_GELU)
+            tok = self.gemm_f32(h, t + "mlp.fc2.weight", t + "mlp.fc2.bias", 2048, 512, res=tok)
+        return self.ln_f32(tok, "enc_norm.w", "enc_norm.b", 1e-6)
+
+    def blocks_sh(self, tok):
+        """LN / attention emit SH, the GEMMs run f16x3 from it"""
+        state = _Tokens(tok)
+        norms = [(f"t{i}.norm1.weight", f"t{i}.norm1.bias", 1e-5) for i in range(6)] + [("enc_norm.w", "enc_norm.b", 1e-6)]     # what consumes each block's result
+        for i in range(6):
+            t = f"t{i}."
+            tok, qkv = self.next_norm(state, norms[i], t + "attn.qkv.w16")
+            att = self.new(self.M, 512)
+            self.run("omni_attention_qkv_sh", "attention", _p(qkv), _p(att), self.bs, self.e.npatches)
+            tok = self.gemm_sh(att, t + "attn.proj.w16", t + "attn.proj.bias", 512, 512, res=tok)
+            h = self.ln_gemm_sh(tok, t + "norm2.weight", t + "norm2.bias", 1e-5, t + "mlp.fc1.w16", t + "mlp.fc1.bias", 2048, act=ACT_GELU, out_sh=True)
+            state = self.fc2(h, t + "mlp.fc2.w16", t + "mlp.fc2.bias", tok, norms[i + 1], out_sh=i < 5)
+        return self.next_norm(state, norms[6])[1]
+
+    def next_norm(self, state, ln, qkv=None):
+        """The consumer of a token state: the LayerNorm `ln` = (weight key, bias key, eps) of the tokens and the `qkv` GEMM of the next block on
+        it, or (qkv None) the final encoder_norm alone with an fp32 result — in the kernel that fits the state.  Returns (tokens, result)."""
+        lnw, lnb, eps = ln
+        if state.parts is not None:                                 # fc2's K slices: sum + bias + residual + LayerNorm (+ GEMM) in one kernel
+            S = state.parts.shape[0]
+            tok, out = self.new(self.M, 512), self.new(self.M, 1536 if qkv else 512)
+            if qkv:
+                self.run("omni_gemm_rows_ln_parts_sh_f16x3", "ln+gemm (slices) " + qkv, _p(state.parts), S, self.wp(state.bkey), _p(state.tok), _p(tok),
+                         self.wp(lnw), self.wp(lnb), eps, _p(self.rows_weights(qkv, 1536, 512)), None, _p(out), 0, self.M, 1536, ACT_NONE)
+            else:
+                self.run("omni_splitk_reduce_ln512", "reduce+ln", _p(state.parts), S, self.wp(state.bkey), _p(state.tok), _p(tok),
+                         self.wp(lnw), self.wp(lnb), eps, _p(out), 0, self.M)
+            return tok, out
+        if state.normed is not None:                                # fc2's second pass has made the LayerNorm already
+            return state.tok, (self.gemm_sh(state.normed, qkv, None, 512, 1536) if qkv else state.normed)
+        return state.tok, (self.ln_gemm_sh(state.tok, lnw, lnb, eps, qkv, None, 1536) if qkv else self.ln_f32(state.tok, lnw, lnb, eps))
+
+    def gemm_f32(self, x, wkey, bkey, K, Nout, act=ACT_NONE, res=None):
+        out = self.new(self.M, Nout)
+        S, ws, nb = self.splitk(self.M, Nout, K // 32)
+        self.run("omni_conv2d_nhwc_f32_ws", "gemm " + wkey, _p(x), None, self.wp(wkey), self.wp(bkey), _p(res), _p(out),
+                 self.M, 1, 1, K, 0, Nout, 1, 1, 1, 0, act, S, _p(ws), nb)
+        return out
+
+    def rows_weights(self, w16key, Nout, K):
+        """the transformer matrix `w16key` in the fragment order of omni_gemm_rows_sh_f16x3 (made on first use: only single-panorama
+        forwards need the second copy, 75 MB for the six layers)"""
+        key = w16key + ".rows"
+        w = self.w.get(key)
+        if w is None:
+            src = self.w[w16key]
+            w = torch.empty_like(src)
+            self.run("omni_gemm_rows_pack", "gemm_rows_pack", _p(src), _p(w), Nout, K)
+            if not torch.cuda.is_current_stream_capturing():     # engines on other streams share the dict: hand over a finished tensor
+                torch.cuda.current_stream(src.device).synchronize()
+            self.w[key] = w
+        return w
+
+    def gemm_sh(self, x, w16key, bkey, K, Nout, act=ACT_NONE, res=None, out_sh=False):
+        """f16x3 GEMM on an SH activation matrix x [M, K]; res (fp32) and bias optional; result fp32 or SH"""
+        out = self.new(self.M, Nout)
+        if self.rows_form and K in (512, 2048):                     # a lone panorama: the register-streaming form
+            self.run("omni_gemm_rows_sh_f16x3", "gemm " + w16key, _p(x), _p(self.rows_weights(w16key, Nout, K)), self.wp(bkey), _p(res), _p(out),
+                     1 if out_sh else 0, self.M, K, Nout, act)
+            return out
+        S, ws, nb = (1, None, 0) if K <= 512 else self.splitk(self.M, Nout, K // 32)
+        self.run("omni_conv2d_sh_f16x3_ws", "gemm " + w16key, _p(x), None, self.wp(w16key), self.wp(bkey), _p(res), _p(out),
+                 (1 if out_sh else 0) | 2, self.M, 1, 1, K, 0, Nout, 1, 1, 1, 0, act, S, _p(ws), nb)
+        return out
+
+    def fc2(self, h, w16key, bkey, tok, nxt, out_sh):
+        """tok + fc2(h) as a token state.  Batches: where fc2 runs split-K, the LayerNorm `nxt` = (weight key, bias key, eps) of the result, SH or fp32,
+        in the same second pass (omni_gemm_sh_f16x3_ln512_ws).  A lone panorama: fc2 as K slices whose sum the NEXT kernel forms
+        (omni_gemm_rows_slices_sh_f16x3)."""
+        e, M = self.e, self.M
+        if self.rows_form and e.fc2_slices > 1 and e.fuse_ln:
+            parts = self.new(e.fc2_slices, M, 512)
+            self.run("omni_gemm_rows_slices_sh_f16x3", "gemm slices " + w16key, _p(h), _p(self.rows_weights(w16key, 512, 2048)), _p(parts), M, 2048, 512, e.fc2_slices)
+            return _Tokens(tok, parts=parts, bkey=bkey)
+        S, ws, nb = (1, None, 0) if self.rows_form else self.splitk(M, 512, 2048 // 32)
+        if S <= 1 or not e.fuse_fc2_ln:
+            return _Tokens(self.gemm_sh(h, w16key, bkey, 2048, 512, res=tok))
+        wk, bk, eps = nxt
+        out, y = self.new(M, 512), self.new(M, 512)
+        self.run("omni_gemm_sh_f16x3_ln512_ws", "gemm+ln " + w16key, _p(h), self.wp(w16key), self.wp(bkey), _p(tok), _p(out), self.wp(wk), self.wp(bk), eps,
+                 _p(y), 1 if out_sh else 0, M, 2048, S, _p(ws), nb)
+        return _Tokens(out, normed=y)
+
+    def ln_gemm_sh(self, x, lnw, lnb, eps, w16key, bkey, Nout, act=ACT_NONE, out_sh=False):
+        """LayerNorm(512) + GEMM (K = 512) on the fp32 token matrix x [M, 512]: one launch for a lone panorama, else the two kernels"""
+        if self.rows_form and self.e.fuse_ln:
+            out = self.new(self.M, Nout)
+            self.run("omni_gemm_rows_ln_sh_f16x3", "ln+gemm " + w16key, _p(x), self.wp(lnw), self.wp(lnb), eps, _p(self.rows_weights(w16key, Nout, 512)),
+                     self.wp(bkey), None, _p(out), 1 if out_sh else 0, self.M, Nout, act)
+            return out
+        y = torch.empty_like(x)
+        self.run("omni_layernorm512_sh", "layernorm", _p(x), self.wp(lnw), self.wp(lnb), _p(y), self.M, eps)
+        return self.gemm_sh(y, w16key, bkey, 512, Nout, act=act, out_sh=out_sh)
+
+    def ln_f32(self, x, wk, bk, eps):
+        y = torch.empty_like(x)
+        self.run("omni_layernorm512_f32", "layernorm", _p(x), self.wp(wk), self.wp(bk), _p(y), self.M, eps)
+        return y

@@ -52,10 +52,12 @@ def test_argument_checks_answer_without_a_device():
 
 
 def test_engine_routes_by_key_set_mode_and_shape_only():
-    """the path is chosen by the layer key, the arithmetic mode and the shape — the source of _up_conv names neither the batch nor the latency plan"""
+    """the path is chosen by the layer key, the arithmetic mode and the shape — the source of the up-sampling router, down to the launch of the
+    tap-product forms, names neither the batch nor the latency plan nor anything the per-forward context derives from them"""
     import inspect
-    from omnifusion_amd.model._engine import Engine
+    from omnifusion_amd.model._engine import Engine, _Forward
     assert Engine.taps_fused <= frozenset(("de_conv2_0", "de_conv3_0"))
-    src = inspect.getsource(Engine._up_conv)
+    src = inspect.getsource(_Forward.up_conv)
     head = src[:src.index("omni_conv3x3_up2_taps_sh_f16x3")]
-    assert "taps_fused" in head and "self.terms == 3" in head and "_bs" not in head and "latency_plan" not in head
+    assert "taps_first" in head and "taps_fused" in head and "terms == 3" in head
+    assert not re.search(r"\b_?(bs|lone|lat|rows_form|plan_batch|latency_plan|SINGLE_BATCH|NOMINAL_BATCH)\b|self\.M\b", head)

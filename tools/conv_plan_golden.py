@@ -33,7 +33,7 @@ def option_sets():
 
 def engine_shapes(bs, splitk):
     """(label, fmt, M, H, W, C1, C2, Cout, KH, KW, stride, pad, splitk) of every omni_conv2d_sh_f16x3[_post]_ws call of Engine.network and
-    Engine.transformer at patch size 128 and `bs` panoramas (model/_engine.py: _conv, _gemm_sh, _fc2_ln), with the engine's own split-K plan
+    Engine.transformer at patch size 128 and `bs` panoramas (model/_engine.py: _Forward.conv, .gemm_sh, .fc2), with the engine's own split-K plan
     (`splitk` = omni_conv2d_splitk_plan at the nominal batch 8, or 4 for a lone panorama) and fmt (bit 2 for a lone panorama's convolutions, bit 1 for the GEMMs' fp32 residual)."""
     M, lat, plan_bs = 18 * bs, (4 if bs == 1 else 0), (4 if bs == 1 else 8)
     out = []

@@ -7,17 +7,15 @@ from omnifusion_amd.model.spherical_model import spherical_fusion
 from omnifusion_amd.model import _engine
 from omnifusion_amd.equi_pers.equi2pers_v3 import equi2pers_patches
 from omnifusion_amd.weights import make_state_dict
-E = _engine.Engine
-oc, ou, og, ol = E._conv, E._up, E._gemm_sh, E._ln_sh
+E, F = _engine.Engine, _engine._Forward
+oc, ou, og = F.conv, F.up_conv, F.gemm_sh               # (self: the per-forward context; self.e: its engine, whose `trace` collects)
 def conv(self, x, key, *a, **k):
-    o = oc(self, x, key, *a, **k); self.trace.append((key, o)); return o
-def up(self, x, M, H, Wd, C, Ho, Wo):
-    o = ou(self, x, M, H, Wd, C, Ho, Wo); self.trace.append(("up%dx%d" % (Ho, C), o)); return o
+    o = oc(self, x, key, *a, **k); self.e.trace.append((key, o)); return o
+def up(self, x, key, *a, **k):
+    o = ou(self, x, key, *a, **k); self.e.trace.append(("up:" + key, o)); return o
 def gemm(self, x, key, *a, **k):
-    o = og(self, x, key, *a, **k); self.trace.append((key, o)); return o
-def ln(self, x, wk, *a, **k):
-    o = ol(self, x, wk, *a, **k); self.trace.append(("ln:" + wk, o)); return o
-E._conv, E._up, E._gemm_sh, E._ln_sh = conv, up, gemm, ln
+    o = og(self, x, key, *a, **k); self.e.trace.append((key, o)); return o
+F.conv, F.up_conv, F.gemm_sh = conv, up, gemm
 E.trace = []
 net = spherical_fusion(4, 18, (128, 128), (80, 80)).cuda(); net.load_state_dict(make_state_dict(42, 18, False))
 B = int(os.environ.get('B', '16'))

@@ -15,7 +15,7 @@ rgb = torch.from_numpy(g["rgb"]).cuda()
 ref = g["depth_conf"]
 keys = []
 target = {"key": None, "bits": 0}
-orig_conv, orig_gemm = _engine.Engine._conv, _engine.Engine._gemm_sh
+orig_conv, orig_gemm = _engine._Forward.conv, _engine._Forward.gemm_sh
 def conv(self, x, key, *a, **k):
     if key not in keys: keys.append(key)
     os.environ["OMNI_CONV_DBG"] = str(target["bits"] if (target["key"] == key or target["key"] == "*") else 0)
@@ -26,7 +26,7 @@ def gemm(self, x, w16key, *a, **k):
     os.environ["OMNI_CONV_DBG"] = str(target["bits"] if (target["key"] == w16key or target["key"] == "*") else 0)
     try: return orig_gemm(self, x, w16key, *a, **k)
     finally: os.environ["OMNI_CONV_DBG"] = "0"
-_engine.Engine._conv, _engine.Engine._gemm_sh = conv, gemm
+_engine._Forward.conv, _engine._Forward.gemm_sh = conv, gemm
 def err():
     return float(np.abs(net(rgb, confidence=True).cpu().numpy() - ref).max())
 base = err()
