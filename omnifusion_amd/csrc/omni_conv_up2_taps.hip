@@ -7,17 +7,21 @@
 //
 // A block owns ROWS low-resolution rows of one image at full width (WL) — 8 rows + one halo row each side at WL = 32 ("bands": 320 pixels; left and right
 // need no halo, the clamp of the up-sampling addresses the same column), or a whole 16 x 16 image (256 pixels, no halo) — and 32 output channels:
-//   * the block's nine taps of weights (9 x 32 rows x 256 B = 72 KiB, tap-major f16x3 rows as `<key>.taps.w16`) go to LDS by LDS-DMA, once, in tap order;
+//   * the block's nine taps of weights (9 x 32 rows x 256 B = 72 KiB, tap-major f16x3 rows as `<key>.taps.w16`) go to LDS by LDS-DMA, once, in processing order;
 //     tap t is waited for just before its products (hand-counted s_waitcnt vmcnt);
 //   * a wave keeps the SH fragments of its pixels (32-pixel fragments w, w + 4, w + 8; K = 64: hi and lo of four 16-channel chunks) in registers for all nine taps;
 //   * per tap: 12 matrix instructions per fragment (the f16x3 three-term product, acc_join) -> the fp32 products of the tap, [pixel][32 channels], parked in
-//     one of two LDS chunks (40 KiB) -> ONE barrier -> every thread adds the tap to its output accumulators: thread = (low-res column j, channel quad),
-//     eight 2 x 2 output cells (rows 2i, 2i+1 x columns 2j, 2j+1 for eight rows i) x 4 channels = 128 registers.  A cell reads each live (row, column)
-//     neighbour once (49 of the 81 (tap, neighbour) pairs);
+//     one of two LDS chunks (40 KiB) -> ONE barrier -> every thread takes the tap into its sums: thread = (low-res column j, channel quad),
+//     eight 2 x 2 output cells (rows 2i, 2i+1 x columns 2j, 2j+1 for eight rows i) x 4 channels = 128 registers;
+//   * the tap sum is SEPARABLE (both the up-sampling and the tap shift are): taps are taken kx-major (0, 3, 6, 1, 4, 7, 2, 5, 8).  Per tap a VERTICAL
+//     stage on the thread's own column, S[it][ay] (+)= hy[ay + ky] * Y[row i - 1 + r] + ly[ay + ky] * Y[row i + r], r = (ay + ky) >> 1 (64 registers; the
+//     column's 9 / 10 / 9 rows are read once per tap); after the three ky taps of a kx a HORIZONTAL stage, out[it][ay][bx] (+)= hx[bx + kx] * S[column
+//     j - 1 + c] + lx[bx + kx] * S[column j + c], c = (bx + kx) >> 1, whose neighbour columns live in other threads and come through the chunks (two more
+//     barriers per kx).  15 FMAs per output element instead of the 36 of a tap-by-tap bilinear sum; tests/test_up2_taps_sep_cpu.py is the specification;
 //   * outputs leave through act_store4<true> (saturation, sticky range flag).
-// Arithmetic of up2_tapsum_sh_kernel (omni_net.hip): the same bilinear weights (0.25 / 0.75 are exact, so the table below holds the values its index
-// arithmetic yields), source rows / columns clamped to the map, taps in the order ky, kx and per tap the neighbours 00, 01, 10, 11.  A tap outside the
-// up-sampled map gets weight zero instead of being skipped.  No atomics, no dependence on block placement: an image's bits do not depend on M.
+// Weights and clamps of up2_tapsum_sh_kernel (omni_net.hip), NOT its order of summation: the same bilinear weights (0.25 / 0.75 are exact, so the
+// tables below hold the values its index arithmetic yields), source rows / columns clamped to the map.  A tap outside the up-sampled map gets weight
+// zero instead of being skipped.  Fixed order, no atomics, no dependence on block placement: an image's bits do not depend on M.
 // LDS: 72 KiB + 2 x 40 KiB = 152 KiB, one block of four waves per CU with up to 512 registers per lane.
 #include <stdint.h>
 #include "omni_conv_sh_common.h"
@@ -47,6 +51,9 @@ __device__ __forceinline__ void wait_taps_in_flight(int n)
     else if (n == 2) wait_vm<2>();
     else wait_vm<0>();
 }
+
+// the tap (ky * 3 + kx) processed at step s: kx-major, 0, 3, 6, 1, 4, 7, 2, 5, 8 — the three taps of a column kx follow each other
+__host__ __device__ constexpr int tap_at(int s) { return 3 * (s % 3) + s / 3; }
 
 template <int WL, int ROWS, int HALO>
 __global__ __launch_bounds__(256, 1) void up2_taps_fused_kernel(TapsArgs a)
@@ -92,12 +99,14 @@ __global__ __launch_bounds__(256, 1) void up2_taps_fused_kernel(TapsArgs a)
     {
         const rsrc_t rsw = make_rsrc(a.wt, (size_t)9 * a.Cout * 256);
 #pragma unroll
-        for (int tp = 0; tp < 9; ++tp)
+        for (int s = 0; s < 9; ++s) {                             // in processing order (kx-major); tap tp keeps its place tp * TAP_BYTES
+            const int tp = tap_at(s);
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 const int i = wave + 4 * k, row = 4 * i + (lane >> 4), piece = (lane & 15) ^ (row & 15);
                 dma16(rsw, lds + tp * TAP_BYTES + i * 1024, ((tp * a.Cout + col0 + row) * 16 + piece) * 16, 0);
             }
+        }
     }
     // weight fragment of row lane & 31: piece K | h (K = 8 group + 4 lo + 2 chunk, h = lane >> 5) sits in slot (K | h) ^ (row & 15) = K ^ (h ^ (row & 15))
     const int wfo = (lane & 31) * 256 + (((lane >> 5) ^ (lane & 15)) * 16);
@@ -119,19 +128,21 @@ __global__ __launch_bounds__(256, 1) void up2_taps_fused_kernel(TapsArgs a)
     hx[2] = 0.75f;                     lx[2] = 0.25f;
     hx[3] = j < WL - 1 ? 0.25f : 0.0f; lx[3] = j < WL - 1 ? 0.75f : 0.0f;
 
-    f4v out[8][2][2];
-#pragma unroll
-    for (int it = 0; it < 8; ++it)
-#pragma unroll
-        for (int ab = 0; ab < 4; ++ab) out[it][ab >> 1][ab & 1] = (f4v)(0.0f);
+    // the same for the rows: only a thread's first row can be the map's top, only its eighth the map's bottom (wave-uniform)
+    const bool top = r0 + ib == 0, bot = r0 + ib + 7 == Hl - 1;
+    const float hy0[4] = {top ? 0.0f : 0.75f, top ? 1.0f : 0.25f, 0.75f, 0.25f}, ly0[4] = {top ? 0.0f : 0.25f, top ? 0.0f : 0.75f, 0.25f, 0.75f};
+    const float hy7 = bot ? 0.0f : 0.25f, ly7 = bot ? 0.0f : 0.75f;
+
+    f4v out[8][2][2];                                             // the 2 x 2 output cells of rows i, column j (written, not added to, by the first column group)
+    f4v S[8][2];                                                  // the vertical sums of the column group kx in flight: up-sampled rows 2i + ay of low-res column j
 
     wait_taps_in_flight(16);                                      // my pieces of tap 0 have landed (the pixel fragments were issued before them)
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 
-    auto tap = [&]<int tp>() {                                    // (a template, called nine times: `#pragma unroll` gives up on a body of this size)
-        constexpr int ky = tp / 3, kx = tp - 3 * ky;
-        unsigned char* chunk = lds + W_BYTES + (tp & 1) * CH_BYTES;
+    auto tap = [&]<int s>() {                                     // (a template, called nine times: `#pragma unroll` gives up on a body of this size)
+        constexpr int tp = tap_at(s), ky = tp / 3, kx = tp - 3 * ky;
+        unsigned char* chunk = lds + W_BYTES + (s & 1) * CH_BYTES;
         // ---- the tap's products of my fragments -> chunk
         {
             const unsigned char* wb = lds + tp * TAP_BYTES;
@@ -167,46 +178,80 @@ __global__ __launch_bounds__(256, 1) void up2_taps_fused_kernel(TapsArgs a)
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        if (tp < 8) wait_taps_in_flight(2 * (7 - tp));            // my pieces of tap tp + 1 have landed
+        if (s < 8) wait_taps_in_flight(2 * (7 - s));              // my pieces of the next tap (step s + 1) have landed
         wait_lds_reads();                                         // my products are in the chunk (and my reads of the weights have returned)
-        __builtin_amdgcn_s_barrier();                             // everybody's are; everybody is done reading the OTHER chunk (tap tp - 1)
+        __builtin_amdgcn_s_barrier();                             // everybody's are; everybody is done reading the OTHER chunk (step s - 1)
         asm volatile("" ::: "memory");
-        // ---- out += the tap
+        // ---- vertical stage: S (+)= the tap, on my own column.  The thread's column of the chunk is read once: rows i0 - 1 + k, k = 0 .. 9 (9 / 10 / 9 of them
+        // for ky = 0 / 1 / 2), clamped to the map; up-sampled row 2i + ay + ky - 1 takes the row pair (it + r, it + r + 1), r = (ay + ky) >> 1
+        {
+            constexpr int klo = ky >> 1, khi = 8 + ((ky + 1) >> 1);
+            f4v R[10];
 #pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int i = r0 + ib + it;
-            // weights of up-sampled row 2i + u - 1 on the row pair (r, r + 1), r = u >> 1, as for the columns (rows 1 .. 6 of a thread are never the map's edge)
-            float hy[4], ly[4];
-            const bool top = it == 0 && i == 0, bot = it == 7 && i == Hl - 1;
-            hy[0] = top ? 0.0f : 0.75f; ly[0] = top ? 0.0f : 0.25f;
-            hy[1] = top ? 1.0f : 0.25f; ly[1] = top ? 0.0f : 0.75f;
-            hy[2] = 0.75f;              ly[2] = 0.25f;
-            hy[3] = bot ? 0.0f : 0.25f; ly[3] = bot ? 0.0f : 0.75f;
-            f4v v[3][3];
+            for (int k = klo; k <= khi; ++k)
+                R[k] = *reinterpret_cast<const f4v*>(chunk + (min(max(r0 + ib - 1 + k, 0), Hl - 1) - sbase) * ROW_BYTES + coff[1]);
 #pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                if (r < (ky >> 1) || r > ((ky + 1) >> 1) + 1) continue;
-                const unsigned char* rp = chunk + (min(max(i - 1 + r, 0), Hl - 1) - sbase) * ROW_BYTES;
+            for (int it = 0; it < 8; ++it)
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    if (c < (kx >> 1) || c > ((kx + 1) >> 1) + 1) continue;
-                    v[r][c] = *reinterpret_cast<const f4v*>(rp + coff[c]);
-                }
-            }
-#pragma unroll
-            for (int ay = 0; ay < 2; ++ay)
-#pragma unroll
-                for (int bx = 0; bx < 2; ++bx) {
-                    const int uy = ay + ky, ux = bx + kx, r = uy >> 1, c = ux >> 1;
-                    const float w00 = hy[uy] * hx[ux], w01 = hy[uy] * lx[ux], w10 = ly[uy] * hx[ux], w11 = ly[uy] * lx[ux];
-                    f4v o = out[it][ay][bx];
+                for (int ay = 0; ay < 2; ++ay) {
+                    const int uy = ay + ky, r = uy >> 1;
+                    // weights of up-sampled row 2i + uy - 1 (rows 1 .. 6 of a thread are never the map's edge)
+                    const float h = it == 0 ? hy0[uy] : it == 7 && uy == 3 ? hy7 : (uy & 1) ? 0.25f : 0.75f;
+                    const float l = it == 0 ? ly0[uy] : it == 7 && uy == 3 ? ly7 : (uy & 1) ? 0.75f : 0.25f;
+                    f4v v;                                        // the first tap of a column group starts S
+                    if constexpr (ky != 0) v = S[it][ay];
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
-                        o[e] = fmaf(w11, v[r + 1][c + 1][e], fmaf(w10, v[r + 1][c][e], fmaf(w01, v[r][c + 1][e], fmaf(w00, v[r][c][e], o[e]))));
-                    asm volatile("" : "+v"(o));                   // pins the sum HERE: the compiler otherwise sinks all nine taps' arithmetic below the last barrier,
-                    out[it][ay][bx] = o;                          // next to the stores, and spills everything it read from the chunks meanwhile
+                        if constexpr (ky == 0) v[e] = fmaf(l, R[it + r + 1][e], h * R[it + r][e]);
+                        else v[e] = fmaf(l, R[it + r + 1][e], fmaf(h, R[it + r][e], v[e]));
+                    asm volatile("" : "+v"(v));                   // pins the sum HERE: the compiler otherwise sinks the arithmetic below later barriers
+                    S[it][ay] = v;                                // and spills everything it read from the chunks meanwhile
                 }
-            __builtin_amdgcn_sched_barrier(0);                    // one cell's neighbours in flight at a time: the scheduler would hoist all eight cells' reads and spill
+            __builtin_amdgcn_sched_barrier(0);                    // one tap's column in flight at a time
+        }
+        // ---- horizontal stage, after the third tap of a column group: out (+)= hx * S[column j - 1 + c] + lx * S[column j + c], c = (bx + kx) >> 1.  The
+        // neighbour columns' S live in other threads (other waves at j % 8 == 0 / 7): they are exchanged through the chunks, in the chunks' own layout
+        // (row ib + it, coff[]: conflict-free like the product reads).  One ay half is 32 KiB: ay = 0 goes to the chunk this step did not use, ay = 1 to
+        // this step's chunk once everybody has left its vertical stage.
+        if constexpr (ky == 2) {
+            unsigned char* other = lds + W_BYTES + ((s & 1) ^ 1) * CH_BYTES;
+            auto horizontal = [&]<int ay>(const unsigned char* buf) {
+#pragma unroll
+                for (int it = 0; it < 8; ++it) {
+                    const unsigned char* rp = buf + (ib + it) * ROW_BYTES;
+                    const f4v own = S[it][ay];
+                    f4v left = own, right = own;                  // (only the live one is read: kx = 0 never looks right, kx = 2 never left)
+                    if (kx <= 1) left = *reinterpret_cast<const f4v*>(rp + coff[0]);
+                    if (kx >= 1) right = *reinterpret_cast<const f4v*>(rp + coff[2]);
+#pragma unroll
+                    for (int bx = 0; bx < 2; ++bx) {
+                        const int ux = bx + kx, c = ux >> 1;
+                        const f4v va = c == 0 ? left : own, vb = c == 0 ? own : right;
+                        f4v o;                                    // the first column group starts out
+                        if constexpr (kx != 0) o = out[it][ay][bx];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if constexpr (kx == 0) o[e] = fmaf(lx[ux], vb[e], hx[ux] * va[e]);
+                            else o[e] = fmaf(lx[ux], vb[e], fmaf(hx[ux], va[e], o[e]));
+                        asm volatile("" : "+v"(o));               // (pinned like the vertical sums)
+                        out[it][ay][bx] = o;
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            };
+#pragma unroll
+            for (int it = 0; it < 8; ++it) *reinterpret_cast<f4v*>(other + (ib + it) * ROW_BYTES + coff[1]) = S[it][0];
+            wait_lds_reads();                                     // my ay = 0 sums are in `other` (and my reads of this step's products have returned)
+            __builtin_amdgcn_s_barrier();                         // everybody's are; everybody has left the vertical stage: this step's chunk is free
+            asm volatile("" ::: "memory");
+#pragma unroll
+            for (int it = 0; it < 8; ++it) *reinterpret_cast<f4v*>(chunk + (ib + it) * ROW_BYTES + coff[1]) = S[it][1];
+            __builtin_amdgcn_sched_barrier(0);
+            horizontal.template operator()<0>(other);
+            wait_lds_reads();                                     // my ay = 1 sums are in the chunk, my reads of `other` have returned
+            __builtin_amdgcn_s_barrier();                         // everybody's: the next step's products may overwrite `other`
+            asm volatile("" ::: "memory");
+            horizontal.template operator()<1>(chunk);             // (the step after next overwrites this chunk, behind the next step's barrier)
         }
     };
     tap.template operator()<0>(); tap.template operator()<1>(); tap.template operator()<2>();
