@@ -3,7 +3,8 @@
 // per batch.   Replaces /root/reference/test.py:151-176 (compute_eval_metrics) and /root/reference/metrics.py:7-26.
 //
 //   omni_masked_median_f32   x[mask>0].median()  — exact: 4-pass radix select on the order-preserving key of the float
-//                            bits (torch.median returns the LOWER middle element for an even count: rank (n-1)/2)
+//                            bits (torch.median returns the LOWER middle element for an even count: rank (n-1)/2, and
+//                            NaN as soon as the selection holds one: pass 0 counts the selected NaNs next to its histogram)
 //   omni_depth_metrics_f32   pred *= scale (in place, as test.py:162 does), then the masked sums of
 //                            |p-g|/g, (p-g)^2/g, (p-g)^2, (log p - log g)^2 [own mask p,g > 1e-7], delta < 1.25^{1,2,3}
 // Reductions are two-stage (per-block partials in double, then one block in fixed order): deterministic.
@@ -18,24 +19,30 @@ __device__ __forceinline__ unsigned fkey(float v)
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);      // ascending unsigned order == ascending float order
 }
 
-// state[0] = prefix key bits decided so far, state[1] = remaining rank within the prefix bucket, state[2] = count
+// state[0] = prefix key bits decided so far, state[1] = remaining rank within the prefix bucket, state[2] = count,
+// state[3] = selected NaNs (either sign; the key order alone would put them beyond +-inf and return a finite median)
 __global__ __launch_bounds__(256) void median_hist_kernel(const float* __restrict__ x, const float* __restrict__ mask, size_t n,
-                                                          int pass, const unsigned* __restrict__ state, unsigned* __restrict__ hist)
+                                                          int pass, unsigned* __restrict__ state, unsigned* __restrict__ hist)
 {
     __shared__ unsigned h[256];
+    __shared__ unsigned nans;
     h[threadIdx.x] = 0;
+    if (threadIdx.x == 0) nans = 0;
     __syncthreads();
     const int shift = 24 - 8 * pass;
     const unsigned prefix = state[0];
     const unsigned pmask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         if (mask[i] > 0.0f) {
-            const unsigned k = fkey(x[i]);
+            const float v = x[i];
+            const unsigned k = fkey(v);
             if ((k & pmask) == prefix) atomicAdd(&h[(k >> shift) & 255u], 1u);
+            if (pass == 0 && v != v) atomicAdd(&nans, 1u);
         }
     }
     __syncthreads();
     if (h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], h[threadIdx.x]);
+    if (threadIdx.x == 0 && nans) atomicAdd(&state[3], nans);
 }
 
 __global__ void median_pick_kernel(int pass, unsigned* __restrict__ state, unsigned* __restrict__ hist, float* __restrict__ out)
@@ -58,7 +65,7 @@ __global__ void median_pick_kernel(int pass, unsigned* __restrict__ state, unsig
     if (pass == 3) {
         const unsigned k = state[0];
         const unsigned bits = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-        *out = state[2] ? __uint_as_float(bits) : __uint_as_float(0x7fc00000u);     // empty selection -> NaN (like torch)
+        *out = (state[2] && !state[3]) ? __uint_as_float(bits) : __uint_as_float(0x7fc00000u);     // empty selection, or a NaN in it -> NaN (like torch)
     }
 }
 
@@ -116,7 +123,7 @@ int omni_masked_median_f32(const float* x, const float* mask, size_t n, unsigned
     OMNI_HIP(hipMemsetAsync(ws, 0, 260 * sizeof(unsigned), s));
     const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
     for (int pass = 0; pass < 4; ++pass) {
-        if (blocks > 0) hipLaunchKernelGGL(median_hist_kernel, dim3(blocks), dim3(256), 0, s, x, mask, n, pass, (const unsigned*)ws, ws + 4);
+        if (blocks > 0) hipLaunchKernelGGL(median_hist_kernel, dim3(blocks), dim3(256), 0, s, x, mask, n, pass, ws, ws + 4);
         hipLaunchKernelGGL(median_pick_kernel, dim3(1), dim3(64), 0, s, pass, ws, ws + 4, out);
     }
     OMNI_HIP(hipGetLastError());

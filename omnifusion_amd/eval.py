@@ -18,7 +18,9 @@ NAMES = ("abs_rel", "sq_rel", "rms_sq_lin", "rms_sq_log", "d1", "d2", "d3")
 
 
 def masked_median(x, mask):
-    """x[mask > 0].median() as a 1-element device tensor (torch.median semantics: lower middle element)."""
+    """x[mask > 0].median() as a 1-element device tensor (torch.median semantics: the lower middle element; NaN for an empty selection and for a
+    selection that holds a NaN of either sign, whatever the rest is — the radix select counts the selected NaNs in its first pass).  Only
+    mask > 0 selects: 0, -0.0, negative values and NaN in the mask do not."""
     lib = _lib.load()
     x = x.contiguous(); mask = mask.contiguous().to(torch.float32)
     ws = torch.empty(260, dtype=torch.int32, device=x.device)
@@ -30,7 +32,10 @@ def masked_median(x, mask):
 
 def compute_eval_metrics(output, gt, depth_mask):
     """test.py:151-176.  Scales `output` in place by median(gt)/median(output) over the mask and returns a device tensor
-    [abs_rel, sq_rel, rms_sq_lin, rms_sq_log, d1, d2, d3, N, N_log]."""
+    [abs_rel, sq_rel, rms_sq_lin, rms_sq_log, d1, d2, d3, N, N_log].  N counts the elements with mask > 0 (a mask value of 0.5 or 2 counts once;
+    the reference sums the mask's values), N_log those with prediction and ground truth > 1e-7 as well.  A prediction with a NaN under the mask
+    (an overflow) has a NaN median: the whole prediction is scaled to NaN, the four error metrics are NaN and the inlier ratios 0, as in the
+    reference."""
     for t, name in ((output, "output"), (gt, "gt"), (depth_mask, "mask")):
         if not t.is_cuda:
             raise ValueError(f"{name} must live on an MI355X device; there is no CPU path")

@@ -90,6 +90,12 @@ def calculate_l1_loss(pred, gt, mask):
 
 
 def calculate_berhu_loss(pred, gt, mask, weights):
+    """Mirror of the reference's supervision/direct.py:3-18: mean_b(sum_b(berhu(gt - pred) * mask * weights) / sum_b(mask)) with the threshold
+    c = max|gt - pred| / 5 over EVERY element (masked-out ones and other batch items included), a 0-d float32 tensor, differentiable w.r.t. pred.
+    |d| <= c is decided in float32 and takes the linear branch (gradient sign(d), 0 at d = 0).  An item whose mask sum is 0 makes the loss NaN
+    (0 / 0) and its own gradient NaN; the other items' gradients stay finite.  One deliberate difference: where pred == gt everywhere, c is 0 and
+    the reference evaluates (d^2 + c^2) / (2 c) = 0 / 0 for every element and returns NaN; here every element takes the linear branch, the loss
+    is 0 and the gradient 0."""
     for t, name in ((pred, "pred"), (gt, "gt"), (mask, "mask"), (weights, "weights")):
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
             raise ValueError(f"{name} must be a tensor on an MI355X device; there is no CPU path")
