@@ -171,6 +171,13 @@ int omni_conv2d_nhwc_f16x3_ws(const float* src1, const float* src2, const void* 
                               const float* res, float* dst, int M, int H, int W, int C1, int C2, int Cout,
                               int KH, int KW, int stride, int pad, int act, int splitk, float* ws, size_t ws_bytes,
                               omni_stream_t stream);
+/* The single-product form ("f16x1"): an operand is hi alone, a product block ONE v_mfma_f32_32x32x16_f16 with fp32
+ * accumulation — the arithmetic of mixed-precision training: fp16 operands, fp32 sums, about 2^-11 relative error per operand.  wt16 is the
+ * hi-only image of omni_conv2d_split_weights_f16x1: halfs [Cout][KH*KW*(C1+C2)].  Same operator, shapes, split-K and rejections. */
+int omni_conv2d_nhwc_f16x1_ws(const float* src1, const float* src2, const void* wt16, const float* bias,
+                              const float* res, float* dst, int M, int H, int W, int C1, int C2, int Cout,
+                              int KH, int KW, int stride, int pad, int act, int splitk, float* ws, size_t ws_bytes,
+                              omni_stream_t stream);
 /* The same operator with SPLIT-HALF ("SH") activations: per pixel and per group of 32 channels a tensor stores 32 hi
  * halfs then 32 lo halfs (x = hi + lo*2^-11; 128 bytes per group = the footprint of 32 floats).  The producer splits
  * once, consumers stream tiles straight into LDS by LDS-DMA.  src1 and src2 are SH tensors; fmt bit 0: dst is SH
@@ -656,7 +663,10 @@ int omni_chamfer_grad_f32(const float* p1, const float* p2, const unsigned char*
  * order: the result is a function of the inputs and the chunk length.
  * `workspace`: omni_conv2d_bwd_workspace_bytes(...) bytes serve any of the three calls (0 for shapes outside the scope above; it depends on
  * "conv_wgrad_rows"), any content, 16-byte aligned; the calls share no state through it — scale is the only hand-over.
- * omni_conv2d_split_weights_f16x3: wt fp32 [Cout][K] -> wt16, the halfs [Cout][K/32][hi32|lo32] the forward reads, on the device. */
+ * omni_conv2d_split_weights_f16x3: wt fp32 [Cout][K] -> wt16, the halfs [Cout][K/32][hi32|lo32] the forward reads, on the device.
+ * The _f16x1 entry points are the single-product forms of their _f16x3 siblings: the same arguments, workspace, rejections,
+ * chunks, epilogue and scale; operands hi(dZ . 2^s), hi(wt), hi(A), one matrix instruction per product block.  An element of dZ below
+ * 2^-22 max|dZ| contributes 0.  omni_conv2d_split_weights_f16x1 writes the hi-only image, halfs [Cout][K] (half the bytes). */
 size_t omni_conv2d_bwd_workspace_bytes(int M, int H, int W, int C1, int C2, int Cout, int KH, int KW, int stride, int pad);
 int omni_conv2d_bwd_epilogue_f32(const float* grad_out, const float* out, float* dz, float* grad_bias, float* scale, long long rows,
                                  int Cout, int act, void* workspace, size_t ws_bytes, omni_stream_t stream);
@@ -667,6 +677,13 @@ int omni_conv2d_bwd_weight_f16x3(const float* dz, const float* src1, const float
                                  int C1, int C2, int Cout, int KH, int KW, int stride, int pad, void* workspace, size_t ws_bytes,
                                  omni_stream_t stream);
 int omni_conv2d_split_weights_f16x3(const float* wt, void* wt16, int Cout, int K, omni_stream_t stream);
+int omni_conv2d_bwd_data_f16x1(const float* dz, const float* wt, const float* scale, float* dx1, float* dx2, int M, int H, int W, int C1,
+                               int C2, int Cout, int KH, int KW, int stride, int pad, void* workspace, size_t ws_bytes,
+                               omni_stream_t stream);
+int omni_conv2d_bwd_weight_f16x1(const float* dz, const float* src1, const float* src2, const float* scale, float* dw, int M, int H, int W,
+                                 int C1, int C2, int Cout, int KH, int KW, int stride, int pad, void* workspace, size_t ws_bytes,
+                                 omni_stream_t stream);
+int omni_conv2d_split_weights_f16x1(const float* wt, void* wt16, int Cout, int K, omni_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Batch normalisation with a fused residual and ReLU, and its backward (csrc/omni_batchnorm.hip):

@@ -53,6 +53,7 @@ omni_conv2d_nhwc_f32 i p6i11p
 omni_conv2d_splitk_plan i lii
 omni_conv2d_nhwc_f32_ws i p6i12pzp
 omni_conv2d_nhwc_f16x3_ws i p6i12pzp
+omni_conv2d_nhwc_f16x1_ws i p6i12pzp
 omni_conv2d_sh_f16x3_ws i p6i13pzp
 omni_conv2d_sh_plan i i13pi
 omni_gemm_rows_sh_f16x3 i p5i5p
@@ -165,6 +166,9 @@ omni_conv2d_bwd_epilogue_f32 i p5liipzp
 omni_conv2d_bwd_data_f16x3 i p5i10pzp
 omni_conv2d_bwd_weight_f16x3 i p5i10pzp
 omni_conv2d_split_weights_f16x3 i ppiip
+omni_conv2d_bwd_data_f16x1 i p5i10pzp
+omni_conv2d_bwd_weight_f16x1 i p5i10pzp
+omni_conv2d_split_weights_f16x1 i ppiip
 omni_batchnorm_workspace_bytes z li
 omni_batchnorm_fwd_f32 i p8liiddipzp
 omni_batchnorm_bwd_f32 i p9li3pzp

@@ -19,6 +19,9 @@
 // is split while it is parked in LDS (2 cvt_pk + 4 sub/mul per 4 channels); the weights are split once at load time
 // ([Cout][K/32][hi32|lo32] halfs).  Max error 1.6e-6..3.7e-6 against float64 on every conv shape of the network.
 //
+// X1 = true (with F16X3) is the single-product form, "f16x1": an operand is hi alone, a product block ONE matrix instruction,
+// the weights a hi-only image [Cout][K] halfs; no lo images in LDS, no acc1 (training's second mode).
+//
 // GEMM view: D[r][j] = sum_k A[r][k] * Wt[j][k],  r = output pixel (m, oy, ox), j = output channel,
 // k = (tap, input channel).  A is gathered on the fly (zero outside the image), channels of a tap
 // are contiguous in NHWC so every A fetch is a 16-byte load; an optional second source supplies
@@ -56,7 +59,7 @@ struct ConvArgs {
     int M, H, W, C1, C2, Ho, Wo, Cout;
     int KH, KW, stride, pad, act;
     int rows;                                // M*Ho*Wo
-    int f16x3;                               // 1: wt is the pre-split half format, products on the fp16 matrix cores
+    int f16x3;                               // 1: wt is the pre-split half format, products on the fp16 matrix cores; 2: hi-only halfs (f16x1)
     int splitk;                              // >1: blockIdx.y owns a K range and writes raw partial sums to ws[y]
     float* ws;                               // [splitk][rows][Cout]
     int dbg;                                 // debug build only (OMNI_CONV_DBG ablation bits): 1 no MFMA, 2 no refetch, 4 no stash
@@ -68,19 +71,20 @@ constexpr int HP = BK + 8;                   // LDS row pitch in halfs (F16X3 im
 
 // __launch_bounds__(256, 5): at most 96 registers (VGPR+AGPR) so that five blocks share a CU (5 x 27.6 KB LDS fits):
 // the 1152-block layers (layer1, de_conv2_x at B=8) then run in ONE round of 4.5 waves per SIMD instead of 4 + a tail.
-template <int BM, int BN, int WM, int WN, bool F16X3>
-__global__ __launch_bounds__(256, (F16X3 ? 3 : 5)) void conv_igemm_f32_kernel(ConvArgs a)
+template <int BM, int BN, int WM, int WN, bool F16X3, bool X1 = false>
+__global__ __launch_bounds__(256, (F16X3 && !X1 ? 3 : 5)) void conv_igemm_f32_kernel(ConvArgs a)
 {
+    static_assert(F16X3 || !X1, "f16x1 is a form of the fp16 path");
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;        // 32x32 MFMA tiles per wave
     constexpr int APASS = BM / 32, BPASS = BN / 32;            // float4 loads per thread per K-step
-    constexpr int LDS_BYTES = F16X3 ? 2 * (BM + BN) * HP * 2 : (BM + BN) * LDP * 4;
+    constexpr int LDS_BYTES = F16X3 ? (X1 ? 1 : 2) * (BM + BN) * HP * 2 : (BM + BN) * LDP * 4;
     __shared__ __attribute__((aligned(16))) unsigned char lds_raw[LDS_BYTES];
     float* As = reinterpret_cast<float*>(lds_raw);
     float* Bs = As + BM * LDP;
     _Float16* Ah = reinterpret_cast<_Float16*>(lds_raw);         // F16X3 images: A_hi, A_lo, B_hi, B_lo
-    _Float16* Al = Ah + BM * HP;
+    _Float16* Al = Ah + (X1 ? 0 : BM * HP);                      // (X1: no lo images; Al and Bl are never touched)
     _Float16* Bh = Al + BM * HP;
-    _Float16* Bl = Bh + BN * HP;
+    _Float16* Bl = Bh + (X1 ? 0 : BN * HP);
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = wave / WN, wn = wave % WN;
@@ -120,10 +124,12 @@ __global__ __launch_bounds__(256, (F16X3 ? 3 : 5)) void conv_igemm_f32_kernel(Co
     const rsrc_t rs1 = make_rsrc(a.src1, (size_t)a.M * a.H * a.W * a.C1 * 4);
     const rsrc_t rs2 = make_rsrc(a.src2 ? a.src2 : a.src1, a.src2 ? (size_t)a.M * a.H * a.W * a.C2 * 4 : 0);
     // weights: fp32 [Cout][K] (16-byte piece = 4 k)  |  F16X3: halfs [Cout][K/32][hi32|lo32] (piece t&7: 0-3 hi, 4-7 lo)
-    const rsrc_t rsw = make_rsrc(a.wt, (size_t)a.Cout * Kfull * 4);
+    //          X1: halfs [Cout][K], a 32-k piece is 64 B: the loads of pieces 4-7 are out of range
+    const rsrc_t rsw = make_rsrc(a.wt, (size_t)a.Cout * Kfull * (X1 ? 2 : 4));
     int wbase[BPASS];
 #pragma unroll
-    for (int i = 0; i < BPASS; ++i) wbase[i] = F16X3 ? ((col0 + lr + 32 * i) * ksteps * 64 + (t & 7) * 8) * 2
+    for (int i = 0; i < BPASS; ++i) wbase[i] = X1 ? ((t & 7) < 4 ? ((col0 + lr + 32 * i) * ksteps * 32 + (t & 3) * 8) * 2 : (int)0x80000000)
+                                             : F16X3 ? ((col0 + lr + 32 * i) * ksteps * 64 + (t & 7) * 8) * 2
                                                       : ((col0 + lr + 32 * i) * Kfull + kq) * 4;
 
     f4v ra[APASS], rb[BPASS];
@@ -142,7 +148,8 @@ __global__ __launch_bounds__(256, (F16X3 ? 3 : 5)) void conv_igemm_f32_kernel(Co
                           : __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rs2, off, 0, 0));
         }
 #pragma unroll
-        for (int i = 0; i < BPASS; ++i) rb[i] = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rsw, wbase[i], ks * (BK * 4), 0));
+        for (int i = 0; i < BPASS; ++i)
+            rb[i] = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rsw, wbase[i], ks * (X1 ? BK * 2 : BK * 4), 0));
         f_c += BK;
         if (f_c == Cin) { f_c = 0; ++f_tap; if (++f_kx == a.KW) { f_kx = 0; ++f_ky; } }
     };
@@ -155,11 +162,12 @@ __global__ __launch_bounds__(256, (F16X3 ? 3 : 5)) void conv_igemm_f32_kernel(Co
                 for (int e = 0; e < 4; ++e) {
                     const float x = ra[i][e];
                     const _Float16 h = (fabsf(x) < 6.103515625e-05f) ? (_Float16)0.0f : (_Float16)x;
-                    hi[e] = h; lo[e] = (_Float16)((x - (float)h) * 2048.0f);
+                    hi[e] = h; if (!X1) lo[e] = (_Float16)((x - (float)h) * 2048.0f);
                 }
                 *reinterpret_cast<h4v*>(Ah + (lr + 32 * i) * HP + kq) = hi;
-                *reinterpret_cast<h4v*>(Al + (lr + 32 * i) * HP + kq) = lo;
+                if (!X1) *reinterpret_cast<h4v*>(Al + (lr + 32 * i) * HP + kq) = lo;
             }
+            if (X1 && (t & 7) >= 4) return;
             _Float16* bd = ((t & 7) >= 4 ? Bl : Bh) + lr * HP + (t & 3) * 8;
 #pragma unroll
             for (int i = 0; i < BPASS; ++i) *reinterpret_cast<f4v*>(bd + 32 * i * HP) = rb[i];
@@ -171,11 +179,12 @@ __global__ __launch_bounds__(256, (F16X3 ? 3 : 5)) void conv_igemm_f32_kernel(Co
         }
     };
 
-    f16v acc[TM][TN], acc1[F16X3 ? TM : 1][F16X3 ? TN : 1];      // F16X3: acc = hi.hi, acc1 = hi.lo + lo.hi (scaled by 2^11)
+    constexpr bool LO = F16X3 && !X1;                            // the lo images and the second accumulator exist
+    f16v acc[TM][TN], acc1[LO ? TM : 1][LO ? TN : 1];            // F16X3: acc = hi.hi, acc1 = hi.lo + lo.hi (scaled by 2^11)
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) { acc[i][j] = (f16v)(0.0f); if (F16X3) acc1[i][j] = (f16v)(0.0f); }
+        for (int j = 0; j < TN; ++j) { acc[i][j] = (f16v)(0.0f); if (LO) acc1[i][j] = (f16v)(0.0f); }
 
     const int frow = lane & 31, fk = (lane >> 5) * 4;
     const float* Aw = As + (wm * TM * 32 + frow) * LDP + fk;
@@ -202,18 +211,19 @@ __global__ __launch_bounds__(256, (F16X3 ? 3 : 5)) void conv_igemm_f32_kernel(Co
 #pragma unroll
                 for (int i = 0; i < TM; ++i) {
                     ah[i] = *reinterpret_cast<const h8v*>(Ah + ((wm * TM + i) * 32) * HP + foff + kc * 16);
-                    al[i] = *reinterpret_cast<const h8v*>(Al + ((wm * TM + i) * 32) * HP + foff + kc * 16);
+                    if (LO) al[i] = *reinterpret_cast<const h8v*>(Al + ((wm * TM + i) * 32) * HP + foff + kc * 16);
                 }
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     bh[j] = *reinterpret_cast<const h8v*>(Bh + ((wn * TN + j) * 32) * HP + foff + kc * 16);
-                    bl[j] = *reinterpret_cast<const h8v*>(Bl + ((wn * TN + j) * 32) * HP + foff + kc * 16);
+                    if (LO) bl[j] = *reinterpret_cast<const h8v*>(Bl + ((wn * TN + j) * 32) * HP + foff + kc * 16);
                 }
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j) {
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+                        if (!LO) continue;
                         acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc1[i][j], 0, 0, 0);
                         acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc1[i][j], 0, 0, 0);
                     }
@@ -247,7 +257,7 @@ __global__ __launch_bounds__(256, (F16X3 ? 3 : 5)) void conv_igemm_f32_kernel(Co
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
                 const int r = row0 + (wm * TM + i) * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-                const float d = F16X3 ? fmaf(acc1[i][j][reg], 4.8828125e-4f, acc[i][j][reg]) : acc[i][j][reg];
+                const float d = LO ? fmaf(acc1[i][j][reg], 4.8828125e-4f, acc[i][j][reg]) : acc[i][j][reg];
                 if (r < a.rows && a.splitk > 1) {
                     a.ws[((size_t)blockIdx.y * a.rows + r) * a.Cout + col] = d;
                 } else if (r < a.rows) {
@@ -273,15 +283,16 @@ __global__ __launch_bounds__(256, (F16X3 ? 3 : 5)) void conv_igemm_f32_kernel(Co
 // A traffic 1.6x the input instead of 9x.  Requires W % 32 == 0, H % 4 == 0 (the 32^2 / 64^2 / 128^2 layers).
 constexpr int HT_H = 4, HT_W = 32, HPX = (HT_H + 2) * (HT_W + 2);     // 204 halo pixels
 
-template <int BN>
-__global__ __launch_bounds__(256, 2) void conv3x3_halo_f16x3_kernel(ConvArgs a)
+// X1: the f16x1 form — hi images only, one matrix instruction per product block, the hi-only weight image [Cout][K] halfs.
+template <int BN, bool X1 = false>
+__global__ __launch_bounds__(256, (X1 ? 3 : 2)) void conv3x3_halo_f16x3_kernel(ConvArgs a)
 {
     constexpr int TN = BN / 32;
-    __shared__ __attribute__((aligned(16))) _Float16 lds[2 * HPX * HP + 2 * 3 * BN * HP];
+    __shared__ __attribute__((aligned(16))) _Float16 lds[(X1 ? 1 : 2) * (HPX * HP + 3 * BN * HP)];
     _Float16* Ah = lds;
-    _Float16* Al = Ah + HPX * HP;
+    _Float16* Al = Ah + (X1 ? 0 : HPX * HP);                     // (X1: Al and Bl are never touched)
     _Float16* Bh = Al + HPX * HP;
-    _Float16* Bl = Bh + 3 * BN * HP;
+    _Float16* Bl = Bh + (X1 ? 0 : 3 * BN * HP);
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int ntn = a.Cout / BN, tw = a.W / HT_W, th = a.H / HT_H;
@@ -305,12 +316,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16x3_kernel(ConvArgs a)
     }
     const rsrc_t rs1 = make_rsrc(a.src1, (size_t)a.M * a.H * a.W * a.C1 * 4);
     const rsrc_t rs2 = make_rsrc(a.src2 ? a.src2 : a.src1, a.src2 ? (size_t)a.M * a.H * a.W * a.C2 * 4 : 0);
-    const rsrc_t rsw = make_rsrc(a.wt, (size_t)a.Cout * ksteps * 128);
-    // B loader: 3 taps x BN rows x 8 pieces (0-3 hi, 4-7 lo)
-    constexpr int BP = 3 * BN * 8 / 256;
-    f16v acc[TN], acc1[TN];
+    const rsrc_t rsw = make_rsrc(a.wt, (size_t)a.Cout * ksteps * (X1 ? 64 : 128));
+    // B loader: 3 taps x BN rows x 8 pieces (0-3 hi, 4-7 lo); X1: x 4 pieces
+    constexpr int BPIECES = 3 * BN * (X1 ? 4 : 8), BP = (BPIECES + 255) / 256;
+    f16v acc[TN], acc1[X1 ? 1 : TN];
 #pragma unroll
-    for (int j = 0; j < TN; ++j) { acc[j] = (f16v)(0.0f); acc1[j] = (f16v)(0.0f); }
+    for (int j = 0; j < TN; ++j) { acc[j] = (f16v)(0.0f); if (!X1) acc1[j] = (f16v)(0.0f); }
     const int frag = (lane >> 5) * 8;
 
     for (int g = 0; g < G; ++g) {
@@ -333,26 +344,26 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16x3_kernel(ConvArgs a)
                 for (int e = 0; e < 4; ++e) {
                     const float x = ra[i][e];
                     const _Float16 h = (fabsf(x) < 6.103515625e-05f) ? (_Float16)0.0f : (_Float16)x;
-                    hi[e] = h; lo[e] = (_Float16)((x - (float)h) * 2048.0f);
+                    hi[e] = h; if (!X1) lo[e] = (_Float16)((x - (float)h) * 2048.0f);
                 }
                 *reinterpret_cast<h4v*>(Ah + (q >> 3) * HP + (q & 7) * 4) = hi;
-                *reinterpret_cast<h4v*>(Al + (q >> 3) * HP + (q & 7) * 4) = lo;
+                if (!X1) *reinterpret_cast<h4v*>(Al + (q >> 3) * HP + (q & 7) * 4) = lo;
             }
         }
         for (int ky = 0; ky < 3; ++ky) {
             f4v rb[BP];
 #pragma unroll
             for (int i = 0; i < BP; ++i) {
-                const int q = t + 256 * i, pc = q & 7, row = q >> 3;            // row = kx*BN + cout
+                const int q = t + 256 * i, pc = X1 ? q & 3 : q & 7, row = X1 ? q >> 2 : q >> 3;            // row = kx*BN + cout
                 const int kx = row / BN, co = row - kx * BN;
-                const int off = (((col0 + co) * ksteps + (ky * 3 + kx) * G + g) * 64 + pc * 8) * 2;
+                const int off = (!X1 || q < BPIECES) ? (((col0 + co) * ksteps + (ky * 3 + kx) * G + g) * (X1 ? 32 : 64) + pc * 8) * 2 : (int)0x80000000;
                 rb[i] = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rsw, off, 0, 0));
             }
             if (ky) __syncthreads();                              // previous kernel row's B fragments are consumed
 #pragma unroll
             for (int i = 0; i < BP; ++i) {
-                const int q = t + 256 * i, pc = q & 7, row = q >> 3;
-                *reinterpret_cast<f4v*>((pc >= 4 ? Bl : Bh) + row * HP + (pc & 3) * 8) = rb[i];
+                const int q = t + 256 * i, pc = X1 ? q & 3 : q & 7, row = X1 ? q >> 2 : q >> 3;
+                if (!X1 || q < BPIECES) *reinterpret_cast<f4v*>((pc >= 4 ? Bl : Bh) + row * HP + (pc & 3) * 8) = rb[i];
             }
             __syncthreads();
 #pragma unroll
@@ -361,13 +372,15 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16x3_kernel(ConvArgs a)
 #pragma unroll
                 for (int kc = 0; kc < 2; ++kc) {
                     const h8v ah = *reinterpret_cast<const h8v*>(Ah + apos + kc * 16);
-                    const h8v al = *reinterpret_cast<const h8v*>(Al + apos + kc * 16);
+                    h8v al;
+                    if (!X1) al = *reinterpret_cast<const h8v*>(Al + apos + kc * 16);
 #pragma unroll
                     for (int j = 0; j < TN; ++j) {
                         const int bpos = (kx * BN + j * 32 + (lane & 31)) * HP + frag + kc * 16;
                         const h8v bh = *reinterpret_cast<const h8v*>(Bh + bpos);
-                        const h8v bl = *reinterpret_cast<const h8v*>(Bl + bpos);
                         acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[j], 0, 0, 0);
+                        if (X1) continue;
+                        const h8v bl = *reinterpret_cast<const h8v*>(Bl + bpos);
                         acc1[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc1[j], 0, 0, 0);
                         acc1[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc1[j], 0, 0, 0);
                     }
@@ -385,7 +398,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_f16x3_kernel(ConvArgs a)
         for (int reg = 0; reg < 16; ++reg) {
             const int px = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
             const size_t o = rowbase + (size_t)px * a.Cout + col;
-            float v = fmaf(acc1[j][reg], 4.8828125e-4f, acc[j][reg]) + bj;
+            float v = (X1 ? acc[j][reg] : fmaf(acc1[j][reg], 4.8828125e-4f, acc[j][reg])) + bj;
             if (a.res) v += a.res[o];
             if (a.act == OMNI_ACT_RELU) v = fmaxf(v, 0.0f);
             else if (a.act == OMNI_ACT_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
@@ -398,7 +411,8 @@ template <int BM, int BN, int WM, int WN>
 void launch_cfg(const ConvArgs& a, hipStream_t s)
 {
     const int grid = ((a.rows + BM - 1) / BM) * (a.Cout / BN);
-    if (a.f16x3) hipLaunchKernelGGL((conv_igemm_f32_kernel<BM, BN, WM, WN, true>), dim3(grid, a.splitk > 1 ? a.splitk : 1), dim3(256), 0, s, a);
+    if (a.f16x3 == 2) hipLaunchKernelGGL((conv_igemm_f32_kernel<BM, BN, WM, WN, true, true>), dim3(grid, a.splitk > 1 ? a.splitk : 1), dim3(256), 0, s, a);
+    else if (a.f16x3) hipLaunchKernelGGL((conv_igemm_f32_kernel<BM, BN, WM, WN, true>), dim3(grid, a.splitk > 1 ? a.splitk : 1), dim3(256), 0, s, a);
     else         hipLaunchKernelGGL((conv_igemm_f32_kernel<BM, BN, WM, WN, false>), dim3(grid, a.splitk > 1 ? a.splitk : 1), dim3(256), 0, s, a);
 }
 
@@ -484,7 +498,10 @@ static int conv2d_impl(const float* src1, const float* src2, const void* wt_any,
 #endif
     if (f16x3 && S <= 1 && KH == 3 && KW == 3 && stride == 1 && pad == 1 && W % HT_W == 0 && H % HT_H == 0 && !omni_options().conv_nohalo) {
         const int grid = M * (H / HT_H) * (W / HT_W);
-        if (Cout % 64 == 0) hipLaunchKernelGGL((conv3x3_halo_f16x3_kernel<64>), dim3(grid * (Cout / 64)), dim3(256), 0, s, a);
+        if (f16x3 == 2) {
+            if (Cout % 64 == 0) hipLaunchKernelGGL((conv3x3_halo_f16x3_kernel<64, true>), dim3(grid * (Cout / 64)), dim3(256), 0, s, a);
+            else                hipLaunchKernelGGL((conv3x3_halo_f16x3_kernel<32, true>), dim3(grid * (Cout / 32)), dim3(256), 0, s, a);
+        } else if (Cout % 64 == 0) hipLaunchKernelGGL((conv3x3_halo_f16x3_kernel<64>), dim3(grid * (Cout / 64)), dim3(256), 0, s, a);
         else                hipLaunchKernelGGL((conv3x3_halo_f16x3_kernel<32>), dim3(grid * (Cout / 32)), dim3(256), 0, s, a);
         OMNI_HIP(hipGetLastError());
         return OMNI_OK;
@@ -530,6 +547,16 @@ extern "C" int omni_conv2d_nhwc_f16x3_ws(const float* src1, const float* src2, c
                                          omni_stream_t stream)
 {
     return conv2d_impl(src1, src2, wt16, 1, bias, res, dst, M, H, W, C1, C2, Cout, KH, KW, stride, pad, act, splitk, ws, ws_bytes, stream);
+}
+
+// The single-product form ("f16x1"): wt16 is the hi-only image [Cout][KH*KW*(C1+C2)] halfs of omni_conv2d_split_weights_f16x1; the same
+// operator, shapes, split-K and rejections.
+extern "C" int omni_conv2d_nhwc_f16x1_ws(const float* src1, const float* src2, const void* wt16, const float* bias,
+                                         const float* res, float* dst, int M, int H, int W, int C1, int C2, int Cout,
+                                         int KH, int KW, int stride, int pad, int act, int splitk, float* ws, size_t ws_bytes,
+                                         omni_stream_t stream)
+{
+    return conv2d_impl(src1, src2, wt16, 2, bias, res, dst, M, H, W, C1, C2, Cout, KH, KW, stride, pad, act, splitk, ws, ws_bytes, stream);
 }
 
 extern "C" int omni_conv2d_nhwc_f32(const float* src1, const float* src2, const float* wt, const float* bias,

@@ -17,6 +17,10 @@
 // omni_partials.h over the blocks); wgrad cuts the rows into chunks of `conv_wgrad_rows` rows (option; 0 = the library's plan), every chunk writes raw partial sums
 // and a second pass adds them in chunk order: a result is a function of the inputs and the chunk length only.
 //
+// f16x1 (X1 = true): an operand is hi alone, a product block ONE matrix instruction; no lo images in LDS, no acc1, no
+// fmaf(acc1, 2^-11, acc) in the epilogue.  Same loaders, same gathers, same chunks, same epilogue pass and scale; the weight operand of
+// dgrad is the hi-only transposed image.  An element of dZ below 2^-22 max|dZ| (2^-14 after the scale) is 0 there.
+//
 // A tap that does not apply (outside the image; at stride 2 the wrong parity) is never read: its lanes get an out-of-range buffer offset,
 // for which the buffer unit returns zeros — a NaN in dZ reaches exactly the elements whose sum contains it.
 #include "omni_internal.h"
@@ -51,6 +55,14 @@ __device__ __forceinline__ void split4(const f4v x, h4v& hi, h4v& lo)
 {
 #pragma unroll
     for (int e = 0; e < 4; ++e) { _Float16 h, l; split1(x[e], h, l); hi[e] = h; lo[e] = l; }
+}
+// f16x1: the hi of the split alone
+__device__ __forceinline__ h4v hi4(const f4v x)
+{
+    h4v hi;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) hi[e] = (fabsf(x[e]) < 6.103515625e-05f) ? (_Float16)0.0f : (_Float16)x[e];
+    return hi;
 }
 
 // ------------------------------------------------------------------ gradient epilogue
@@ -125,6 +137,8 @@ __global__ __launch_bounds__(256) void conv_bwd_epilogue_finish_kernel(const flo
 // transpose = 0: w [R = Cout][K = taps * Cin]  ->  halfs [Cout][K/32][hi32|lo32]           (the forward's operand)
 // transpose = 1: w [Cout][(tap, ci)]           ->  halfs [Cin][taps * Cout/32][hi32|lo32], k = (tap, co)   (dgrad's operand: taps NOT flipped,
 //                the dgrad loader walks the source pixel instead)
+// X1: the hi-only image, halfs [row][kd] with the same row and k order (f16x1)
+template <bool X1>
 __global__ __launch_bounds__(256) void conv_wsplit_kernel(const float* __restrict__ w, _Float16* __restrict__ out, int Cout, int taps, int Cin,
                                                           int transpose)
 {
@@ -140,6 +154,7 @@ __global__ __launch_bounds__(256) void conv_wsplit_kernel(const float* __restric
     }
     _Float16 h, l;
     split1(w[src], h, l);
+    if (X1) { out[row * kd + kk] = h; return; }
     const size_t d = (row * (kd >> 5) + (kk >> 5)) * 64 + (kk & 31);
     out[d] = h; out[d + 32] = l;
 }
@@ -155,16 +170,16 @@ struct DgradArgs {
     int rows;                                // M*H*W
 };
 
-template <int BM, int BN, int WM, int WN>
-__global__ __launch_bounds__(256, 2) void conv_dgrad_kernel(DgradArgs a)
+template <int BM, int BN, int WM, int WN, bool X1>
+__global__ __launch_bounds__(256, (X1 ? 4 : 2)) void conv_dgrad_kernel(DgradArgs a)
 {
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
     constexpr int APASS = BM / 32, BPASS = BN / 32;
-    __shared__ __attribute__((aligned(16))) _Float16 lds[2 * (BM + BN) * HP];
+    __shared__ __attribute__((aligned(16))) _Float16 lds[(X1 ? 1 : 2) * (BM + BN) * HP];
     _Float16* Ah = lds;
-    _Float16* Al = Ah + BM * HP;
+    _Float16* Al = Ah + (X1 ? 0 : BM * HP);                      // (X1: no lo images; Al and Bl are never touched)
     _Float16* Bh = Al + BM * HP;
-    _Float16* Bl = Bh + BN * HP;
+    _Float16* Bl = Bh + (X1 ? 0 : BN * HP);
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = wave / WN, wn = wave % WN;
@@ -194,10 +209,13 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_kernel(DgradArgs a)
         }
     }
     const rsrc_t rsz = make_rsrc(a.dz, (size_t)a.M * a.Ho * a.Wo * a.Cout * 4);
-    const rsrc_t rsw = make_rsrc(a.wt16, (size_t)Cin * ksteps * 128);
+    const rsrc_t rsw = make_rsrc(a.wt16, (size_t)Cin * ksteps * (X1 ? 64 : 128));
+    // f16x3: a 32-k piece of a row is 128 B (hi32 | lo32), eight 16-byte loads; X1: 64 B, the loads of lanes t&7 >= 4 are out of range
     int wbase[BPASS];
 #pragma unroll
-    for (int i = 0; i < BPASS; ++i) wbase[i] = ((col0 + lr + 32 * i) * ksteps * 64 + (t & 7) * 8) * 2;
+    for (int i = 0; i < BPASS; ++i)
+        wbase[i] = X1 ? ((t & 7) < 4 ? ((col0 + lr + 32 * i) * ksteps * 32 + (t & 3) * 8) * 2 : OOR)
+                      : ((col0 + lr + 32 * i) * ksteps * 64 + (t & 7) * 8) * 2;
 
     f4v ra[APASS], rb[BPASS];
     int f_c = 0, f_ky = 0, f_kx = 0;                             // (tap, channel chunk) of the NEXT fetch
@@ -211,28 +229,31 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_kernel(DgradArgs a)
             ra[i] = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rsz, off, 0, 0));
         }
 #pragma unroll
-        for (int i = 0; i < BPASS; ++i) rb[i] = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rsw, wbase[i], ks * (BK * 4), 0));
+        for (int i = 0; i < BPASS; ++i)
+            rb[i] = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rsw, wbase[i], ks * (X1 ? BK * 2 : BK * 4), 0));
         f_c += BK;
         if (f_c == a.Cout) { f_c = 0; if (++f_kx == a.KW) { f_kx = 0; ++f_ky; } }
     };
     auto stash = [&]() {
 #pragma unroll
         for (int i = 0; i < APASS; ++i) {
+            if (X1) { *reinterpret_cast<h4v*>(Ah + (lr + 32 * i) * HP + kq) = hi4(ra[i] * sc); continue; }
             h4v hi, lo;
             split4(ra[i] * sc, hi, lo);                          // the scaled split
             *reinterpret_cast<h4v*>(Ah + (lr + 32 * i) * HP + kq) = hi;
             *reinterpret_cast<h4v*>(Al + (lr + 32 * i) * HP + kq) = lo;
         }
+        if (X1 && (t & 7) >= 4) return;
         _Float16* bd = ((t & 7) >= 4 ? Bl : Bh) + lr * HP + (t & 3) * 8;
 #pragma unroll
         for (int i = 0; i < BPASS; ++i) *reinterpret_cast<f4v*>(bd + 32 * i * HP) = rb[i];
     };
 
-    f16v acc[TM][TN], acc1[TM][TN];                              // acc = hi.hi, acc1 = hi.lo + lo.hi (scaled by 2^11)
+    f16v acc[TM][TN], acc1[X1 ? 1 : TM][X1 ? 1 : TN];            // acc = hi.hi, acc1 = hi.lo + lo.hi (scaled by 2^11)
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) { acc[i][j] = (f16v)(0.0f); acc1[i][j] = (f16v)(0.0f); }
+        for (int j = 0; j < TN; ++j) { acc[i][j] = (f16v)(0.0f); if (!X1) acc1[i][j] = (f16v)(0.0f); }
 
     fetch(0);
     for (int ks = 0; ks < ksteps; ++ks) {
@@ -247,18 +268,19 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_kernel(DgradArgs a)
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 ah[i] = *reinterpret_cast<const h8v*>(Ah + ((wm * TM + i) * 32) * HP + foff + kc * 16);
-                al[i] = *reinterpret_cast<const h8v*>(Al + ((wm * TM + i) * 32) * HP + foff + kc * 16);
+                if (!X1) al[i] = *reinterpret_cast<const h8v*>(Al + ((wm * TM + i) * 32) * HP + foff + kc * 16);
             }
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 bh[j] = *reinterpret_cast<const h8v*>(Bh + ((wn * TN + j) * 32) * HP + foff + kc * 16);
-                bl[j] = *reinterpret_cast<const h8v*>(Bl + ((wn * TN + j) * 32) * HP + foff + kc * 16);
+                if (!X1) bl[j] = *reinterpret_cast<const h8v*>(Bl + ((wn * TN + j) * 32) * HP + foff + kc * 16);
             }
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+                    if (X1) continue;
                     acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc1[i][j], 0, 0, 0);
                     acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc1[i][j], 0, 0, 0);
                 }
@@ -275,7 +297,7 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_kernel(DgradArgs a)
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
                 const int r = row0 + (wm * TM + i) * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-                if (r < a.rows) dx[(size_t)r * cs + col] = fmaf(acc1[i][j][reg], 4.8828125e-4f, acc[i][j][reg]) * isc;
+                if (r < a.rows) dx[(size_t)r * cs + col] = (X1 ? acc[i][j][reg] : fmaf(acc1[i][j][reg], 4.8828125e-4f, acc[i][j][reg])) * isc;
             }
         }
     }
@@ -295,13 +317,14 @@ struct WgradArgs {
     int chunk;                               // rows per blockIdx.y, a multiple of 32
 };
 
-__global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradArgs a)
+template <bool X1>
+__global__ __launch_bounds__(256, (X1 ? 4 : 2)) void conv_wgrad_kernel(WgradArgs a)
 {
-    __shared__ __attribute__((aligned(16))) _Float16 lds[4 * 64 * HP];
+    __shared__ __attribute__((aligned(16))) _Float16 lds[(X1 ? 2 : 4) * 64 * HP];
     _Float16* Zh = lds;
-    _Float16* Zl = Zh + 64 * HP;
+    _Float16* Zl = Zh + (X1 ? 0 : 64 * HP);                      // (X1: no lo images; Zl and Al are never touched)
     _Float16* Ah = Zl + 64 * HP;
-    _Float16* Al = Ah + 64 * HP;
+    _Float16* Al = Ah + (X1 ? 0 : 64 * HP);
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = wave >> 1, wn = wave & 1;
@@ -358,12 +381,18 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradArgs a)
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             h4v zh, zl, ah, al;
-            split4(rz[i] * sc, zh, zl);                          // the scaled split
-            split4(ra[i], ah, al);
+            if (X1) { zh = hi4(rz[i] * sc); ah = hi4(ra[i]); }
+            else {
+                split4(rz[i] * sc, zh, zl);                      // the scaled split
+                split4(ra[i], ah, al);
+            }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int o = (32 * i + kq + e) * HP + lr;
-                Zh[o] = zh[e]; Zl[o] = zl[e]; Ah[o] = ah[e]; Al[o] = al[e];
+                Zh[o] = zh[e];
+                if (!X1) Zl[o] = zl[e];
+                Ah[o] = ah[e];
+                if (!X1) Al[o] = al[e];
             }
         }
     };
@@ -379,11 +408,13 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradArgs a)
         const int ao = (wn * 32 + (lane & 31)) * HP + (lane >> 5) * 8;
 #pragma unroll
         for (int kc = 0; kc < 2; ++kc) {
+            h8v zl, al;
             const h8v zh = *reinterpret_cast<const h8v*>(Zh + zo + kc * 16);
-            const h8v zl = *reinterpret_cast<const h8v*>(Zl + zo + kc * 16);
+            if (!X1) zl = *reinterpret_cast<const h8v*>(Zl + zo + kc * 16);
             const h8v ah = *reinterpret_cast<const h8v*>(Ah + ao + kc * 16);
-            const h8v al = *reinterpret_cast<const h8v*>(Al + ao + kc * 16);
+            if (!X1) al = *reinterpret_cast<const h8v*>(Al + ao + kc * 16);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(zh, ah, acc, 0, 0, 0);
+            if (X1) continue;
             acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(zh, al, acc1, 0, 0, 0);
             acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(zl, ah, acc1, 0, 0, 0);
         }
@@ -396,7 +427,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradArgs a)
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
             const int co = co0 + wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-            if (co < a.Cout) w[(size_t)co * Kfull + k] = fmaf(acc1[reg], 4.8828125e-4f, acc[reg]);
+            if (co < a.Cout) w[(size_t)co * Kfull + k] = X1 ? acc[reg] : fmaf(acc1[reg], 4.8828125e-4f, acc[reg]);
         }
     }
 }
@@ -487,21 +518,23 @@ extern "C" int omni_conv2d_bwd_epilogue_f32(const float* grad_out, const float* 
     return OMNI_OK;
 }
 
-extern "C" int omni_conv2d_split_weights_f16x3(const float* wt, void* wt16, int Cout, int K, omni_stream_t stream)
+namespace {
+template <bool X1>
+int split_weights_impl(const float* wt, void* wt16, int Cout, int K, omni_stream_t stream)
 {
     if (!wt || !wt16) OMNI_FAIL(OMNI_ERR_INVALID, "omni_conv2d_split_weights: null pointer");
     if (Cout <= 0 || K <= 0 || K % 32) OMNI_FAIL(OMNI_ERR_INVALID, "omni_conv2d_split_weights: K must be a multiple of 32");
     const size_t total = (size_t)Cout * K;
     if (total * 4 >= (1ull << 31)) OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_conv2d_split_weights: an operand of 2 GiB or more");
-    hipLaunchKernelGGL(conv_wsplit_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, wt, (_Float16*)wt16, Cout, 1,
+    hipLaunchKernelGGL(conv_wsplit_kernel<X1>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, wt, (_Float16*)wt16, Cout, 1,
                        K, 0);
     OMNI_HIP(hipGetLastError());
     return OMNI_OK;
 }
 
-extern "C" int omni_conv2d_bwd_data_f16x3(const float* dz, const float* wt, const float* scale, float* dx1, float* dx2, int M, int H, int W,
-                                          int C1, int C2, int Cout, int KH, int KW, int stride, int pad, void* workspace, size_t ws_bytes,
-                                          omni_stream_t stream)
+template <bool X1>
+int bwd_data_impl(const float* dz, const float* wt, const float* scale, float* dx1, float* dx2, int M, int H, int W, int C1, int C2, int Cout,
+                  int KH, int KW, int stride, int pad, void* workspace, size_t ws_bytes, omni_stream_t stream)
 {
     BwdShape sh; const char* why = "";
     if (const int rc = bwd_shape(M, H, W, C1, C2, Cout, KH, KW, stride, pad, sh, why); rc != OMNI_OK)
@@ -512,7 +545,7 @@ extern "C" int omni_conv2d_bwd_data_f16x3(const float* dz, const float* wt, cons
     hipStream_t s = (hipStream_t)stream;
     const int Cin = C1 + C2;
     const size_t total = (size_t)Cout * sh.K;
-    hipLaunchKernelGGL(conv_wsplit_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, wt, (_Float16*)workspace, Cout, KH * KW, Cin, 1);
+    hipLaunchKernelGGL(conv_wsplit_kernel<X1>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, wt, (_Float16*)workspace, Cout, KH * KW, Cin, 1);
     OMNI_HIP(hipGetLastError());
     DgradArgs a;
     a.dz = dz; a.wt16 = workspace; a.scale = scale; a.dx1 = dx1; a.dx2 = C2 > 0 ? dx2 : nullptr;
@@ -521,19 +554,19 @@ extern "C" int omni_conv2d_bwd_data_f16x3(const float* dz, const float* wt, cons
     if (C1 % 64 == 0 && C2 % 64 == 0) {
         const long long grid = ((sh.rows_in + 63) / 64) * (Cin / 64);
         if (grid >= (1ll << 31)) OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_conv2d_bwd_data: too many blocks");
-        hipLaunchKernelGGL((conv_dgrad_kernel<64, 64, 2, 2>), dim3((unsigned)grid), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((conv_dgrad_kernel<64, 64, 2, 2, X1>), dim3((unsigned)grid), dim3(256), 0, s, a);
     } else {
         const long long grid = ((sh.rows_in + 127) / 128) * (Cin / 32);
         if (grid >= (1ll << 31)) OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_conv2d_bwd_data: too many blocks");
-        hipLaunchKernelGGL((conv_dgrad_kernel<128, 32, 4, 1>), dim3((unsigned)grid), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((conv_dgrad_kernel<128, 32, 4, 1, X1>), dim3((unsigned)grid), dim3(256), 0, s, a);
     }
     OMNI_HIP(hipGetLastError());
     return OMNI_OK;
 }
 
-extern "C" int omni_conv2d_bwd_weight_f16x3(const float* dz, const float* src1, const float* src2, const float* scale, float* dw, int M,
-                                            int H, int W, int C1, int C2, int Cout, int KH, int KW, int stride, int pad, void* workspace,
-                                            size_t ws_bytes, omni_stream_t stream)
+template <bool X1>
+int bwd_weight_impl(const float* dz, const float* src1, const float* src2, const float* scale, float* dw, int M, int H, int W, int C1, int C2,
+                    int Cout, int KH, int KW, int stride, int pad, void* workspace, size_t ws_bytes, omni_stream_t stream)
 {
     BwdShape sh; const char* why = "";
     if (const int rc = bwd_shape(M, H, W, C1, C2, Cout, KH, KW, stride, pad, sh, why); rc != OMNI_OK)
@@ -550,11 +583,50 @@ extern "C" int omni_conv2d_bwd_weight_f16x3(const float* dz, const float* src1, 
     a.M = M; a.H = H; a.W = W; a.C1 = C1; a.C2 = C2; a.Ho = sh.Ho; a.Wo = sh.Wo; a.Cout = Cout;
     a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.rows = (int)sh.rows_out; a.chunk = chunk;
     const int tiles = ((Cout + 63) / 64) * (int)((sh.K / 32 + 1) / 2);
-    hipLaunchKernelGGL(conv_wgrad_kernel, dim3(tiles, (unsigned)nchunks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(conv_wgrad_kernel<X1>, dim3(tiles, (unsigned)nchunks), dim3(256), 0, s, a);
     OMNI_HIP(hipGetLastError());
     const size_t n4 = slab / 4;
     hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, (const float*)workspace, scale, dw, n4,
                        (int)nchunks, slab);
     OMNI_HIP(hipGetLastError());
     return OMNI_OK;
+}
+}  // namespace
+
+extern "C" int omni_conv2d_split_weights_f16x3(const float* wt, void* wt16, int Cout, int K, omni_stream_t stream)
+{
+    return split_weights_impl<false>(wt, wt16, Cout, K, stream);
+}
+
+extern "C" int omni_conv2d_split_weights_f16x1(const float* wt, void* wt16, int Cout, int K, omni_stream_t stream)
+{
+    return split_weights_impl<true>(wt, wt16, Cout, K, stream);
+}
+
+extern "C" int omni_conv2d_bwd_data_f16x3(const float* dz, const float* wt, const float* scale, float* dx1, float* dx2, int M, int H, int W,
+                                          int C1, int C2, int Cout, int KH, int KW, int stride, int pad, void* workspace, size_t ws_bytes,
+                                          omni_stream_t stream)
+{
+    return bwd_data_impl<false>(dz, wt, scale, dx1, dx2, M, H, W, C1, C2, Cout, KH, KW, stride, pad, workspace, ws_bytes, stream);
+}
+
+extern "C" int omni_conv2d_bwd_data_f16x1(const float* dz, const float* wt, const float* scale, float* dx1, float* dx2, int M, int H, int W,
+                                          int C1, int C2, int Cout, int KH, int KW, int stride, int pad, void* workspace, size_t ws_bytes,
+                                          omni_stream_t stream)
+{
+    return bwd_data_impl<true>(dz, wt, scale, dx1, dx2, M, H, W, C1, C2, Cout, KH, KW, stride, pad, workspace, ws_bytes, stream);
+}
+
+extern "C" int omni_conv2d_bwd_weight_f16x3(const float* dz, const float* src1, const float* src2, const float* scale, float* dw, int M,
+                                            int H, int W, int C1, int C2, int Cout, int KH, int KW, int stride, int pad, void* workspace,
+                                            size_t ws_bytes, omni_stream_t stream)
+{
+    return bwd_weight_impl<false>(dz, src1, src2, scale, dw, M, H, W, C1, C2, Cout, KH, KW, stride, pad, workspace, ws_bytes, stream);
+}
+
+extern "C" int omni_conv2d_bwd_weight_f16x1(const float* dz, const float* src1, const float* src2, const float* scale, float* dw, int M,
+                                            int H, int W, int C1, int C2, int Cout, int KH, int KW, int stride, int pad, void* workspace,
+                                            size_t ws_bytes, omni_stream_t stream)
+{
+    return bwd_weight_impl<true>(dz, src1, src2, scale, dw, M, H, W, C1, C2, Cout, KH, KW, stride, pad, workspace, ws_bytes, stream);
 }

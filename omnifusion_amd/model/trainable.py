@@ -2,7 +2,7 @@
 operators of omnifusion_amd.ops, so that `loss.backward()` of train_erp_depth.py:260-294 runs on the device:
 
     from omnifusion_amd.model.trainable import spherical_fusion          # the one import train_erp_depth.py changes
-    net = spherical_fusion(nrows=4, npatches=18, patch_size=(128, 128), fov=(80, 80)).cuda()
+    net = spherical_fusion(nrows=4, npatches=18, patch_size=(128, 128), fov=(80, 80), precision="f16x3").cuda()
     net.load_state_dict(ckpt)                   # the reference's schema (5-D conv weights), 'module.' prefix optional
     depth = net(rgb, confidence=True)           # rgb [B,3,H,W] float32 on the GPU -> [B,1,H,W], with a graph behind it
     loss(depth, gt).backward(); optimiser.step()
@@ -22,8 +22,15 @@ Run by torch operators with autograd (small; tools/train_bench.py reports their 
 ops.BatchNorm2d are the reference's; written as a product and a sum, whose bits repeat), the two broadcast additions
 `layer1 + point_feat` and `layer4 + tokens`, and the reshapes around the transformer.
 
+`precision` (keyword-only; "f16x3" default | "f16x1") is the product mode of every ops.conv2d of the network, forward and
+backward: the ResNet blocks, `down`, the decoder's two-source convolutions and the transformer's linear layers.  "f16x1" is mixed
+precision: fp16 operands, one matrix instruction per product block, fp32 accumulation, the output gradient scaled per tensor on the device.
+The stem, the heads, the point convolutions, the normalisations, attention, GELU, up-sampling and the blend are the same in both modes, and
+so are the parameters, the saved activations (fp32) and the state dict.  Anything else raises ValueError ("fp32": training has no fp32
+product path); the environment's OMNI_NET_PRECISION is not read here.  `net.precision` reports the mode.
+
 The iterative model is model/trainable_iterative.py, a subclass.  Not built: DataParallel /
-SyncBatchNorm / convert_model, fp16, an image gradient, a hand-written optimiser (torch.optim.AdamW steps the parameters), capture of a
+SyncBatchNorm / convert_model, fp16 storage of activations or weights, an image gradient, a hand-written optimiser (torch.optim.AdamW steps the parameters), capture of a
 whole step in a graph.  fp32 CUDA input, one device.
 """
 import ctypes
@@ -50,6 +57,7 @@ class _Conv(nn.Module):
     def __init__(self, cin, cout, k, stride=1, padding=0, bias=False):
         super().__init__()
         self.stride, self.padding = stride, padding
+        self.precision = "f16x3"                                               # the model sets its own on every convolution it holds
         self.weight = nn.Parameter(torch.empty(cout, cin, k, k, 1))
         nn.init.kaiming_normal_(self.weight, mode="fan_out", nonlinearity="relu")
         if bias:
@@ -58,7 +66,8 @@ class _Conv(nn.Module):
             self.register_parameter("bias", None)
 
     def forward(self, x, x2=None, res=None):
-        return ops.conv2d(x, self.weight[..., 0], self.bias, x2=x2, res=res, stride=self.stride, padding=self.padding)
+        return ops.conv2d(x, self.weight[..., 0], self.bias, x2=x2, res=res, stride=self.stride, padding=self.padding,
+                          precision=self.precision)
 
 
 class _Stem(_Conv):
@@ -117,8 +126,9 @@ def _layer(cin, cout, blocks, stride):
 class spherical_fusion(nn.Module):
     _DOWN = "down"                                                             # the token projection's name (trainable_iterative.py: "down1")
 
-    def __init__(self, nrows=4, npatches=18, patch_size=(128, 128), fov=(80, 80)):
+    def __init__(self, nrows=4, npatches=18, patch_size=(128, 128), fov=(80, 80), *, precision="f16x3"):
         super().__init__()
+        self.precision = ops._check_precision("spherical_fusion", precision)
         self.nrows, self.npatches, self.patch_size, self.fov = nrows, npatches, patch_size, fov
         ph, pw = (int(v) for v in pair(patch_size))
         if ph != pw or 32 * (ph // 32) * (pw // 32) != TOKEN_WIDTH or ph % 32:
@@ -133,7 +143,7 @@ class spherical_fusion(nn.Module):
         self.layer1, self.layer2 = _layer(64, 64, 3, 1), _layer(64, 128, 4, 2)
         self.layer3, self.layer4 = _layer(128, 256, 6, 2), _layer(256, 512, 3, 2)
         setattr(self, self._DOWN, _Conv(512, 512 // 16, 1, bias=True))
-        self.transformer = ops.TransformerCascade(TOKEN_WIDTH, npatches, depth=6, num_heads=4)      # encoder_norm: eps 1e-6, block norms 1e-5
+        self.transformer = ops.TransformerCascade(TOKEN_WIDTH, npatches, depth=6, num_heads=4, precision=precision)   # encoder_norm: eps 1e-6, block norms 1e-5
         self.de_conv0_0, self.de_conv0_1 = _ConvBnReLU(512, 256), _ConvBnReLU(256 + 256, 128)
         self.de_conv1_0, self.de_conv1_1 = _ConvBnReLU(128, 128), _ConvBnReLU(128 + 128, 64)
         self.de_conv2_0, self.de_conv2_1 = _ConvBnReLU(64, 64), _ConvBnReLU(64 + 64, 64)
@@ -141,6 +151,9 @@ class spherical_fusion(nn.Module):
         self.de_conv4_0 = _ConvBnReLU(32, 32)
         self.pred, self.weight_pred = _Head(), _Head()
         self._add_point_mlps()
+        for m in self.modules():
+            if isinstance(m, _Conv):
+                m.precision = precision                                        # (the stem and the heads hold parameters only: other kernels)
         self._pool, self._up = ops.MaxPool2d(3, 2, 1), ops.UpsampleBilinear2x()
         cp = (ctypes.c_float * (2 * npatches))()
         if _lib.load().omni_patch_centers(int(nrows), 0, cp) != _lib.OMNI_OK:

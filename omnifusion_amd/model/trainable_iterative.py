@@ -23,7 +23,7 @@ confidence, pers2equi without (the reference's default).  `.eval()` runs the sam
 
 All six 1x1 convolutions of the point MLPs are ops.PointConv2d (csrc/omni_point_conv.hip): fp32 FMAs, a deterministic weight gradient.
 
-Not built: sharing conv1 .. layer1 between the passes, DataParallel / SyncBatchNorm, fp16, an image gradient, capture of
+Not built: sharing conv1 .. layer1 between the passes, DataParallel / SyncBatchNorm, fp16 storage, an image gradient, capture of
 a whole step in a graph, `iter` as a tensor.  fp32 CUDA input, one device.
 """
 import torch
@@ -44,8 +44,8 @@ def _point_mlp(cin):
 class spherical_fusion(trainable.spherical_fusion):
     _DOWN = "down1"
 
-    def __init__(self, nrows=4, npatches=18, patch_size=(256, 256), fov=(80, 80)):
-        super().__init__(nrows, npatches, patch_size, fov)
+    def __init__(self, nrows=4, npatches=18, patch_size=(256, 256), fov=(80, 80), *, precision="f16x3"):
+        super().__init__(nrows, npatches, patch_size, fov, precision=precision)
         self.__dict__["_rays"] = {}                                            # device -> the unit rays; not a buffer: not in the state dict
 
     def _add_point_mlps(self):

@@ -1,12 +1,12 @@
 """Differentiable operators of libomnifusion_hip.so for torch models: the network's convolution and its batch normalisation, each with
 its backward.
 
-    y = conv2d(x, weight, bias=None, *, x2=None, res=None, stride=1, padding=0, act="none" | "relu")
-    layer = Conv2d(64, 64, 3, padding=1, act="relu")          # an nn.Conv2d whose forward is the call above
+    y = conv2d(x, weight, bias=None, *, x2=None, res=None, stride=1, padding=0, act="none" | "relu", precision="f16x3" | "f16x1")
+    layer = Conv2d(64, 64, 3, padding=1, act="relu")          # an nn.Conv2d whose forward is the call above (precision="f16x3")
     y = batch_norm(x, weight=None, bias=None, running_mean=None, running_var=None, *, res=None, training=True, momentum=0.1, eps=1e-5,
                    act="none" | "relu")
     layer = BatchNorm2d(64, act="relu")                       # an nn.BatchNorm2d whose forward(x, res=None) is the call above
-    model, names = convert(model)                             # swaps the nn.Conv2d / nn.BatchNorm2d layers of a torch model in place
+    model, names = convert(model, precision=None)             # swaps the nn.Conv2d / nn.BatchNorm2d layers of a torch model in place
 
 y = act(conv(cat(x, x2), weight) + bias + res) — the operator that is about 99 % of spherical_fusion's work (csrc/omni_conv.hip, f16x3
 products on the matrix cores) — and its gradients w.r.t. x, x2, weight, bias and res (csrc/omni_conv_bwd.hip): the same
@@ -18,12 +18,20 @@ without a copy and y is channels-last; other formats are converted.  Limits: C1,
 materialised), k = 1 or 3, stride 1 or 2, no groups, no dilation; act "gelu" has no backward and is rejected (apply GELU outside).
 No double backward.  There is no CPU path.
 
+`precision` is the arithmetic of the convolution's products, forward and backward of one call alike.  "f16x3" (default):
+every operand a pair of halfs, three matrix instructions per product block, fp32-class results.  "f16x1": the mixed precision of training
+stacks — an operand is fp16(x) alone (0 below 2^-14), one matrix instruction per block, fp32 accumulation; about 2^-11 relative error per
+operand, and an element of the output gradient below 2^-22 of its tensor's largest magnitude counts as 0 (the gradient is scaled into
+[2^8, 2^9) on the device before it is rounded: a per-tensor dynamic loss scale).  Master weights, activations, saved tensors and every
+gradient stay fp32 in both modes; parameters and state dicts do not change.  Anything else raises ValueError: training has no fp32
+product path.  Conv2d, linear, Linear, TransformerBlock and TransformerCascade take the same keyword and expose `.precision`.
+
 y = act(batch_norm(x) + res) (csrc/omni_batchnorm.hip) on x [M,C,H,W], C a multiple of 4: batch statistics over M.H.W with
 `training=True` (the running buffers, when given, are updated in place, the variance unbiased), the running statistics with
 `training=False` (the usual way to fine-tune).  Gradients w.r.t. x, weight, bias and res; the same rules: fixed summation order (in
 double), no atomics, no host synchronisation, only what autograd asks for, channels-last tensors without a copy.  The per-channel
 statistics of a BatchNorm3d over [B,C,P,P,N] are those of this operator over [M = B.N, C, P, P].  Not covered: momentum=None (the
-cumulative average reads a counter on the host), statistics across GPUs, fp16, double backward.
+cumulative average reads a counter on the host), statistics across GPUs, fp16 storage, double backward.
 
 The transformer between layer4 and the decoder (csrc/omni_transformer_bwd.hip), under the reference's state-dict names:
 
@@ -80,6 +88,16 @@ from . import _lib
 from ._lib import ptr as _p
 
 ACTS = {"none": 0, "relu": 1}
+PRECISIONS = ("f16x3", "f16x1")
+
+
+def _check_precision(who, precision):
+    """The product mode of a convolution, validated before anything is launched."""
+    if isinstance(precision, str) and precision in PRECISIONS:
+        return precision
+    if precision == "fp32":
+        raise ValueError(f"{who}: precision='fp32' is not available: training has no fp32 product path (use 'f16x3', fp32-class results)")
+    raise ValueError(f"{who}: precision must be 'f16x3' or 'f16x1' (got {precision!r})")
 _empty = torch.empty          # every buffer of this module is allocated through this name (tests fill them with NaN)
 
 
@@ -149,7 +167,7 @@ def _check_args(x, weight, bias, x2, res, stride, padding, act):
     return k, Ho, Wo
 
 
-def _forward_nhwc(x1, x2, w, bias, res, stride, pad, act):
+def _forward_nhwc(x1, x2, w, bias, res, stride, pad, act, precision="f16x3"):
     """x1 [M,H,W,C1], x2 [M,H,W,C2] | None, w [Cout,k,k,C1+C2], res [M,Ho,Wo,Cout] | None, all contiguous -> y [M,Ho,Wo,Cout]"""
     lib = _lib.load()
     M, H, W, C1 = x1.shape
@@ -157,19 +175,24 @@ def _forward_nhwc(x1, x2, w, bias, res, stride, pad, act):
     Cout, k = w.shape[0], w.shape[1]
     K = k * k * (C1 + C2)
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-    w16 = _empty(Cout * K * 2, dtype=torch.float16, device=x1.device)          # the weights change every step: split on the device
+    x1_mode = precision == "f16x1"
+    split, conv = ((lib.omni_conv2d_split_weights_f16x1, lib.omni_conv2d_nhwc_f16x1_ws) if x1_mode else
+                   (lib.omni_conv2d_split_weights_f16x3, lib.omni_conv2d_nhwc_f16x3_ws))
+    w16 = _empty(Cout * K * (1 if x1_mode else 2), dtype=torch.float16, device=x1.device)   # the weights change every step: split on the device
     y = _empty((M, Ho, Wo, Cout), dtype=torch.float32, device=x1.device)
     with torch.cuda.device(x1.device):
         st = _lib.stream_of(x1)
-        _lib.check(lib.omni_conv2d_split_weights_f16x3(_p(w), _p(w16), Cout, K, st), "conv2d_split_weights")
-        _lib.check(lib.omni_conv2d_nhwc_f16x3_ws(_p(x1), _p(x2), _p(w16), _p(bias), _p(res), _p(y), M, H, W, C1, C2, Cout, k, k, stride, pad,
-                                                 ACTS[act], 1, None, 0, st), "conv2d")
+        _lib.check(split(_p(w), _p(w16), Cout, K, st), "conv2d_split_weights")
+        _lib.check(conv(_p(x1), _p(x2), _p(w16), _p(bias), _p(res), _p(y), M, H, W, C1, C2, Cout, k, k, stride, pad, ACTS[act], 1, None, 0, st),
+                   "conv2d")
     return y
 
 
-def _backward_nhwc(g, y, x1, x2, w, stride, pad, act, need_x1, need_x2, need_w):
+def _backward_nhwc(g, y, x1, x2, w, stride, pad, act, need_x1, need_x2, need_w, precision="f16x3"):
     """The three calls of the backward on contiguous NHWC tensors.  Returns (dx1, dx2, dw, dbias, dz); dz is the residual's gradient."""
     lib = _lib.load()
+    bwd_data, bwd_weight = ((lib.omni_conv2d_bwd_data_f16x1, lib.omni_conv2d_bwd_weight_f16x1) if precision == "f16x1" else
+                            (lib.omni_conv2d_bwd_data_f16x3, lib.omni_conv2d_bwd_weight_f16x3))
     M, H, W, C1 = x1.shape
     C2 = x2.shape[3] if x2 is not None else 0
     Cout, k = w.shape[0], w.shape[1]
@@ -190,21 +213,20 @@ def _backward_nhwc(g, y, x1, x2, w, stride, pad, act, need_x1, need_x2, need_w):
         if need_x1 or need_x2:
             dx1 = _empty((M, H, W, C1), dtype=torch.float32, device=dev) if need_x1 else None
             dx2 = _empty((M, H, W, C2), dtype=torch.float32, device=dev) if need_x2 else None
-            _lib.check(lib.omni_conv2d_bwd_data_f16x3(_p(dz), _p(w), _p(scale), _p(dx1), _p(dx2), *shape, _p(ws), nbytes, st), "conv2d_bwd_data")
+            _lib.check(bwd_data(_p(dz), _p(w), _p(scale), _p(dx1), _p(dx2), *shape, _p(ws), nbytes, st), "conv2d_bwd_data")
         if need_w:
             dw = _empty(tuple(w.shape), dtype=torch.float32, device=dev)
-            _lib.check(lib.omni_conv2d_bwd_weight_f16x3(_p(dz), _p(x1), _p(x2), _p(scale), _p(dw), *shape, _p(ws), nbytes, st),
-                       "conv2d_bwd_weight")
+            _lib.check(bwd_weight(_p(dz), _p(x1), _p(x2), _p(scale), _p(dw), *shape, _p(ws), nbytes, st), "conv2d_bwd_weight")
     return dx1, dx2, dw, dbias, dz
 
 
 class _Conv2d(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, x2, weight, bias, res, stride, padding, act):
+    def forward(ctx, x, x2, weight, bias, res, stride, padding, act, precision):
         x1n, x2n, wn, resn = _nhwc(x), _nhwc(x2), _nhwc(weight), _nhwc(res)
         b = bias.contiguous() if bias is not None else None
-        y = _forward_nhwc(x1n, x2n, wn, b, resn, stride, padding, act)
-        ctx.conf = (stride, padding, act)
+        y = _forward_nhwc(x1n, x2n, wn, b, resn, stride, padding, act, precision)
+        ctx.conf = (stride, padding, act, precision)
         ctx.save_for_backward(x1n, x2n, wn, y if act == "relu" else None)
         return _nchw(y)
 
@@ -212,24 +234,29 @@ class _Conv2d(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         x1n, x2n, wn, y = ctx.saved_tensors
-        stride, padding, act = ctx.conf
+        stride, padding, act, precision = ctx.conf
         need = ctx.needs_input_grad
         g = _nhwc(grad_out.to(torch.float32))
-        dx1, dx2, dw, dbias, dz = _backward_nhwc(g, y, x1n, x2n, wn, stride, padding, act, need[0], x2n is not None and need[1], need[2])
-        return (_nchw(dx1), _nchw(dx2), _nchw(dw), dbias if need[3] else None, _nchw(dz) if need[4] else None, None, None, None)
+        dx1, dx2, dw, dbias, dz = _backward_nhwc(g, y, x1n, x2n, wn, stride, padding, act, need[0], x2n is not None and need[1], need[2],
+                                                 precision)
+        return (_nchw(dx1), _nchw(dx2), _nchw(dw), dbias if need[3] else None, _nchw(dz) if need[4] else None, None, None, None, None)
 
 
-def conv2d(x, weight, bias=None, *, x2=None, res=None, stride=1, padding=0, act="none"):
-    """act(conv(cat(x, x2), weight) + bias + res), differentiable w.r.t. x, x2, weight, bias and res (module docstring)."""
+def conv2d(x, weight, bias=None, *, x2=None, res=None, stride=1, padding=0, act="none", precision="f16x3"):
+    """act(conv(cat(x, x2), weight) + bias + res), differentiable w.r.t. x, x2, weight, bias and res; `precision` ("f16x3" | "f16x1") is
+    the product mode of the forward and of the backward (module docstring)."""
+    _check_precision("conv2d", precision)
     _check_args(x, weight, bias, x2, res, stride, padding, act)
-    return _Conv2d.apply(x, x2, weight, bias, res, stride, padding, act)
+    return _Conv2d.apply(x, x2, weight, bias, res, stride, padding, act, precision)
 
 
 class Conv2d(torch.nn.Conv2d):
     """nn.Conv2d with the library's kernels under forward and backward, so that a torch model can swap its layers: the same parameters and
-    state dict.  `act` ("none" | "relu") is fused; forward(x, x2=None, res=None) takes the optional second source and residual."""
+    state dict.  `act` ("none" | "relu") is fused; forward(x, x2=None, res=None) takes the optional second source and residual;
+    `precision` ("f16x3" | "f16x1") is the product mode of its forward and backward."""
 
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True, act="none", **kw):
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True, act="none", precision="f16x3", **kw):
+        _check_precision("ops.Conv2d", precision)
         super().__init__(in_channels, out_channels, kernel_size, stride=stride, padding=padding, bias=bias, **kw)
         if self.groups != 1 or tuple(self.dilation) != (1, 1) or self.padding_mode != "zeros" or isinstance(self.padding, str):
             raise ValueError("ops.Conv2d: no groups, no dilation, zero padding given as a number")
@@ -238,9 +265,14 @@ class Conv2d(torch.nn.Conv2d):
         if act not in ACTS:
             raise ValueError(f"ops.Conv2d: act must be 'none' or 'relu' (got {act!r}; GELU has no backward here)")
         self.act = act
+        self.precision = precision
 
     def forward(self, x, x2=None, res=None):
-        return conv2d(x, self.weight, self.bias, x2=x2, res=res, stride=self.stride[0], padding=self.padding[0], act=self.act)
+        return conv2d(x, self.weight, self.bias, x2=x2, res=res, stride=self.stride[0], padding=self.padding[0], act=self.act,
+                      precision=self.precision)
+
+    def extra_repr(self):
+        return f"{super().extra_repr()}, act={self.act}, precision={self.precision}"
 
 
 # ------------------------------------------------------------------------------------------------ batch normalisation
@@ -540,27 +572,39 @@ def attention(q, kv, batch):
     return _Attention.apply(q, kv, batch, N)
 
 
-def linear(x, weight, bias=None, res=None):
+def linear(x, weight, bias=None, res=None, precision="f16x3"):
     """x W^T + bias + res for x [rows, K], weight [out, K], res [rows, out]: conv2d on [rows, K, 1, 1] (its kernels, its backward, its
-    checks: K and out multiples of 32)."""
+    checks: K and out multiples of 32; its `precision`)."""
+    _check_precision("linear", precision)
     _check_f32_dev((("x", x), ("weight", weight), ("bias", bias), ("res", res)), optional=("bias", "res"))
     if x.dim() != 2 or weight.dim() != 2 or x.numel() == 0:
         raise ValueError(f"x must be a non-empty [rows, K] tensor and weight [out, K] (got {tuple(x.shape)} and {tuple(weight.shape)})")
     rows, out = x.shape[0], weight.shape[0]
     if res is not None and tuple(res.shape) != (rows, out):
         raise ValueError(f"res must have the result's shape {(rows, out)} (got {tuple(res.shape)})")
-    y = conv2d(x[:, :, None, None], weight[:, :, None, None], bias, res=res[:, :, None, None] if res is not None else None)
+    y = conv2d(x[:, :, None, None], weight[:, :, None, None], bias, res=res[:, :, None, None] if res is not None else None,
+               precision=precision)
     return y.reshape(rows, out)
 
 
 class Linear(torch.nn.Linear):
-    """nn.Linear with the convolution's kernels under forward and backward; forward(x [..., K], res=None) adds the residual in the kernel."""
+    """nn.Linear with the convolution's kernels under forward and backward; forward(x [..., K], res=None) adds the residual in the kernel.
+    `precision` ("f16x3" | "f16x1") is the convolution's product mode."""
+
+    def __init__(self, in_features, out_features, bias=True, precision="f16x3", **kw):
+        _check_precision("ops.Linear", precision)
+        super().__init__(in_features, out_features, bias=bias, **kw)
+        self.precision = precision
+
+    def extra_repr(self):
+        return f"{super().extra_repr()}, precision={self.precision}"
 
     def forward(self, x, res=None):
         if not isinstance(x, torch.Tensor) or x.dim() < 1:
             raise ValueError("x must be a tensor on an MI355X device; there is no CPU path")
         lead = x.shape[:-1]
-        y = linear(x.reshape(-1, x.shape[-1]), self.weight, self.bias, res.reshape(-1, self.out_features) if res is not None else None)
+        y = linear(x.reshape(-1, x.shape[-1]), self.weight, self.bias, res.reshape(-1, self.out_features) if res is not None else None,
+                   precision=self.precision)
         return y.reshape(*lead, self.out_features)
 
 
@@ -570,29 +614,36 @@ def _check_transformer_conf(who, dim, num_heads):
 
 
 class _AttentionLayers(torch.nn.Module):
-    def __init__(self, dim):
+    def __init__(self, dim, precision="f16x3"):
         super().__init__()
-        self.q, self.kv, self.proj = Linear(dim, dim, bias=False), Linear(dim, 2 * dim, bias=False), Linear(dim, dim)
+        self.q, self.kv = Linear(dim, dim, bias=False, precision=precision), Linear(dim, 2 * dim, bias=False, precision=precision)
+        self.proj = Linear(dim, dim, precision=precision)
 
 
 class _MlpLayers(torch.nn.Module):
-    def __init__(self, dim):
+    def __init__(self, dim, precision="f16x3"):
         super().__init__()
-        self.fc1, self.fc2 = Linear(dim, 4 * dim), Linear(4 * dim, dim)
+        self.fc1, self.fc2 = Linear(dim, 4 * dim, precision=precision), Linear(4 * dim, dim, precision=precision)
 
 
 class TransformerBlock(torch.nn.Module):
     """The reference's pre-LN block under its parameter names (norm1, attn.q, attn.kv, attn.proj, norm2, mlp.fc1, mlp.fc2):
     x + proj(attention(q(norm1 x), kv(norm1 x))), then x + fc2(gelu(fc1(norm2 x))); the two additions are the `res` of proj and fc2.
-    forward(x [B.N, 512], batch = B).  Dropout and drop-path are identity in the reference's configuration and are not built."""
+    forward(x [B.N, 512], batch = B).  Dropout and drop-path are identity in the reference's configuration and are not built.
+    `precision` is the product mode of the five linear layers; layer norm, attention and GELU are fp32 in both modes."""
 
-    def __init__(self, dim=ATT_DIM, num_heads=ATT_HEADS):
+    def __init__(self, dim=ATT_DIM, num_heads=ATT_HEADS, precision="f16x3"):
         _check_transformer_conf("ops.TransformerBlock", dim, num_heads)
+        _check_precision("ops.TransformerBlock", precision)
         super().__init__()
+        self.precision = precision
         self.norm1 = LayerNorm(dim, eps=1e-5)
-        self.attn = _AttentionLayers(dim)
+        self.attn = _AttentionLayers(dim, precision)
         self.norm2 = LayerNorm(dim, eps=1e-5)
-        self.mlp = _MlpLayers(dim)
+        self.mlp = _MlpLayers(dim, precision)
+
+    def extra_repr(self):
+        return f"precision={self.precision}"
 
     def forward(self, x, batch):
         y = self.norm1(x)
@@ -605,17 +656,22 @@ class TransformerCascade(torch.nn.Module):
     """The reference's Transformer_cascade under its parameter names (pos_emb [1, num_patch, 512], layer.{i}, encoder_norm with eps 1e-6):
     forward(x [bs, num_patch, 512]) -> [bs, num_patch, 512].  The `transformer.*` entries of a spherical_fusion state dict load into it."""
 
-    def __init__(self, emb_dims=ATT_DIM, num_patch=18, depth=6, num_heads=ATT_HEADS):
+    def __init__(self, emb_dims=ATT_DIM, num_patch=18, depth=6, num_heads=ATT_HEADS, precision="f16x3"):
         _check_transformer_conf("ops.TransformerCascade", emb_dims, num_heads)
+        _check_precision("ops.TransformerCascade", precision)
         if not isinstance(num_patch, int) or not 1 <= num_patch <= ATT_MAX_N:
             raise ValueError(f"ops.TransformerCascade: 1 to {ATT_MAX_N} patches (got num_patch = {num_patch!r})")
         if not isinstance(depth, int) or depth < 1:
             raise ValueError(f"ops.TransformerCascade: depth >= 1 (got {depth!r})")
         super().__init__()
-        self.layer = torch.nn.ModuleList([TransformerBlock(emb_dims, num_heads) for _ in range(depth)])
+        self.precision = precision
+        self.layer = torch.nn.ModuleList([TransformerBlock(emb_dims, num_heads, precision) for _ in range(depth)])
         self.encoder_norm = LayerNorm(emb_dims, eps=1e-6)
         self.pos_emb = torch.nn.Parameter(torch.zeros(1, num_patch, emb_dims))
         torch.nn.init.normal_(self.pos_emb, std=0.02)
+
+    def extra_repr(self):
+        return f"precision={self.precision}"
 
     def forward(self, x):
         _check_f32_dev((("x", x),))
@@ -1027,16 +1083,21 @@ def _swap_class(old, cls):
     return new
 
 
-def convert(module, spatial=False):
+def convert(module, spatial=False, precision=None):
     """Replaces, in place, every nn.Conv2d inside Conv2d's scope (module docstring) and every nn.BatchNorm2d (channels a multiple of 4, a
     numeric momentum) by the class of this module, act="none".  The new layers hold the SAME Parameter and buffer objects, so an optimiser
     built before or after sees the same tensors and the state dict keeps its keys.  Everything else — a 3-channel stem, grouped or dilated
     convolutions, momentum=None layers, subclasses — is left alone.  With `spatial=True` the stem, nn.Conv2d(3, 64, 7, stride=2,
     padding=3) (no groups, no dilation, zero padding; a bias is allowed), becomes a StemConv2d and nn.MaxPool2d(3, 2, 1) (dilation 1,
-    ceil_mode=False, return_indices=False) a MaxPool2d as well.  Returns (module, [the names replaced])."""
+    ceil_mode=False, return_indices=False) a MaxPool2d as well.  `precision` ("f16x3" | "f16x1"; None = the default, "f16x3") is the
+    product mode of every Conv2d created.  Returns (module, [the names replaced])."""
+    precision = _check_precision("convert", "f16x3" if precision is None else precision)
+
     def swapped(m):
         if type(m) is torch.nn.Conv2d and _conv_in_scope(m):
-            return _swap_class(m, Conv2d)
+            new = _swap_class(m, Conv2d)
+            new.precision = precision
+            return new
         if type(m) is torch.nn.BatchNorm2d and m.momentum is not None and m.num_features % 4 == 0:
             return _swap_class(m, BatchNorm2d)
         if spatial and type(m) is torch.nn.Conv2d and _stem_in_scope(m):

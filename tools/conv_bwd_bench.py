@@ -1,6 +1,7 @@
 """Data and weight gradient of the convolution (csrc/omni_conv_bwd.hip) at the network's layer shapes, B = 8 panoramas x 18 patches (M = 144).
 
-    python tools/conv_bwd_bench.py [--m 144] [--iters 20] [--repeats 3] [--only 0,3] [--out profiles/r17a_conv_bwd.json]
+    python tools/conv_bwd_bench.py [--m 144] [--iters 20] [--repeats 3] [--only 0,3] [--precision f16x3|f16x1|both]
+                                   [--out profiles/r17a_conv_bwd.json]
 
 Per layer (the shapes of tools/convbench.py), in ONE process and one run, each timed with device events around `iters` back-to-back calls after
 a warm-up of the same calls, the median of `repeats` windows:
@@ -8,7 +9,11 @@ a warm-up of the same calls, the median of `repeats` windows:
     dgrad   omni_conv2d_bwd_data_f16x3 (includes the per-call weight repack)        t_dgrad / t_fwd
     wgrad   omni_conv2d_bwd_weight_f16x3 (partial sums + the ordered second pass)     t_wgrad / t_fwd
     torch   torch.nn.grad.conv2d_input / conv2d_weight, fp32, channels-last, same GPU  t_dgrad / t_torch_dgrad, t_wgrad / t_torch_wgrad
-The gradient epilogue (one element-wise pass) is timed on its own.  There is no GPU -> the tool fails; it never falls back.
+The gradient epilogue (one element-wise pass) is timed on its own.
+--precision f16x1 times the single-product entry points in the same way.  --precision both times the two modes INTERLEAVED:
+per kernel (fwd, dgrad, wgrad) the windows alternate f16x3, f16x1, f16x3, ... in one process, and a row holds per mode the median, the
+smallest and the largest window, the ratio f16x1 / f16x3 of the medians and the run's own spread (largest - smallest window over the
+median, the larger of the two modes); torch is not timed then.  There is no GPU -> the tool fails; it never falls back.
 Writes the rows with the library's source hash; the README quotes the ratios from that file.
 """
 import argparse
@@ -52,12 +57,38 @@ def timed(fn, iters, repeats):
     return statistics.median(out)
 
 
+def timed_interleaved(fns, iters, repeats):
+    """[{median, min, max} per function], seconds: the windows of the functions alternate, so that clock and thermal drift reach all alike"""
+    for fn in fns:
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    out = [[] for _ in fns]
+    for _ in range(repeats):
+        for i, fn in enumerate(fns):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            out[i].append(e0.elapsed_time(e1) / iters * 1e-3)
+    return [{"median": statistics.median(v), "min": min(v), "max": max(v)} for v in out]
+
+
+def entry_points(lib, precision):
+    sfx = "_" + precision
+    return (getattr(lib, "omni_conv2d_split_weights" + sfx), getattr(lib, "omni_conv2d_nhwc" + sfx + "_ws"),
+            getattr(lib, "omni_conv2d_bwd_data" + sfx), getattr(lib, "omni_conv2d_bwd_weight" + sfx))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--m", type=int, default=144)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--only", default="")
+    ap.add_argument("--precision", default="f16x3", choices=("f16x3", "f16x1", "both"))
     ap.add_argument("--out", default=os.path.join("profiles", "r17a_conv_bwd.json"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -92,12 +123,33 @@ def main():
         def ok(rc):
             assert rc == 0, lib.omni_last_error()
 
-        ok(lib.omni_conv2d_split_weights_f16x3(P(w), P(w16), Cout, K, S()))
-        fwd = lambda: ok(lib.omni_conv2d_nhwc_f16x3_ws(P(x1), P(x2), P(w16), P(b), None, P(out), M, H, W, C1, C2, Cout, k, k, s, pad, 1, sk,
-                                                       P(fws), ctypes.c_size_t(fws.numel() * 4), S()))
+        def calls(precision, w16):
+            split, conv, bdata, bweight = entry_points(lib, precision)
+            ok(split(P(w), P(w16), Cout, K, S()))
+            return {"fwd": lambda: ok(conv(P(x1), P(x2), P(w16), P(b), None, P(out), M, H, W, C1, C2, Cout, k, k, s, pad, 1, sk, P(fws),
+                                           ctypes.c_size_t(fws.numel() * 4), S())),
+                    "dgrad": lambda: ok(bdata(P(dz), P(w), P(scale), P(dx1), P(dx2), *shape, P(ws), nbytes, S())),
+                    "wgrad": lambda: ok(bweight(P(dz), P(x1), P(x2), P(scale), P(dw), *shape, P(ws), nbytes, S()))}
+
         epi = lambda: ok(lib.omni_conv2d_bwd_epilogue_f32(P(g), P(out), P(dz), P(dbias), P(scale), M * Ho * Wo, Cout, 1, P(ws), nbytes, S()))
-        dgrad = lambda: ok(lib.omni_conv2d_bwd_data_f16x3(P(dz), P(w), P(scale), P(dx1), P(dx2), *shape, P(ws), nbytes, S()))
-        wgrad = lambda: ok(lib.omni_conv2d_bwd_weight_f16x3(P(dz), P(x1), P(x2), P(scale), P(dw), *shape, P(ws), nbytes, S()))
+        if a.precision == "both":
+            c3, c1 = calls("f16x3", w16), calls("f16x1", torch.empty(Cout * K, dtype=torch.float16, device=dev))
+            c3["fwd"]()
+            epi()
+            row = {"layer": name, "M": M, "H": H, "W": W, "C1": C1, "C2": C2, "Cout": Cout, "k": k, "stride": s, "pad": pad, "splitk_fwd": sk,
+                   "us": {}, "f16x1_over_f16x3": {}, "spread": {}}
+            for key in ("fwd", "dgrad", "wgrad"):
+                t3, t1 = timed_interleaved([c3[key], c1[key]], a.iters, a.repeats)
+                row["us"][key] = {m: {q: round(v * 1e6, 2) for q, v in t.items()} for m, t in (("f16x3", t3), ("f16x1", t1))}
+                row["f16x1_over_f16x3"][key] = round(t1["median"] / t3["median"], 3)
+                row["spread"][key] = round(max((t["max"] - t["min"]) / t["median"] for t in (t3, t1)), 3)
+            rows_out.append(row)
+            print("%-10s " % name + " | ".join("%s %8.1f -> %8.1f us (x%.3f, spread %.3f)" % (
+                key, row["us"][key]["f16x3"]["median"], row["us"][key]["f16x1"]["median"], row["f16x1_over_f16x3"][key], row["spread"][key])
+                for key in ("fwd", "dgrad", "wgrad")), flush=True)
+            continue
+        c = calls(a.precision, w16)
+        fwd, dgrad, wgrad = c["fwd"], c["dgrad"], c["wgrad"]
         fwd()
         epi()
         # torch, fp32, channels-last views of the same storage
@@ -127,8 +179,9 @@ def main():
         print("%-10s fwd %8.1f us | dgrad %8.1f (%5.2fx fwd, %5.2fx torch) | wgrad %8.1f (%5.2fx fwd, %5.2fx torch) | epilogue %7.1f | rel. diff to torch %.1e %.1e"
               % (name, t["fwd"] * 1e6, t["dgrad"] * 1e6, row["dgrad_over_fwd"], row["dgrad_over_torch"], t["wgrad"] * 1e6, row["wgrad_over_fwd"],
                  row["wgrad_over_torch"], t["epilogue"] * 1e6, ed, ew), flush=True)
-    res = {"tool": "tools/conv_bwd_bench.py", "source_hash": build.source_hash(), "device": torch.cuda.get_device_name(0), "M": M,
-           "iters": a.iters, "repeats": a.repeats, "timing": "device events, median of the windows, warm-up of 3 calls per shape",
+    res = {"tool": "tools/conv_bwd_bench.py", "precision": a.precision, "source_hash": build.source_hash(), "device": torch.cuda.get_device_name(0), "M": M,
+           "iters": a.iters, "repeats": a.repeats, "timing": "device events, median of the windows, warm-up of 3 calls per shape" +
+           ("; the windows of the two modes alternate" if a.precision == "both" else ""),
            "grad_out_scale": 1e-6, "rows": rows_out}
     os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
     with open(a.out, "w") as f:

@@ -1,7 +1,7 @@
 """One training step of the trainable spherical_fusion (omnifusion_amd/model/trainable.py) on one MI355X, at 8 panoramas of
 512 x 1024, nrows 4 (M = 144 patches of 128 x 128), random weights make_state_dict(42, 18).
 
-    python tools/train_bench.py [--bs 8] [--iters 5] [--repeats 3] [--out profiles/r21a_train_step.json]
+    python tools/train_bench.py [--bs 8] [--iters 5] [--repeats 3] [--precision f16x3|f16x1|both] [--out profiles/r21a_train_step.json]
 
 In ONE process and one run, each row timed with device events around `iters` back-to-back calls after a warm-up of the same calls; the
 median of `repeats` windows with the smallest and the largest beside it:
@@ -17,6 +17,9 @@ median of `repeats` windows with the smallest and the largest beside it:
                          point_feat, the token reshape and layer4 + tokens; `torch_pieces_share` is their sum over train_fwd_bwd
     floor                302 MB (the [144,128,128,32] tensor once) at 8 TB/s per heads kernel
     peak_memory          torch.cuda.max_memory_allocated over one training step of either model
+--precision f16x1 builds the trainable model with precision="f16x1" (DESIGN.md §27).  --precision both times ONLY the training step, of
+two models that differ in the mode alone, with the windows alternating f16x3, f16x1, f16x3, ... in one process: per mode the median, the
+smallest and the largest window and the peak memory, their ratio, and whether the f16x1 median lies below the smallest f16x3 window.
 There is no GPU -> the tool fails; it never falls back.  Writes the rows with the library's source hash; DESIGN §23 and the README quote them.
 """
 import argparse
@@ -64,6 +67,24 @@ def timed(fn, iters, repeats, warm=2):
     return {"median_s": statistics.median(out), "min_s": min(out), "max_s": max(out)}
 
 
+def timed_interleaved(fns, iters, repeats, warm=2):
+    for fn in fns:
+        for _ in range(warm):
+            fn()
+    torch.cuda.synchronize()
+    out = [[] for _ in fns]
+    for _ in range(repeats):
+        for i, fn in enumerate(fns):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            out[i].append(e0.elapsed_time(e1) / iters * 1e-3)
+    return [{"median_s": statistics.median(v), "min_s": min(v), "max_s": max(v), "windows_s": v} for v in out]
+
+
 def peak(fn):
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
@@ -78,6 +99,7 @@ def main():
     ap.add_argument("--bs", type=int, default=8)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--precision", default="f16x3", choices=("f16x3", "f16x1", "both"))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r21a_train_step.json"))
     a = ap.parse_args()
     assert torch.cuda.is_available(), "train_bench needs an MI355X"
@@ -88,14 +110,40 @@ def main():
     sd = make_state_dict(42, N)
     rows = {}
 
-    net = trainable.spherical_fusion(NROWS, N, (P, P), FOV)
-    net.load_state_dict(sd)
-    net.to(DEV)
+    def model(precision):
+        m = trainable.spherical_fusion(NROWS, N, (P, P), FOV, precision=precision)
+        m.load_state_dict(sd)
+        return m.to(DEV)
 
-    def train_step():
-        for p in net.parameters():
-            p.grad = None
-        (net(rgb, confidence=True) * g).sum().backward()
+    def step_of(m):
+        def step():
+            for p in m.parameters():
+                p.grad = None
+            (m(rgb, confidence=True) * g).sum().backward()
+        return step
+
+    if a.precision == "both":
+        modes = ("f16x3", "f16x1")
+        steps = [step_of(model(m)) for m in modes]
+        for m, t, st in zip(modes, timed_interleaved(steps, a.iters, a.repeats), steps):
+            rows["train_fwd_bwd_" + m] = t
+            t["peak_memory_bytes"] = peak(st)
+        r3, r1 = rows["train_fwd_bwd_f16x3"], rows["train_fwd_bwd_f16x1"]
+        result = {"tool": "tools/train_bench.py", "precision": "both", "device": torch.cuda.get_device_name(0),
+                  "source_hash": build.source_hash(), "panoramas": bs, "erp": [H, W], "nrows": NROWS, "patches": M, "iters": a.iters,
+                  "repeats": a.repeats, "timing": "device events; the windows of the two modes alternate", "rows": rows,
+                  "f16x1_over_f16x3": r1["median_s"] / r3["median_s"],
+                  "f16x1_median_below_f16x3_min": r1["median_s"] < r3["min_s"],
+                  "peak_memory_f16x1_over_f16x3": r1["peak_memory_bytes"] / r3["peak_memory_bytes"]}
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        print(json.dumps(result))
+        return
+
+    net = model(a.precision)
+    train_step = step_of(net)
     rows["train_fwd_bwd"] = timed(train_step, a.iters, a.repeats)
     rows["train_fwd_bwd"]["peak_memory_bytes"] = peak(train_step)
 
@@ -180,7 +228,7 @@ def main():
 
     floor = M * P * P * 32 * 4 / HBM
     result = {
-        "tool": "tools/train_bench.py", "device": torch.cuda.get_device_name(0), "source_hash": build.source_hash(),
+        "tool": "tools/train_bench.py", "precision": a.precision, "device": torch.cuda.get_device_name(0), "source_hash": build.source_hash(),
         "panoramas": bs, "erp": [H, W], "nrows": NROWS, "patches": M, "iters": a.iters, "repeats": a.repeats,
         "rows": rows, "heads_floor_s": floor,
         "train_over_torch": rows["train_fwd_bwd"]["median_s"] / rows["torch_fwd_bwd"]["median_s"],
