@@ -819,7 +819,8 @@ extern "C" int omni_sh_overflow(int* flag, int reset)
     unsigned v = 0;
     if (omni_sh_overflow_conv(&v, reset) != 0 || omni_sh_overflow_halo(&v, reset) != 0 || omni_sh_overflow_up2(&v, reset) != 0 ||
         omni_sh_overflow_rows(&v, reset) != 0 || omni_sh_overflow_net(&v, reset) != 0 || omni_sh_overflow_pm(&v, reset) != 0 ||
-        omni_sh_overflow_halo2(&v, reset) != 0 || omni_sh_overflow_up2_taps(&v, reset) != 0)
+        omni_sh_overflow_halo2(&v, reset) != 0 || omni_sh_overflow_up2_taps(&v, reset) != 0 ||
+        omni_sh_overflow_up2_heads_taps(&v, reset) != 0)
         OMNI_FAIL(OMNI_ERR_HIP, "omni_sh_overflow: could not read the device flag");
     *flag = v ? 1 : 0;
     return OMNI_OK;

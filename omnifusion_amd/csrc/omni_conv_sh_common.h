@@ -299,6 +299,10 @@ int omni_sh_overflow_pm(unsigned* out, int reset);
 int omni_halo2_launch(const void* args, int iw, bool x1, unsigned grid, hipStream_t s);
 int omni_sh_overflow_halo2(unsigned* out, int reset);
 int omni_sh_overflow_up2_taps(unsigned* out, int reset);  // omni_conv_up2_taps.hip's (up2_taps_fused_kernel; its entry point lives in that unit)
+// omni_conv_up2_heads_taps.hip: up2_heads_taps_kernel, de_conv4_0 + the heads' first half as tap products on the low-resolution map (f16x3, P == 128 only: src SH
+// [M, 64, 64, 32], hr = the scratch of omni_conv3x3_up2_heads_sh_f16x3) on one persistent block of 512 threads per CU
+int omni_up2_heads_taps_launch(const void* src, const void* wt16, const float* bias, const void* heads_w16f, float* hr, int M, hipStream_t s);
+int omni_sh_overflow_up2_heads_taps(unsigned* out, int reset);
 // the sticky range flag of omni_sh.h, one copy per translation unit whose kernels write SH: omni_sh_overflow (omni_conv_sh.hip) reads them all
 int omni_sh_overflow_halo(unsigned* out, int reset);
 int omni_sh_overflow_up2(unsigned* out, int reset);

@@ -400,8 +400,15 @@ static int up2_heads_impl(const void* src, const void* wt16, const float* bias, 
     a.M = M; a.H = P; a.W = P; a.C1 = 32; a.C2 = 0; a.Cout = 32; a.KH = 3; a.KW = 3; a.stride = 1; a.pad = 1; a.act = OMNI_ACT_RELU;
     a.Ho = P; a.Wo = P; a.rows = M * P * P; a.splitk = 1; a.ws = nullptr; a.post = nullptr; a.post_rows = 1; a.wino_th = a.wino_tw = a.wino_pix = 0;
     const int grid = M * (P / 4) * (P / HT_W);
-    hipLaunchKernelGGL((conv3x3_up2_g1_kernel<true, X1>), dim3(grid < 256 ? (grid + 7) / 8 * 8 : 256), dim3(64 * (4 + OMNI_G1_PW)), 0, (hipStream_t)stream, a, grid, HeadsArgs{heads_w16f, scratch});
-    OMNI_HIP(hipGetLastError());
+    // f16x3 at P == 128 with conv_up2_heads_taps: the tap products on the 64 x 64 map (omni_conv_up2_heads_taps.hip; a band needs the full low-resolution width of 64)
+    const bool taps = !X1 && P == 128 && omni_options().conv_up2_heads_taps == 1 &&
+                      !((uintptr_t)src % 16 || (uintptr_t)wt16 % 16 || (uintptr_t)bias % 16 || (uintptr_t)heads_w16f % 16 || (uintptr_t)scratch % 16);
+    if (taps) {
+        if (const int rc = omni_up2_heads_taps_launch(src, wt16, bias, heads_w16f, scratch, M, (hipStream_t)stream); rc != OMNI_OK) return rc;
+    } else {
+        hipLaunchKernelGGL((conv3x3_up2_g1_kernel<true, X1>), dim3(grid < 256 ? (grid + 7) / 8 * 8 : 256), dim3(64 * (4 + OMNI_G1_PW)), 0, (hipStream_t)stream, a, grid, HeadsArgs{heads_w16f, scratch});
+        OMNI_HIP(hipGetLastError());
+    }
     const size_t n = (size_t)M * P * P / 4;
     hipLaunchKernelGGL(heads_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)scratch, bias_pred, bias_weight,
                        out_a, out_c, M, P, confidence);

@@ -23,7 +23,8 @@ void omni_set_error(const std::string& msg);
 // `omni_set_option()` (include/omnifusion.h) changes one at run time (tests and tools sweep tile shapes with it).  No option
 // changes a result bit except the three that change the K summation ORDER of a convolution: `splitk_max`, `conv_img` (16-wide images on
 // the halo kernel: K runs (tap, group) per channel group instead of im2col order) and the latency form a lone panorama selects (fmt bit 2
-// of omni_conv2d_sh_f16x3_ws) — results then agree to ~2e-5, not bit for bit (tests assert exactly that).  Launch paths read the struct, never getenv().
+// of omni_conv2d_sh_f16x3_ws) — results then agree to ~2e-5, not bit for bit (tests assert exactly that) — and `conv_up2_heads_taps`, which selects another form
+// of the same sum for de_conv4_0 (tap products summed in fp32: ~1e-6).  Launch paths read the struct, never getenv().
 struct OmniOptions {
     int conv_sh_tile;     // OMNI_CONV_SH_TILE   -1 auto (8-wave 256x128 / 128x128 / 128x64 where >= 128 blocks remain) | 0 64x64 | 1 128x64 | 2 128x128 | 3, 4 the 8-wave forms | 5..7 auto without 256x128 (64 / 128 / 256 blocks) | 8 = auto | 9 = auto without the loader waves
     int conv_nohalo;      // OMNI_CONV_NOHALO    1: never take the halo-reuse 3x3 kernel
@@ -42,6 +43,7 @@ struct OmniOptions {
     int conv_stem_pc;     // OMNI_CONV_STEM_PC   1 (default): the stem with producer / consumer waves (8 waves, two image buffers: +2 % one forward at a time, nothing pipelined) | 0: 4 waves
     int conv_epi_lds;     // OMNI_CONV_EPI_LDS   1 (default): split-half outputs of the convolution kernels leave through an LDS transposition, 16 bytes per lane | 0: 8 bytes per lane straight from the accumulators
     int conv_up2_persist; // OMNI_CONV_UP2_PERSIST 1 (default): conv3x3(up2(x)) with 32 -> 32 channels (de_conv4_0) on the persistent kernel with resident weights | 0: the halo kernel
+    int conv_up2_heads_taps; // OMNI_CONV_UP2_HEADS_TAPS 1 (default; profiles/EXPERIMENTS.md, r29a): de_conv4_0 + heads (omni_conv3x3_up2_heads_sh_f16x3) at patches of 128 x 128 on up2_heads_taps_kernel (omni_conv_up2_heads_taps.hip: tap products on the low-resolution map; another fp32 summation order than the g1 kernel's, results agree to ~1e-6) | 0: conv3x3_up2_g1_kernel<HEADS>, which f16x1 and every other patch size keep whatever this says
     int splitk_max;       // OMNI_SPLITK_MAX     cap of the split-K plan (0 = none)
     int e2p_gather;       // OMNI_E2P_GATHER     1: equi2pers always takes the direct-gather kernel (no LDS staging)
     int e2p_notab;        // OMNI_E2P_NOTAB      1: no per-geometry sampling-coordinate table
