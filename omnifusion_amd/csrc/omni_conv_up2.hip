@@ -2,6 +2,7 @@
 // heads_finish_kernel, and the entry points omni_conv3x3_up2_sh_f16x3, omni_conv3x3_up2_heads_sh_f16x3 / _f16x1, omni_heads_pack_f16x3.
 // The other up-sampling shapes run conv3x3_halo_sh_kernel<.., UP2> (omni_conv_halo.hip) through omni_halo_launch.
 #include "omni_conv_sh_common.h"
+#include "omni_heads_hr.h"
 
 namespace {
 
@@ -22,11 +23,9 @@ namespace {
 // x[p] lives in registers, contributes w[dy][dx] . x[p] to q = p - (dy,dx) — eighteen 32-channel dot products per pixel (9 taps x 2 heads), which are
 // ONE more matrix product: rows = (dy, head, dx), k = the 32 channels in the order the accumulator quads already hold them (a lane's 16 channels
 // are its two k chunks: no data movement), three f16x3 terms like every other product = 6 matrix instructions per wave and tile beside the 54 of
-// the convolution.  The three dx terms of a row are summed across neighbouring lanes (fixed order dx = -1, 0, +1), which leaves per tile row and
-// (dy, head) 34 partial sums — pixels -1 .. 32: the two outer ones belong to the neighbouring tiles' pixels — written to `hr`
-// [tile][row 4][(dy, head) 6][32 sums | pixel -1 | pixel 32 | 2 pad]: 3.4 KB per tile instead of 16 KB.  heads_finish_kernel adds the three rows (dy) and the neighbour tiles'
-// outer sums in a fixed order, then bias, ReLU / sigmoid and the product.  Deterministic; equal to heads_kernel up to fp32 summation order.
-constexpr int HR_PITCH = 36;                                 // floats per (tile row, (dy, head)) record of `hr`: 32 sums, pixel -1, pixel 32, 2 of padding (16-byte rows)
+// the convolution.  The product, the sum of its three dx terms across neighbouring lanes and the record `hr` they leave — 3.4 KB per tile instead of
+// 16 KB — are omni_heads_hr.h's.  heads_finish_kernel adds the three rows (dy) and the neighbour tiles' outer sums in a fixed order, then bias, ReLU /
+// sigmoid and the product.  Deterministic; equal to heads_kernel up to fp32 summation order.
 struct HeadsArgs { const void* w16; float* hr; };           // w16: the heads' weights in fragment order (Engine: heads.w16f), [hi kc0, hi kc1, lo kc0, lo kc1][64 lanes] x 16 B
 
 template <bool HEADS, bool X1 = false>                       // X1: f16x1 for the convolution (acc_join); the heads' own products stay f16x3
@@ -154,29 +153,12 @@ __global__ __launch_bounds__(HEADS ? 64 * (4 + OMNI_G1_PW) : 512) void conv3x3_u
                     for (int e = 0; e < 4; ++e) { ph[q >> 1][4 * (q & 1) + e] = hi[e]; pl[q >> 1][4 * (q & 1) + e] = lo[e]; }
                 }
                 if (OMNI_ABL(32768)) { if (ph[0][0] == (_Float16)77.0f && pl[1][3] == (_Float16)3.0f) hd.hr[1] = 1.0f; if (wave == 0) stamp(0, it, 2); }
-                f16v d0 = (f16v)(0.0f), d1 = (f16v)(0.0f);
-#pragma unroll
-                for (int kc = 0; kc < 2; ++kc) {
-                    d0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(hwf[kc], ph[kc], d0, 0, 0, 0);
-                    d1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(hwf[2 + kc], ph[kc], d1, 0, 0, 0);
-                    d1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(hwf[kc], pl[kc], d1, 0, 0, 0);
-                }
-                // rows (reg & 3) + 8 (reg >> 2) + 4 h: register group g = 0..2 is (dy, head) pair g + 3h, its registers 0..2 are dx = -1, 0, +1
+                f16v d0, d1;
+                heads_product(hwf, ph, pl, d0, d1);
                 if (OMNI_ABL(32768)) { if (d0[0] == 12345.678f && d1[5] == 3.0f) hd.hr[2] = 1.0f; if (wave == 0) stamp(0, it, 3); }
                 const int px = lane & 31, h = lane >> 5;
                 float* hp = hd.hr + ((size_t)tile * TH + wave) * (6 * HR_PITCH);
-#pragma unroll
-                for (int g = 0; g < 3; ++g) {
-                    const float tl = fmaf(d1[4 * g], 4.8828125e-4f, d0[4 * g]), tc = fmaf(d1[4 * g + 1], 4.8828125e-4f, d0[4 * g + 1]),
-                                tr = fmaf(d1[4 * g + 2], 4.8828125e-4f, d0[4 * g + 2]);
-                    // out[q] takes w[dx] . x[q + dx]: its dx = -1 term comes from pixel q - 1, its dx = +1 term from pixel q + 1
-                    const float fl = __shfl_up(tl, 1, 32), fr = __shfl_down(tr, 1, 32);
-                    const float sum = ((px > 0 ? fl : 0.0f) + tc) + (px < 31 ? fr : 0.0f);
-                    float* row = hp + (g + 3 * h) * HR_PITCH;
-                    row[px] = sum;
-                    if (px == 0) row[32] = tr;                     // pixel -1 of this row (the left neighbour tile's column 31) takes my dx = +1 term
-                    if (px == 31) row[33] = tl;                    // pixel 32 takes my dx = -1 term
-                }
+                OMNI_HEADS_HR_WRITE(d0, d1, hp, px, h)
             } else
             {   // epilogue of this tile: column lane & 31 = pixel x0 + (lane & 31) of image row y0 + wave (through an LDS transposition, split-half or
                 // fp32: 247 | 248 us — the stores are not this kernel's limit, and 18 KB of LDS more per block are felt beside other kernels)

@@ -18,24 +18,22 @@
 //     up2_taps_fused_kernel does, the launch took 183 us instead of 173 at 144 patches).  The next band's fragments are loaded as soon as the ninth tap's
 //     products are issued;
 //   * per tap: 6 matrix instructions per fragment (the f16x3 three-term product, acc_join) -> the fp32 products [pixel][32 channels] in one of two LDS
-//     chunks (48 KiB) -> ONE barrier -> the SEPARABLE tap sum of up2_taps_fused_kernel: taps kx-major (0, 3, 6, 1, 4, 7, 2, 5, 8), a vertical stage per tap
-//     on the thread's own column, a horizontal stage once per kx whose neighbour columns come through the chunk that is not in use (two more barriers per
-//     kx).  Thread = (low-res column j, channel quad): four 2 x 2 output cells x 4 channels = 64 accumulator registers + 32 for the vertical stage.  Same
-//     weights, clamps, order of summation and chunk piece permutation as there; tests/test_up2_taps_sep_cpu.py is the specification;
+//     chunks (48 KiB) -> ONE barrier -> the SEPARABLE tap sum of omni_up2_tapsum.h with ROWS = 4 (the one up2_taps_fused_kernel runs: same tap order, weights,
+//     clamps, order of summation and chunk piece permutation), two more barriers per kx around its horizontal stage.  Thread = (low-res column j, channel
+//     quad): four 2 x 2 output cells x 4 channels = 64 accumulator registers + 32 for the vertical stage;
 //   * heads: bias, ReLU and sh_split4 (range guard, sticky flag) as every SH epilogue; the band's 8 x 128 output pixels are parked in the chunks as SH rows
 //     in two halves of 4 rows (64 KiB each) with the 16-byte pieces in FRAGMENT order — piece 2 kc + h of a pixel holds channel quads 4 kc + h and
 //     4 kc + 2 + h, the k order in which the g1 kernel's accumulator quads meet `heads.w16f` — so the heads' product of a 32-pixel row segment is four
 //     ds_read_b128 and the same six matrix instructions, the three dx terms meet across neighbouring lanes in the order -1, 0, +1, and the 34 partial sums
-//     per (tile row, (dy, head)) land in `hr` at the addresses and with the meaning conv3x3_up2_g1_kernel<HEADS> gives them (tile = 4 output rows x 32
-//     pixels, HR_PITCH = 36).  heads_finish_kernel runs unchanged.
+//     per (tile row, (dy, head)) land in `hr` through the product and the record writer conv3x3_up2_g1_kernel<HEADS> uses (omni_heads_hr.h; tile = 4 output
+//     rows x 32 pixels).  heads_finish_kernel runs unchanged.
 // Fixed order, no atomics but the sticky flag, no dependence on block placement or on M: an image's bits are the same alone and inside a batch.
 // LDS: 36 KiB + 2 x 48 KiB = 132 KiB, one block of eight waves per CU, at most 256 registers per lane, no scratch.
 #include <stdint.h>
-#include "omni_conv_sh_common.h"
+#include "omni_up2_tapsum.h"
+#include "omni_heads_hr.h"
 
 namespace {
-
-constexpr int HR_PITCH = 36;                 // floats per (tile row, (dy, head)) record of `hr`, as in omni_conv_up2.hip (heads_finish_kernel reads it)
 
 struct HeadsTapsArgs {
     const void* src;                         // SH [M, 64, 64, 32]
@@ -49,9 +47,6 @@ struct HeadsTapsArgs {
 constexpr int WL = 64, HL = 64, ROWS = 4, SROWS = ROWS + 2, NPX = SROWS * WL, NF = NPX / 32;
 constexpr int TAP_BYTES = 32 * 128, W_BYTES = 9 * TAP_BYTES, CH_BYTES = NPX * 128, ROW_BYTES = WL * 128;
 constexpr int BANDS_PER_IMG = HL / ROWS;
-
-// the tap (ky * 3 + kx) processed at step s: kx-major, 0, 3, 6, 1, 4, 7, 2, 5, 8 — the three taps of a column kx follow each other
-__host__ __device__ constexpr int tap_at(int s) { return 3 * (s % 3) + s / 3; }
 
 __global__ __launch_bounds__(512, 1) void up2_heads_taps_kernel(HeadsTapsArgs a)
 {
@@ -103,9 +98,7 @@ __global__ __launch_bounds__(512, 1) void up2_heads_taps_kernel(HeadsTapsArgs a)
 
     // ---- tap sum geometry: thread = (low-res column j, channel quad), rows i = r0 + it, it = 0 .. 3
     const int quad = t & 7, j = t >> 3;
-    // byte offset of column col in a chunk row, the lane's channel quad (chunk pieces are permuted with (pixel >> 1) & 3)
-    auto col_off = [&](int col) { return col * 128 + ((quad ^ ((col >> 1) & 3)) * 16); };
-    const int coff1 = col_off(j);
+    const int coff1 = tapsum_col_off(j, quad);
     wait_vm<0>();                                                 // my pieces of the weights have landed (and my first pixel fragments)
     __builtin_amdgcn_s_barrier();                                 // everybody's have
     asm volatile("" ::: "memory");
@@ -115,9 +108,7 @@ __global__ __launch_bounds__(512, 1) void up2_heads_taps_kernel(HeadsTapsArgs a)
         const int r0 = band * ROWS, sbase = r0 - 1;               // sbase: image row of LDS slot row 0
         const int next = bandid + nlb;
         // the rows' weights: only a thread's first row can be the map's top, only its fourth the map's bottom (block-uniform)
-        const bool top = r0 == 0, bot = r0 + ROWS - 1 == HL - 1;
-        const float hy0[4] = {top ? 0.0f : 0.75f, top ? 1.0f : 0.25f, 0.75f, 0.25f}, ly0[4] = {top ? 0.0f : 0.25f, top ? 0.0f : 0.75f, 0.25f, 0.75f};
-        const float hy3 = bot ? 0.0f : 0.25f, ly3 = bot ? 0.0f : 0.75f;
+        const TapsumRowW wy = tapsum_row_weights(r0 == 0, r0 + ROWS - 1 == HL - 1);
 
         f4v out[ROWS][2][2];                                      // the 2 x 2 output cells of rows i, column j (written, not added to, by the first column group)
         f4v S[ROWS][2];                                           // the vertical sums of the column group kx in flight: up-sampled rows 2i + ay of low-res column j
@@ -145,15 +136,7 @@ __global__ __launch_bounds__(512, 1) void up2_heads_taps_kernel(HeadsTapsArgs a)
                         acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[kc], xl[fi][kc], acc1, 0, 0, 0);
                     }
                     const int px = frag(fi) * 32 + (lane & 31);
-                    unsigned char* cp = chunk + px * 128;
-                    const int sw = (px >> 1) & 3;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {                 // channels 8q + 4 (lane >> 5) .. + 3 of pixel px
-                        f4v v;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = acc_join<false>(acc1[4 * q + e], acc[4 * q + e]);
-                        *reinterpret_cast<f4v*>(cp + (((2 * q + (lane >> 5)) ^ sw) * 16)) = v;
-                    }
+                    tapsum_park(acc1, acc, chunk + px * 128, (px >> 1) & 3, lane >> 5);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -161,80 +144,25 @@ __global__ __launch_bounds__(512, 1) void up2_heads_taps_kernel(HeadsTapsArgs a)
             wait_lds_reads();                                     // my products are in the chunk (and my reads of the weights have returned)
             __builtin_amdgcn_s_barrier();                         // everybody's are; everybody is done reading the OTHER chunk (step s - 1)
             asm volatile("" ::: "memory");
-            // ---- vertical stage: S (+)= the tap, on my own column.  The thread's column of the chunk is read once: rows r0 - 1 + k, k = 0 .. 5 (5 / 6 / 5 of them
-            // for ky = 0 / 1 / 2), clamped to the map; up-sampled row 2i + ay + ky - 1 takes the row pair (it + r, it + r + 1), r = (ay + ky) >> 1
-            {
-                constexpr int klo = ky >> 1, khi = ROWS + ((ky + 1) >> 1);
-                f4v R[ROWS + 2];
-#pragma unroll
-                for (int k = klo; k <= khi; ++k)
-                    R[k] = *reinterpret_cast<const f4v*>(chunk + (min(max(r0 - 1 + k, 0), HL - 1) - sbase) * ROW_BYTES + coff1);
-#pragma unroll
-                for (int it = 0; it < ROWS; ++it)
-#pragma unroll
-                    for (int ay = 0; ay < 2; ++ay) {
-                        const int uy = ay + ky, r = uy >> 1;
-                        // weights of up-sampled row 2i + uy - 1 (rows 1 and 2 of a thread are never the map's edge)
-                        const float h = it == 0 ? hy0[uy] : it == ROWS - 1 && uy == 3 ? hy3 : (uy & 1) ? 0.25f : 0.75f;
-                        const float l = it == 0 ? ly0[uy] : it == ROWS - 1 && uy == 3 ? ly3 : (uy & 1) ? 0.75f : 0.25f;
-                        f4v v;                                    // the first tap of a column group starts S
-                        if constexpr (ky != 0) v = S[it][ay];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if constexpr (ky == 0) v[e] = fmaf(l, R[it + r + 1][e], h * R[it + r][e]);
-                            else v[e] = fmaf(l, R[it + r + 1][e], fmaf(h, R[it + r][e], v[e]));
-                        asm volatile("" : "+v"(v));               // pins the sum HERE: the compiler otherwise sinks the arithmetic below later barriers
-                        S[it][ay] = v;
-                    }
-                __builtin_amdgcn_sched_barrier(0);                // one tap's column in flight at a time
-            }
-            // ---- horizontal stage, after the third tap of a column group: out (+)= hx * S[column j - 1 + c] + lx * S[column j + c], c = (bx + kx) >> 1.  The
-            // neighbour columns' S live in other threads: they are exchanged through the chunks, in the chunks' own layout (row it, coff[]).  One ay half is
-            // 32 KiB: ay = 0 goes to the chunk this step did not use, ay = 1 to this step's chunk once everybody has left its vertical stage.
+            tapsum_vertical<ROWS, ky, ROW_BYTES>(S, chunk, r0, sbase, HL, coff1, wy);
+            // ---- horizontal stage, after the third tap of a column group.  The neighbour columns' S live in other threads: one ay half is 32 KiB: ay = 0 goes to
+            // the chunk this step did not use, ay = 1 to this step's chunk once everybody has left its vertical stage.
             if constexpr (ky == 2) {
                 unsigned char* other = lds + W_BYTES + ((s & 1) ^ 1) * CH_BYTES;
                 auto horizontal = [&]<int ay>(const unsigned char* buf) {
                     // The column's constants are formed HERE, from a copy of j the compiler cannot see through: kept across the band they cost 10 registers the
-                    // products' phase does not have.  Bilinear weights of up-sampled column 2j + u - 1, u = 0 .. 3, on the column pair (c, c + 1), c = u >> 1:
-                    // (1 - l, l) with l = frac(max(0.5 (p + 0.5) - 0.5, 0)), zero where the column is outside the map
+                    // products' phase does not have.
                     int jj = j;
                     asm volatile("" : "+v"(jj));
-                    const int coff[3] = {col_off(max(jj - 1, 0)), 0, col_off(min(jj + 1, WL - 1))};
                     float hx[4], lx[4];
-                    hx[0] = jj > 0 ? 0.75f : 0.0f;      lx[0] = jj > 0 ? 0.25f : 0.0f;
-                    hx[1] = jj > 0 ? 0.25f : 1.0f;      lx[1] = jj > 0 ? 0.75f : 0.0f;
-                    hx[2] = 0.75f;                      lx[2] = 0.25f;
-                    hx[3] = jj < WL - 1 ? 0.25f : 0.0f; lx[3] = jj < WL - 1 ? 0.75f : 0.0f;
-#pragma unroll
-                    for (int it = 0; it < ROWS; ++it) {
-                        const unsigned char* rp = buf + it * ROW_BYTES;
-                        const f4v own = S[it][ay];
-                        f4v left = own, right = own;              // (only the live one is read: kx = 0 never looks right, kx = 2 never left)
-                        if (kx <= 1) left = *reinterpret_cast<const f4v*>(rp + coff[0]);
-                        if (kx >= 1) right = *reinterpret_cast<const f4v*>(rp + coff[2]);
-#pragma unroll
-                        for (int bx = 0; bx < 2; ++bx) {
-                            const int ux = bx + kx, c = ux >> 1;
-                            const f4v va = c == 0 ? left : own, vb = c == 0 ? own : right;
-                            f4v o;                                // the first column group starts out
-                            if constexpr (kx != 0) o = out[it][ay][bx];
-#pragma unroll
-                            for (int e = 0; e < 4; ++e)
-                                if constexpr (kx == 0) o[e] = fmaf(lx[ux], vb[e], hx[ux] * va[e]);
-                                else o[e] = fmaf(lx[ux], vb[e], fmaf(hx[ux], va[e], o[e]));
-                            asm volatile("" : "+v"(o));           // (pinned like the vertical sums)
-                            out[it][ay][bx] = o;
-                        }
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
+                    tapsum_col_weights<WL>(jj, hx, lx);
+                    tapsum_horizontal<ROWS, kx, ay, ROW_BYTES>(out, S, buf, 0, tapsum_col_off(max(jj - 1, 0), quad), tapsum_col_off(min(jj + 1, WL - 1), quad), hx, lx);
                 };
-#pragma unroll
-                for (int it = 0; it < ROWS; ++it) *reinterpret_cast<f4v*>(other + it * ROW_BYTES + coff1) = S[it][0];
+                tapsum_put<ROWS, 0, ROW_BYTES>(S, other, 0, coff1);
                 wait_lds_reads();                                 // my ay = 0 sums are in `other` (and my reads of this step's products have returned)
                 __builtin_amdgcn_s_barrier();                     // everybody's are; everybody has left the vertical stage: this step's chunk is free
                 asm volatile("" ::: "memory");
-#pragma unroll
-                for (int it = 0; it < ROWS; ++it) *reinterpret_cast<f4v*>(chunk + it * ROW_BYTES + coff1) = S[it][1];
+                tapsum_put<ROWS, 1, ROW_BYTES>(S, chunk, 0, coff1);
                 __builtin_amdgcn_sched_barrier(0);
                 horizontal.template operator()<0>(other);
                 wait_lds_reads();                                 // my ay = 1 sums are in the chunk, my reads of `other` have returned
@@ -291,28 +219,11 @@ __global__ __launch_bounds__(512, 1) void up2_heads_taps_kernel(HeadsTapsArgs a)
                     ph[kc] = *reinterpret_cast<const h8v*>(fp + (fo ^ (2 * kc * 16)));
                     pl[kc] = *reinterpret_cast<const h8v*>(fp + (fo ^ ((2 * kc + 4) * 16)));
                 }
-                f16v d0 = (f16v)(0.0f), d1 = (f16v)(0.0f);
-#pragma unroll
-                for (int kc = 0; kc < 2; ++kc) {
-                    d0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(hwf[kc], ph[kc], d0, 0, 0, 0);
-                    d1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(hwf[2 + kc], ph[kc], d1, 0, 0, 0);
-                    d1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(hwf[kc], pl[kc], d1, 0, 0, 0);
-                }
-                // rows (reg & 3) + 8 (reg >> 2) + 4 h: register group g = 0..2 is (dy, head) pair g + 3h, its registers 0..2 are dx = -1, 0, +1
+                f16v d0, d1;
+                heads_product(hwf, ph, pl, d0, d1);
                 const size_t tile = ((size_t)m * (2 * BANDS_PER_IMG) + 2 * band + half) * 4 + sx;
                 float* hp = a.hr + (tile * 4 + row) * (6 * HR_PITCH);
-#pragma unroll
-                for (int g = 0; g < 3; ++g) {
-                    const float tl = fmaf(d1[4 * g], 4.8828125e-4f, d0[4 * g]), tc = fmaf(d1[4 * g + 1], 4.8828125e-4f, d0[4 * g + 1]),
-                                tr = fmaf(d1[4 * g + 2], 4.8828125e-4f, d0[4 * g + 2]);
-                    // out[q] takes w[dx] . x[q + dx]: its dx = -1 term comes from pixel q - 1, its dx = +1 term from pixel q + 1
-                    const float fl = __shfl_up(tl, 1, 32), fr = __shfl_down(tr, 1, 32);
-                    const float sum = ((px > 0 ? fl : 0.0f) + tc) + (px < 31 ? fr : 0.0f);
-                    float* rowp = hp + (g + 3 * h) * HR_PITCH;
-                    rowp[px] = sum;
-                    if (px == 0) rowp[32] = tr;                   // pixel -1 of this row (the left neighbour tile's column 31) takes my dx = +1 term
-                    if (px == 31) rowp[33] = tl;                  // pixel 32 takes my dx = -1 term
-                }
+                OMNI_HEADS_HR_WRITE(d0, d1, hp, px, h)
             }
         }
         if (next >= b_end) break;

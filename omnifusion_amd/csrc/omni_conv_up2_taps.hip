@@ -13,18 +13,13 @@
 //   * per tap: 12 matrix instructions per fragment (the f16x3 three-term product, acc_join) -> the fp32 products of the tap, [pixel][32 channels], parked in
 //     one of two LDS chunks (40 KiB) -> ONE barrier -> every thread takes the tap into its sums: thread = (low-res column j, channel quad),
 //     eight 2 x 2 output cells (rows 2i, 2i+1 x columns 2j, 2j+1 for eight rows i) x 4 channels = 128 registers;
-//   * the tap sum is SEPARABLE (both the up-sampling and the tap shift are): taps are taken kx-major (0, 3, 6, 1, 4, 7, 2, 5, 8).  Per tap a VERTICAL
-//     stage on the thread's own column, S[it][ay] (+)= hy[ay + ky] * Y[row i - 1 + r] + ly[ay + ky] * Y[row i + r], r = (ay + ky) >> 1 (64 registers; the
-//     column's 9 / 10 / 9 rows are read once per tap); after the three ky taps of a kx a HORIZONTAL stage, out[it][ay][bx] (+)= hx[bx + kx] * S[column
-//     j - 1 + c] + lx[bx + kx] * S[column j + c], c = (bx + kx) >> 1, whose neighbour columns live in other threads and come through the chunks (two more
-//     barriers per kx).  15 FMAs per output element instead of the 36 of a tap-by-tap bilinear sum; tests/test_up2_taps_sep_cpu.py is the specification;
+//   * the tap sum is the SEPARABLE one of omni_up2_tapsum.h (tap order, chunk layout, weight tables, vertical and horizontal stage: all there), ROWS = 8: 64
+//     registers for the vertical sums, the column's 9 / 10 / 9 rows read once per tap, two more barriers per kx around the horizontal stage;
 //   * outputs leave through act_store4<true> (saturation, sticky range flag).
-// Weights and clamps of up2_tapsum_sh_kernel (omni_net.hip), NOT its order of summation: the same bilinear weights (0.25 / 0.75 are exact, so the
-// tables below hold the values its index arithmetic yields), source rows / columns clamped to the map.  A tap outside the up-sampled map gets weight
-// zero instead of being skipped.  Fixed order, no atomics, no dependence on block placement: an image's bits do not depend on M.
+// Fixed order, no atomics, no dependence on block placement: an image's bits do not depend on M.
 // LDS: 72 KiB + 2 x 40 KiB = 152 KiB, one block of four waves per CU with up to 512 registers per lane.
 #include <stdint.h>
-#include "omni_conv_sh_common.h"
+#include "omni_up2_tapsum.h"
 
 namespace {
 
@@ -51,9 +46,6 @@ __device__ __forceinline__ void wait_taps_in_flight(int n)
     else if (n == 2) wait_vm<2>();
     else wait_vm<0>();
 }
-
-// the tap (ky * 3 + kx) processed at step s: kx-major, 0, 3, 6, 1, 4, 7, 2, 5, 8 — the three taps of a column kx follow each other
-__host__ __device__ constexpr int tap_at(int s) { return 3 * (s % 3) + s / 3; }
 
 template <int WL, int ROWS, int HALO>
 __global__ __launch_bounds__(256, 1) void up2_taps_fused_kernel(TapsArgs a)
@@ -114,24 +106,13 @@ __global__ __launch_bounds__(256, 1) void up2_taps_fused_kernel(TapsArgs a)
     // ---- tap sum geometry: thread = (low-res column j, channel quad), rows i = r0 + ib + it, it = 0 .. 7
     const int quad = t & 7, j = (t >> 3) & (WL - 1);
     const int ib = WL == 32 ? 0 : 8 * (wave >> 1);
-    int coff[3];                                                  // byte offset of columns clamp(j - 1 + c) in a chunk row, the lane's channel quad (chunk pieces are permuted with (pixel >> 1) & 3)
+    int coff[3];                                                  // tapsum_col_off of columns clamp(j - 1 + c), the lane's channel quad
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int col = min(max(j - 1 + c, 0), WL - 1);
-        coff[c] = col * 128 + ((quad ^ ((col >> 1) & 3)) * 16);
-    }
-    // bilinear weights of up-sampled column 2j + u - 1, u = 0 .. 3, on the column pair (c, c + 1), c = u >> 1: (1 - l, l) with l = frac(max(0.5 (p + 0.5) - 0.5, 0)),
-    // zero where the column is outside the map
+    for (int c = 0; c < 3; ++c) coff[c] = tapsum_col_off(min(max(j - 1 + c, 0), WL - 1), quad);
     float hx[4], lx[4];
-    hx[0] = j > 0 ? 0.75f : 0.0f;      lx[0] = j > 0 ? 0.25f : 0.0f;
-    hx[1] = j > 0 ? 0.25f : 1.0f;      lx[1] = j > 0 ? 0.75f : 0.0f;
-    hx[2] = 0.75f;                     lx[2] = 0.25f;
-    hx[3] = j < WL - 1 ? 0.25f : 0.0f; lx[3] = j < WL - 1 ? 0.75f : 0.0f;
-
-    // the same for the rows: only a thread's first row can be the map's top, only its eighth the map's bottom (wave-uniform)
-    const bool top = r0 + ib == 0, bot = r0 + ib + 7 == Hl - 1;
-    const float hy0[4] = {top ? 0.0f : 0.75f, top ? 1.0f : 0.25f, 0.75f, 0.25f}, ly0[4] = {top ? 0.0f : 0.25f, top ? 0.0f : 0.75f, 0.25f, 0.75f};
-    const float hy7 = bot ? 0.0f : 0.25f, ly7 = bot ? 0.0f : 0.75f;
+    tapsum_col_weights<WL>(j, hx, lx);
+    // the rows' weights: only a thread's first row can be the map's top, only its eighth the map's bottom (wave-uniform)
+    const TapsumRowW wy = tapsum_row_weights(r0 + ib == 0, r0 + ib + 7 == Hl - 1);
 
     f4v out[8][2][2];                                             // the 2 x 2 output cells of rows i, column j (written, not added to, by the first column group)
     f4v S[8][2];                                                  // the vertical sums of the column group kx in flight: up-sampled rows 2i + ay of low-res column j
@@ -165,15 +146,7 @@ __global__ __launch_bounds__(256, 1) void up2_taps_fused_kernel(TapsArgs a)
                         acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[kc], xl[fi][kc], acc1, 0, 0, 0);
                     }
                     const int px = f * 32 + (lane & 31);
-                    unsigned char* cp = chunk + px * 128;
-                    const int sw = (px >> 1) & 3;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {                 // channels 8q + 4 (lane >> 5) .. + 3 of pixel px
-                        f4v v;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = acc_join<false>(acc1[4 * q + e], acc[4 * q + e]);
-                        *reinterpret_cast<f4v*>(cp + (((2 * q + (lane >> 5)) ^ sw) * 16)) = v;
-                    }
+                    tapsum_park(acc1, acc, chunk + px * 128, (px >> 1) & 3, lane >> 5);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -182,76 +155,22 @@ __global__ __launch_bounds__(256, 1) void up2_taps_fused_kernel(TapsArgs a)
         wait_lds_reads();                                         // my products are in the chunk (and my reads of the weights have returned)
         __builtin_amdgcn_s_barrier();                             // everybody's are; everybody is done reading the OTHER chunk (step s - 1)
         asm volatile("" ::: "memory");
-        // ---- vertical stage: S (+)= the tap, on my own column.  The thread's column of the chunk is read once: rows i0 - 1 + k, k = 0 .. 9 (9 / 10 / 9 of them
-        // for ky = 0 / 1 / 2), clamped to the map; up-sampled row 2i + ay + ky - 1 takes the row pair (it + r, it + r + 1), r = (ay + ky) >> 1
-        {
-            constexpr int klo = ky >> 1, khi = 8 + ((ky + 1) >> 1);
-            f4v R[10];
-#pragma unroll
-            for (int k = klo; k <= khi; ++k)
-                R[k] = *reinterpret_cast<const f4v*>(chunk + (min(max(r0 + ib - 1 + k, 0), Hl - 1) - sbase) * ROW_BYTES + coff[1]);
-#pragma unroll
-            for (int it = 0; it < 8; ++it)
-#pragma unroll
-                for (int ay = 0; ay < 2; ++ay) {
-                    const int uy = ay + ky, r = uy >> 1;
-                    // weights of up-sampled row 2i + uy - 1 (rows 1 .. 6 of a thread are never the map's edge)
-                    const float h = it == 0 ? hy0[uy] : it == 7 && uy == 3 ? hy7 : (uy & 1) ? 0.25f : 0.75f;
-                    const float l = it == 0 ? ly0[uy] : it == 7 && uy == 3 ? ly7 : (uy & 1) ? 0.75f : 0.25f;
-                    f4v v;                                        // the first tap of a column group starts S
-                    if constexpr (ky != 0) v = S[it][ay];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if constexpr (ky == 0) v[e] = fmaf(l, R[it + r + 1][e], h * R[it + r][e]);
-                        else v[e] = fmaf(l, R[it + r + 1][e], fmaf(h, R[it + r][e], v[e]));
-                    asm volatile("" : "+v"(v));                   // pins the sum HERE: the compiler otherwise sinks the arithmetic below later barriers
-                    S[it][ay] = v;                                // and spills everything it read from the chunks meanwhile
-                }
-            __builtin_amdgcn_sched_barrier(0);                    // one tap's column in flight at a time
-        }
-        // ---- horizontal stage, after the third tap of a column group: out (+)= hx * S[column j - 1 + c] + lx * S[column j + c], c = (bx + kx) >> 1.  The
-        // neighbour columns' S live in other threads (other waves at j % 8 == 0 / 7): they are exchanged through the chunks, in the chunks' own layout
-        // (row ib + it, coff[]: conflict-free like the product reads).  One ay half is 32 KiB: ay = 0 goes to the chunk this step did not use, ay = 1 to
-        // this step's chunk once everybody has left its vertical stage.
+        tapsum_vertical<8, ky, ROW_BYTES>(S, chunk, r0 + ib, sbase, Hl, coff[1], wy);
+        // ---- horizontal stage, after the third tap of a column group.  The neighbour columns' S live in other threads (other waves at j % 8 == 0 / 7): one ay
+        // half is 32 KiB: ay = 0 goes to the chunk this step did not use, ay = 1 to this step's chunk once everybody has left its vertical stage.
         if constexpr (ky == 2) {
             unsigned char* other = lds + W_BYTES + ((s & 1) ^ 1) * CH_BYTES;
-            auto horizontal = [&]<int ay>(const unsigned char* buf) {
-#pragma unroll
-                for (int it = 0; it < 8; ++it) {
-                    const unsigned char* rp = buf + (ib + it) * ROW_BYTES;
-                    const f4v own = S[it][ay];
-                    f4v left = own, right = own;                  // (only the live one is read: kx = 0 never looks right, kx = 2 never left)
-                    if (kx <= 1) left = *reinterpret_cast<const f4v*>(rp + coff[0]);
-                    if (kx >= 1) right = *reinterpret_cast<const f4v*>(rp + coff[2]);
-#pragma unroll
-                    for (int bx = 0; bx < 2; ++bx) {
-                        const int ux = bx + kx, c = ux >> 1;
-                        const f4v va = c == 0 ? left : own, vb = c == 0 ? own : right;
-                        f4v o;                                    // the first column group starts out
-                        if constexpr (kx != 0) o = out[it][ay][bx];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if constexpr (kx == 0) o[e] = fmaf(lx[ux], vb[e], hx[ux] * va[e]);
-                            else o[e] = fmaf(lx[ux], vb[e], fmaf(hx[ux], va[e], o[e]));
-                        asm volatile("" : "+v"(o));               // (pinned like the vertical sums)
-                        out[it][ay][bx] = o;
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            };
-#pragma unroll
-            for (int it = 0; it < 8; ++it) *reinterpret_cast<f4v*>(other + (ib + it) * ROW_BYTES + coff[1]) = S[it][0];
+            tapsum_put<8, 0, ROW_BYTES>(S, other, ib, coff[1]);
             wait_lds_reads();                                     // my ay = 0 sums are in `other` (and my reads of this step's products have returned)
             __builtin_amdgcn_s_barrier();                         // everybody's are; everybody has left the vertical stage: this step's chunk is free
             asm volatile("" ::: "memory");
-#pragma unroll
-            for (int it = 0; it < 8; ++it) *reinterpret_cast<f4v*>(chunk + (ib + it) * ROW_BYTES + coff[1]) = S[it][1];
+            tapsum_put<8, 1, ROW_BYTES>(S, chunk, ib, coff[1]);
             __builtin_amdgcn_sched_barrier(0);
-            horizontal.template operator()<0>(other);
+            tapsum_horizontal<8, kx, 0, ROW_BYTES>(out, S, other, ib, coff[0], coff[2], hx, lx);
             wait_lds_reads();                                     // my ay = 1 sums are in the chunk, my reads of `other` have returned
             __builtin_amdgcn_s_barrier();                         // everybody's: the next step's products may overwrite `other`
             asm volatile("" ::: "memory");
-            horizontal.template operator()<1>(chunk);             // (the step after next overwrites this chunk, behind the next step's barrier)
+            tapsum_horizontal<8, kx, 1, ROW_BYTES>(out, S, chunk, ib, coff[0], coff[2], hx, lx);   // (the step after next overwrites this chunk, behind the next step's barrier)
         }
     };
     tap.template operator()<0>(); tap.template operator()<1>(); tap.template operator()<2>();

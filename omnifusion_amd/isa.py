@@ -12,7 +12,7 @@ found by measurement on MI355X:
     prevents it is a compiler flag in build.py — one object built without it, or a toolchain
     that ignores it, would re-open the hazard silently.  So the DISASSEMBLY is checked.
  2. the kernels that count their own `s_waitcnt vmcnt(N)` by hand (`e2p_box_kernel`,
-    `p2e_lds_kernel`, `p2e_walk_kernel`, `up2_taps_fused_kernel`) must not spill: a scratch store/load in the middle of
+    `p2e_lds_kernel`, `p2e_walk_kernel`, `up2_taps_fused_kernel`, `up2_heads_taps_kernel`) must not spill: a scratch store/load in the middle of
     the LDS-DMA pipeline shifts every hand-counted wait.  So `.private_segment_fixed_size` and
     the spill counts of those kernels are checked to be 0.
 

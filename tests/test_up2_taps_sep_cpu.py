@@ -1,5 +1,6 @@
-"""The separable tap sum of up2_taps_fused_kernel (csrc/omni_conv_up2_taps.hip), restated in float64 with the kernel's own weight tables, clamps
-and tap order, against the operator `conv2d(interpolate(x, 2, bilinear), w, pad 1)`.  This is the specification the kernel is read against:
+"""The separable tap sum of csrc/omni_up2_tapsum.h — the one text that up2_taps_fused_kernel (csrc/omni_conv_up2_taps.hip) and up2_heads_taps_kernel
+(csrc/omni_conv_up2_heads_taps.hip) both run — restated in float64 with the header's own weight tables, clamps and tap order, against the operator
+`conv2d(interpolate(x, 2, bilinear), w, pad 1)`.  This is the specification the header is read against:
 
   vertical stage, per tap (ky, kx), on the thread's own column:
       S_kx[i][ay][j] (+)= hy[ay + ky] * Y[clamp(i - 1 + r)][j] + ly[ay + ky] * Y[clamp(i + r)][j],            r = (ay + ky) >> 1
