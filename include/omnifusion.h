@@ -710,6 +710,38 @@ int omni_batchnorm_bwd_f32(const float* g, const float* x, const float* y, const
                            omni_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * The same operator in training mode with its statistics over the rows of ALL ranks of a group (csrc/omni_batchnorm.hip):
+ * the two calls above, cut at their finishes into four.  The library moves no data between ranks: the caller gathers the records.  The
+ * same rules: fp32 contiguous NHWC, C a multiple of 4, nothing allocated, nothing synchronised, nothing read back, no atomics, fixed
+ * summation orders, every rejection before a launch.  `rows` is THIS rank's row count, >= 1 (only the group's total has to be >= 2; with
+ * world == 1 a single row is rejected).  `workspace`: omni_batchnorm_workspace_bytes(rows, C) bytes.
+ * A rank's exchange record `sums` is 2 C + 1 doubles, 8-byte aligned: [0][c] and [1][c] the two sums of channel c over the rank's rows (the
+ * slab plan and summation order of the calls above, left in double), [2 C] = rows.  `all_sums` is [world][2 C + 1]: the records of the
+ * ranks in rank order, 1 <= world <= 64 (else INVALID).  Totals over ranks are added in ascending rank order in double, so every rank
+ * computes the same bits from the same table.
+ * omni_syncbn_stats_f32: the record of (sum x, sum x^2).
+ * omni_syncbn_fwd_apply_f32: n = sum_r rows_r, mean = sum x / n, var = max(sum x^2 / n - mean^2, 0) (a NaN stays a NaN), saved = (float)(mean,
+ * 1 / sqrt(var + eps)), the running buffers (both or neither) move with var . n / (n - 1) as in omni_batchnorm_fwd_f32; then the apply pass.
+ * omni_syncbn_bwd_reduce_f32: the record of (sum dZ, sum dZ . xhat), dZ = g . [y > 0] with act RELU (y required), g with act NONE.  dgamma /
+ * dbeta (each may be NULL) get THIS rank's sums rounded to fp32: parameter gradients stay local, the gradient exchange adds them.  dz
+ * non-NULL: dZ is written (act RELU only; with act NONE dZ is g itself and dz must be NULL).
+ * omni_syncbn_bwd_apply_f32: per channel the total of each sum over the ranks, rounded once to fp32; k = (float)((double)total / n);
+ * dx = gamma . invstd . ((dZ - k1) - xhat . k2).  y non-NULL with act RELU: the first argument is g and dZ is selected again; y NULL (or act
+ * NONE): the first argument is dZ.  dres non-NULL (act RELU and y required): dZ is written there.  dx or dres may be NULL, not both; without
+ * dx, x, saved and all_sums are not read.
+ * With world == 1 and their own record the four calls write bit for bit the y, saved, running buffers, dx, dres, dgamma and dbeta of
+ * omni_batchnorm_fwd_f32 / omni_batchnorm_bwd_f32 (training) on the same tensors. */
+int omni_syncbn_stats_f32(const float* x, double* sums, long long rows, int C, void* workspace, size_t ws_bytes, omni_stream_t stream);
+int omni_syncbn_fwd_apply_f32(const float* x, const float* res, const float* gamma, const float* beta, const double* all_sums, int world,
+                              float* running_mean, float* running_var, float* y, float* saved, long long rows, int C, double momentum,
+                              double eps, int act, omni_stream_t stream);
+int omni_syncbn_bwd_reduce_f32(const float* g, const float* x, const float* y, const float* saved, float* dz, double* sums, float* dgamma,
+                               float* dbeta, long long rows, int C, int act, void* workspace, size_t ws_bytes, omni_stream_t stream);
+int omni_syncbn_bwd_apply_f32(const float* g_or_dz, const float* y, const float* x, const float* gamma, const float* saved,
+                              const double* all_sums, int world, float* dx, float* dres, long long rows, int C, int act,
+                              omni_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * The transformer's training operators beyond its linear layers (csrc/omni_transformer_bwd.hip): layer normalisation over
  * the last axis with its backward, the backward of omni_attention_f32, the exact GELU with its backward.  fp32, contiguous.  Nothing is
  * allocated, nothing synchronises, nothing is read back; no atomics, every sum in a fixed order that depends on the shapes alone: the same

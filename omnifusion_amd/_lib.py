@@ -172,6 +172,10 @@ omni_conv2d_split_weights_f16x1 i ppiip
 omni_batchnorm_workspace_bytes z li
 omni_batchnorm_fwd_f32 i p8liiddipzp
 omni_batchnorm_bwd_f32 i p9li3pzp
+omni_syncbn_stats_f32 i pplipzp
+omni_syncbn_fwd_apply_f32 i p5ip4liddip
+omni_syncbn_bwd_reduce_f32 i p8liipzp
+omni_syncbn_bwd_apply_f32 i p6ippliip
 omni_layernorm_bwd_workspace_bytes z li
 omni_layernorm_fwd_f32 i p4lifp
 omni_layernorm_bwd_f32 i p6lifpzp

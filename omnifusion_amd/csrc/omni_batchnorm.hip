@@ -15,7 +15,12 @@
 // stopped at offset QW (lanes that differ in a bit >= QW hold the same quad), the four waves as (w0 + w1) + (w2 + w3): block_sum's order,
 // spelled out here because block_sum reduces all 64 lanes.  The finish kernels add a channel's slab partials by the column finish of
 // omni_partials.h.  No atomics, nothing allocated, nothing synchronised, nothing read back: the same bits on every run.
+//
+// Statistics across ranks (omni_syncbn_*): the same passes, cut at the two finishes.  A rank leaves its two sums per channel
+// in double with its row count (the exchange record, 2 C + 1 doubles); the caller gathers the records of all ranks; the forward's finish and
+// the backward apply's prologue add them in rank order.  With one record the four calls give the bits of the two calls above.
 #include <cmath>
+#include <cstdint>
 
 #include "omni_internal.h"
 #include "omni_partials.h"
@@ -91,8 +96,23 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
     bn_block_partials(s, ss, part, C, q, active, qw);
 }
 
-// Block c: channel c.  n = rows.  saved[0][c] = mean, saved[1][c] = 1 / sqrt(var_biased + eps), both computed in double and rounded once;
-// the running buffers (both or neither) move by the momentum, the variance unbiased.
+// Channel c from its two sums over n values: saved[0][c] = mean, saved[1][c] = 1 / sqrt(var_biased + eps), both computed in double and rounded
+// once; the running buffers (both or neither) move by the momentum, the variance unbiased.
+__device__ __forceinline__ void bn_finish_channel(double sum, double sumsq, double n, double eps, double momentum, int c, int C,
+                                                  float* __restrict__ saved, float* __restrict__ running_mean, float* __restrict__ running_var)
+{
+    const double mean = sum / n;
+    double var = sumsq / n - mean * mean;
+    var = var < 0.0 ? 0.0 : var;                                 // (a NaN stays a NaN)
+    saved[c] = (float)mean;
+    saved[C + c] = (float)(1.0 / sqrt(var + eps));
+    if (running_mean) {
+        running_mean[c] = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * mean);
+        running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * (var * (n / (n - 1.0))));
+    }
+}
+
+// Block c: channel c, n = rows.
 __global__ __launch_bounds__(256) void bn_stats_finish_kernel(const double* __restrict__ part, int nslab, int C, double n, double eps,
                                                               double momentum, float* __restrict__ saved, float* __restrict__ running_mean,
                                                               float* __restrict__ running_var)
@@ -101,17 +121,47 @@ __global__ __launch_bounds__(256) void bn_stats_finish_kernel(const double* __re
     const int t = threadIdx.x, c = blockIdx.x;
     double v[2];
     column_sums<2>(part + c, nslab, (size_t)2 * C, C, v, red);
+    if (t == 0) bn_finish_channel(v[0], v[1], n, eps, momentum, c, C, saved, running_mean, running_var);
+}
+
+// Statistics across ranks.  A rank's exchange record is 2 C + 1 doubles: the two sums of every channel over its own rows —
+// the column finish of its slab partials, left in double — and its row count.  Block c: channel c; dbeta / dgamma (backward; may be null)
+// get the rank's own sums rounded once.
+__global__ __launch_bounds__(256) void bn_record_finish_kernel(const double* __restrict__ part, int nslab, int C, double n,
+                                                               double* __restrict__ rec, float* __restrict__ dgamma, float* __restrict__ dbeta)
+{
+    __shared__ double red[2][4];
+    const int t = threadIdx.x, c = blockIdx.x;
+    double v[2];
+    column_sums<2>(part + c, nslab, (size_t)2 * C, C, v, red);
     if (t == 0) {
-        const double mean = v[0] / n;
-        double var = v[1] / n - mean * mean;
-        var = var < 0.0 ? 0.0 : var;                             // (a NaN stays a NaN)
-        saved[c] = (float)mean;
-        saved[C + c] = (float)(1.0 / sqrt(var + eps));
-        if (running_mean) {
-            running_mean[c] = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * mean);
-            running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * (var * (n / (n - 1.0))));
-        }
+        rec[c] = v[0];
+        rec[C + c] = v[1];
+        if (c == 0) rec[2 * C] = n;
+        if (dbeta) dbeta[c] = (float)v[0];
+        if (dgamma) dgamma[c] = (float)v[1];
     }
+}
+
+// Slot i of the gathered records all[world][2 C + 1], added in ascending rank order in double: every rank adds the same numbers in the same
+// order, so all of them hold the same bits.  world == 1: the record's own value.
+__device__ __forceinline__ double bn_rank_total(const double* __restrict__ all, int world, int C, int i)
+{
+    double v = all[i];
+    for (int r = 1; r < world; ++r) v += all[(size_t)r * (2 * C + 1) + i];
+    return v;
+}
+
+// Thread c: channel c from the totals over the ranks, n = the total of their row counts.
+__global__ __launch_bounds__(256) void bn_sync_stats_finish_kernel(const double* __restrict__ all, int world, int C, double eps, double momentum,
+                                                                   float* __restrict__ saved, float* __restrict__ running_mean,
+                                                                   float* __restrict__ running_var)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    const double n = bn_rank_total(all, world, C, 2 * C);
+    bn_finish_channel(bn_rank_total(all, world, C, c), bn_rank_total(all, world, C, C + c), n, eps, momentum, c, C, saved, running_mean,
+                      running_var);
 }
 
 // eval mode: the saved pair from the running buffers
@@ -255,6 +305,58 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     }
 }
 
+// The apply loop of bn_bwd_apply_kernel in training mode for a caller that holds k1 and k2 (statistics across ranks; that kernel keeps its
+// own copy: its machine code is pinned).  dx = gamma . invstd . ((dZ - k1) - xhat . k2), a = gamma . invstd; dres != null: dZ is written too;
+// dx may be null then.
+__device__ __forceinline__ void bn_bwd_apply_rows(const float* __restrict__ g, const float* __restrict__ y, const float* __restrict__ x,
+                                                  float* __restrict__ dx, float* __restrict__ dres, int rows, int C, int q, int qshift, int slab,
+                                                  f4v mean, f4v inv, f4v a, f4v k1, f4v k2)
+{
+    const int t = threadIdx.x, rl = 256 >> qshift;
+    const int r0 = blockIdx.x * slab, rend = min(rows - r0, slab) + r0;
+#pragma unroll 4
+    for (int r = r0 + (t >> qshift); r < rend; r += rl) {
+        const size_t o = (size_t)r * C + 4 * q;
+        const f4v d = bn_dz(g, y, o);
+        if (dres) *(f4v*)(dres + o) = d;
+        if (dx) {
+            const f4v v = *(const f4v*)(x + o);
+            f4v out;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float xh = (v[e] - mean[e]) * inv[e];
+                out[e] = a[e] * fmaf(-xh, k2[e], d[e] - k1[e]);
+            }
+            *(f4v*)(dx + o) = out;
+        }
+    }
+}
+
+// Statistics across ranks: the prologue adds the ranks' records of the thread's four channels (bn_rank_total), rounds each total once to
+// fp32 — the pair the one-device backward keeps in its workspace — and divides by n = the total of the row counts.
+__global__ __launch_bounds__(256) void bn_sync_bwd_apply_kernel(const float* __restrict__ g, const float* __restrict__ y, const float* __restrict__ x,
+                                                                const float* __restrict__ gamma, const float* __restrict__ saved,
+                                                                const double* __restrict__ all, int world, float* __restrict__ dx,
+                                                                float* __restrict__ dres, int rows, int C, int qw, int qshift, int slab)
+{
+    const int q = blockIdx.y * qw + (threadIdx.x & (qw - 1));
+    if (4 * q >= C) return;
+    f4v mean = {0.0f, 0.0f, 0.0f, 0.0f}, inv = mean, a = mean, k1 = mean, k2 = mean;
+    if (dx) {
+        mean = ld4(saved, q, 0.0f);
+        inv = ld4(saved + C, q, 0.0f);
+        a = inv * ld4(gamma, q, 1.0f);
+        const double n = bn_rank_total(all, world, C, 2 * C);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float sb = (float)bn_rank_total(all, world, C, 4 * q + e), sg = (float)bn_rank_total(all, world, C, C + 4 * q + e);
+            k1[e] = (float)((double)sb / n);
+            k2[e] = (float)((double)sg / n);
+        }
+    }
+    bn_bwd_apply_rows(g, y, x, dx, dres, rows, C, q, qshift, slab, mean, inv, a, k1, k2);
+}
+
 int bn_check_common(const char* who, long long rows, int C, int act, std::string& why, BnPlan& p)
 {
     if (act == OMNI_ACT_GELU) { why = std::string(who) + ": no GELU (the operator keeps no pre-activation for its backward)"; return OMNI_ERR_UNSUPPORTED; }
@@ -348,5 +450,102 @@ extern "C" int omni_batchnorm_bwd_f32(const float* g, const float* x, const floa
                            (int)rows, C, p.qw, p.qshift, p.slab, (double)rows);
         OMNI_HIP(hipGetLastError());
     }
+    return OMNI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- statistics across ranks
+namespace {
+
+bool bn_misaligned8(const void* p) { return ((uintptr_t)p & 7) != 0; }
+
+}  // namespace
+
+extern "C" int omni_syncbn_stats_f32(const float* x, double* sums, long long rows, int C, void* workspace, size_t ws_bytes, omni_stream_t stream)
+{
+    BnPlan p; std::string why;
+    const int rc = bn_check_common("omni_syncbn_stats", rows, C, OMNI_ACT_NONE, why, p);
+    if (rc != OMNI_OK) OMNI_FAIL(rc, why);
+    if (!x || !sums) OMNI_FAIL(OMNI_ERR_INVALID, "omni_syncbn_stats: null pointer");
+    if (bn_misaligned8(sums)) OMNI_FAIL(OMNI_ERR_INVALID, "omni_syncbn_stats: the record must be 8-byte aligned");
+    if (!workspace || ws_bytes < bn_ws_bytes(p, C)) OMNI_FAIL(OMNI_ERR_INVALID, "omni_syncbn_stats: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    double* part = (double*)workspace;
+    hipLaunchKernelGGL(bn_stats_kernel, dim3(p.nslab, p.ncol), dim3(256), 0, s, x, part, (int)rows, C, p.qw, p.qshift, p.slab);
+    OMNI_HIP(hipGetLastError());
+    hipLaunchKernelGGL(bn_record_finish_kernel, dim3(C), dim3(256), 0, s, (const double*)part, p.nslab, C, (double)rows, sums, (float*)nullptr,
+                       (float*)nullptr);
+    OMNI_HIP(hipGetLastError());
+    return OMNI_OK;
+}
+
+extern "C" int omni_syncbn_fwd_apply_f32(const float* x, const float* res, const float* gamma, const float* beta, const double* all_sums,
+                                         int world, float* running_mean, float* running_var, float* y, float* saved, long long rows, int C,
+                                         double momentum, double eps, int act, omni_stream_t stream)
+{
+    BnPlan p; std::string why;
+    const int rc = bn_check_common("omni_syncbn_fwd_apply", rows, C, act, why, p);
+    if (rc != OMNI_OK) OMNI_FAIL(rc, why);
+    if (!x || !y || !saved || !all_sums) OMNI_FAIL(OMNI_ERR_INVALID, "omni_syncbn_fwd_apply: null pointer");
+    if (world < 1 || world > 64) OMNI_FAIL(OMNI_ERR_INVALID, "omni_syncbn_fwd_apply: world must lie in [1, 64]");
+    if (bn_misaligned8(all_sums)) OMNI_FAIL(OMNI_ERR_INVALID, "omni_syncbn_fwd_apply: the records must be 8-byte aligned");
+    if (!(eps > 0.0) || !std::isfinite(eps)) OMNI_FAIL(OMNI_ERR_INVALID, "omni_syncbn_fwd_apply: eps must be positive and finite");
+    if (!(momentum >= 0.0 && momentum <= 1.0)) OMNI_FAIL(OMNI_ERR_INVALID, "omni_syncbn_fwd_apply: momentum must lie in [0, 1]");
+    if ((running_mean == nullptr) != (running_var == nullptr))
+        OMNI_FAIL(OMNI_ERR_INVALID, "omni_syncbn_fwd_apply: running_mean and running_var come together");
+    if (world == 1 && rows == 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_syncbn_fwd_apply: training mode expects more than 1 value per channel");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(bn_sync_stats_finish_kernel, dim3((C + 255) / 256), dim3(256), 0, s, all_sums, world, C, eps, momentum, saved, running_mean,
+                       running_var);
+    OMNI_HIP(hipGetLastError());
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(p.nslab, p.ncol), dim3(256), 0, s, x, res, gamma, beta, (const float*)saved, y, (int)rows, C, p.qw,
+                       p.qshift, p.slab, act == OMNI_ACT_RELU ? 1 : 0);
+    OMNI_HIP(hipGetLastError());
+    return OMNI_OK;
+}
+
+extern "C" int omni_syncbn_bwd_reduce_f32(const float* g, const float* x, const float* y, const float* saved, float* dz, double* sums,
+                                          float* dgamma, float* dbeta, long long rows, int C, int act, void* workspace, size_t ws_bytes,
+                                          omni_stream_t stream)
+{
+    BnPlan p; std::string why;
+    const int rc = bn_check_common("omni_syncbn_bwd_reduce", rows, C, act, why, p);
+    if (rc != OMNI_OK) OMNI_FAIL(rc, why);
+    const bool relu = act == OMNI_ACT_RELU;
+    if (!g || !x || !saved || !sums) OMNI_FAIL(OMNI_ERR_INVALID, "omni_syncbn_bwd_reduce: null pointer");
+    if (bn_misaligned8(sums)) OMNI_FAIL(OMNI_ERR_INVALID, "omni_syncbn_bwd_reduce: the record must be 8-byte aligned");
+    if (relu && !y) OMNI_FAIL(OMNI_ERR_INVALID, "omni_syncbn_bwd_reduce: ReLU needs the forward's output");
+    if (!relu && dz) OMNI_FAIL(OMNI_ERR_INVALID, "omni_syncbn_bwd_reduce: without an activation dZ is g itself (pass dz = NULL)");
+    if (!workspace || ws_bytes < bn_ws_bytes(p, C)) OMNI_FAIL(OMNI_ERR_INVALID, "omni_syncbn_bwd_reduce: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    double* part = (double*)workspace;
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(p.nslab, p.ncol), dim3(256), 0, s, g, relu ? y : (const float*)nullptr, x, saved, dz, part,
+                       (int)rows, C, p.qw, p.qshift, p.slab);
+    OMNI_HIP(hipGetLastError());
+    hipLaunchKernelGGL(bn_record_finish_kernel, dim3(C), dim3(256), 0, s, (const double*)part, p.nslab, C, (double)rows, sums, dgamma, dbeta);
+    OMNI_HIP(hipGetLastError());
+    return OMNI_OK;
+}
+
+extern "C" int omni_syncbn_bwd_apply_f32(const float* g_or_dz, const float* y, const float* x, const float* gamma, const float* saved,
+                                         const double* all_sums, int world, float* dx, float* dres, long long rows, int C, int act,
+                                         omni_stream_t stream)
+{
+    BnPlan p; std::string why;
+    const int rc = bn_check_common("omni_syncbn_bwd_apply", rows, C, act, why, p);
+    if (rc != OMNI_OK) OMNI_FAIL(rc, why);
+    const bool relu = act == OMNI_ACT_RELU;
+    if (!g_or_dz) OMNI_FAIL(OMNI_ERR_INVALID, "omni_syncbn_bwd_apply: null pointer");
+    if (!dx && !dres) OMNI_FAIL(OMNI_ERR_INVALID, "omni_syncbn_bwd_apply: no gradient requested");
+    if (dres && !(relu && y))
+        OMNI_FAIL(OMNI_ERR_INVALID, "omni_syncbn_bwd_apply: dres is dZ = g . [y > 0]: it needs act RELU and the forward's output (else the "
+                                    "residual's gradient is the first argument itself)");
+    if (dx && (!x || !saved || !all_sums)) OMNI_FAIL(OMNI_ERR_INVALID, "omni_syncbn_bwd_apply: null pointer (x, saved and the records, for dx)");
+    if (dx && (world < 1 || world > 64)) OMNI_FAIL(OMNI_ERR_INVALID, "omni_syncbn_bwd_apply: world must lie in [1, 64]");
+    if (dx && bn_misaligned8(all_sums)) OMNI_FAIL(OMNI_ERR_INVALID, "omni_syncbn_bwd_apply: the records must be 8-byte aligned");
+    if (dx && world == 1 && rows == 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_syncbn_bwd_apply: training mode expects more than 1 value per channel");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(bn_sync_bwd_apply_kernel, dim3(p.nslab, p.ncol), dim3(256), 0, s, g_or_dz, relu ? y : (const float*)nullptr, x, gamma, saved,
+                       all_sums, world, dx, dres, (int)rows, C, p.qw, p.qshift, p.slab);
+    OMNI_HIP(hipGetLastError());
     return OMNI_OK;
 }

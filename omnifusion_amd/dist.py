@@ -9,6 +9,10 @@ gather (`/root/reference/test.py:105-107,198`).  Every panorama is independent e
     [B/R,1,H,W] — 16.8 MB per GPU at BASELINE cfg 4, a single large message per xGMI link),
   * for the barrier / MAX-over-ranks of the timing protocol (`timed_steps`).
 
+Training is the other case: the batch normalisations of a data-parallel model take their statistics over the batches of
+all ranks.  `all_gather_records` is that exchange — one small all_gather per normalisation and direction, ON the data path — and
+`sync_gradients` adds the ranks' parameter gradients before the optimiser's step.
+
 The functions take tensors on whatever device the process group's backend serves ("nccl" = RCCL: the rank's
 GPU; "gloo": CPU), which is what lets tests/test_sharding_gloo.py drive exactly this code with world_size 2
 on a box without GPUs.
@@ -248,6 +252,65 @@ def broadcast_state_dict(state_dict, src=0):
             out[k] = flat[o:o + m].reshape(s).clone()
             o += m
     return {k: out[k] for k, _, _ in meta[0]}
+
+
+# ---------------------------------------------------------------------------------------------- training across ranks
+def _group_world(group=None):
+    """ranks of `group` (None: the default group); 1 without an initialised process group — nothing is created"""
+    return dist.get_world_size(group) if _grouped() else 1
+
+
+def _group_device(device, group=None):
+    """_coll_device for `group`: the rank's GPU where the group's backend is RCCL, else the CPU"""
+    if _grouped() and dist.get_backend(group) == "nccl":
+        return device if torch.device(device).type == "cuda" else torch.device("cuda", torch.cuda.current_device())
+    return torch.device("cpu")
+
+
+def all_gather_records(vec, group=None):
+    """The synchronised batch normalisation's exchange: `vec` [L] (a rank's float64 record of sums, ops.sync_batch_norm) -> [world, L], the
+    records of all ranks in rank order, on vec's device.  ONE all_gather_into_tensor — a gather, not an all-reduce: every rank then adds
+    the same numbers in the same order itself, so the statistics have the same bits on all ranks whatever the backend's reduction
+    algorithm.  With RCCL the collective runs on the GPU, ordered after the current stream, and nothing synchronises with the host; with
+    gloo the record travels through the CPU, which SYNCHRONISES the device twice per call (single-GPU test boxes, CPU tests).  World 1 or
+    no process group: vec itself as [1, L], no collective."""
+    if vec.dim() != 1:
+        raise ValueError(f"all_gather_records: a record is a vector (got {tuple(vec.shape)})")
+    world = _group_world(group)
+    if world == 1:
+        return vec.reshape(1, -1)
+    dev = _group_device(vec.device, group)
+    out = torch.empty(world * vec.numel(), dtype=vec.dtype, device=dev)        # the concatenated form: the one gloo takes too
+    dist.all_gather_into_tensor(out, vec.contiguous().to(dev), group=group)
+    return out.reshape(world, vec.numel()).to(vec.device)
+
+
+def sync_gradients(module_or_params, group=None, average=False):
+    """Adds the gradients of the ranks, in place: call it between loss.backward() and optimizer.step() (it replaces the gradient
+    reduction of nn.DataParallel's backward).  The gradients of all parameters that have one travel through ONE flat fp32 buffer and one
+    all_reduce(SUM), then are copied back; `average` divides by the world size.  Every rank must hold gradients for the same parameters
+    (the buffer's layout is their order).  `module_or_params`: an nn.Module or an iterable of parameters.  Returns the number of
+    gradients exchanged.  World 1 or no process group: nothing is touched."""
+    params = module_or_params.parameters() if isinstance(module_or_params, torch.nn.Module) else module_or_params
+    grads = [p.grad for p in params if p.grad is not None]
+    world = _group_world(group)
+    if world == 1 or not grads:
+        return len(grads)
+    for g in grads:
+        if g.dtype != torch.float32:
+            raise ValueError(f"sync_gradients: fp32 gradients only (got {g.dtype})")
+    dev = _group_device(grads[0].device, group)
+    flat = torch.cat([g.reshape(-1) for g in grads]).to(dev)
+    dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
+    if average:
+        flat /= world
+    flat = flat.to(grads[0].device)
+    o = 0
+    with torch.no_grad():
+        for g in grads:
+            g.copy_(flat[o:o + g.numel()].view_as(g))
+            o += g.numel()
+    return len(grads)
 
 
 # ---------------------------------------------------------------------------------------------- launcher

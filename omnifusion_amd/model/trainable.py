@@ -29,9 +29,13 @@ The stem, the heads, the point convolutions, the normalisations, attention, GELU
 so are the parameters, the saved activations (fp32) and the state dict.  Anything else raises ValueError ("fp32": training has no fp32
 product path); the environment's OMNI_NET_PRECISION is not read here.  `net.precision` reports the mode.
 
-The iterative model is model/trainable_iterative.py, a subclass.  Not built: DataParallel /
-SyncBatchNorm / convert_model, fp16 storage of activations or weights, an image gradient, a hand-written optimiser (torch.optim.AdamW steps the parameters), capture of a
-whole step in a graph.  fp32 CUDA input, one device.
+Several GPUs: one process per GPU, `omnifusion_amd.sync_batchnorm.convert_model(net)` — every batch normalisation but
+those of `SYNCBN_REPLICATED` then takes its statistics over the batches of all ranks — and `omnifusion_amd.dist.sync_gradients(net)`
+before the optimiser's step.
+
+The iterative model is model/trainable_iterative.py, a subclass.  Not built: DataParallel (threads in one
+process), fp16 storage of activations or weights, an image gradient, a hand-written optimiser (torch.optim.AdamW steps the parameters),
+capture of a whole step in a graph.  fp32 CUDA input, one device per process.
 """
 import ctypes
 
@@ -125,6 +129,9 @@ def _layer(cin, cout, blocks, stride):
 
 class spherical_fusion(nn.Module):
     _DOWN = "down"                                                             # the token projection's name (trainable_iterative.py: "down1")
+    # sync_batchnorm.convert_model's default `skip`: the normalisations whose input is the same on every rank (mlp_points is fed the patch
+    # centres alone), so that their local statistics are the group's and a collective would buy nothing
+    SYNCBN_REPLICATED = ("mlp_points",)
 
     def __init__(self, nrows=4, npatches=18, patch_size=(128, 128), fov=(80, 80), *, precision="f16x3"):
         super().__init__()

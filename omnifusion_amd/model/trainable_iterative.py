@@ -23,8 +23,12 @@ confidence, pers2equi without (the reference's default).  `.eval()` runs the sam
 
 All six 1x1 convolutions of the point MLPs are ops.PointConv2d (csrc/omni_point_conv.hip): fp32 FMAs, a deterministic weight gradient.
 
-Not built: sharing conv1 .. layer1 between the passes, DataParallel / SyncBatchNorm, fp16 storage, an image gradient, capture of
-a whole step in a graph, `iter` as a tensor.  fp32 CUDA input, one device.
+Several GPUs: `omnifusion_amd.sync_batchnorm.convert_model(net)` synchronises every batch normalisation but mlp_points1's
+(`SYNCBN_REPLICATED`: its input, the rays, is the same on every rank; mlp_points2's is not), `omnifusion_amd.dist.sync_gradients(net)` adds
+the ranks' gradients.
+
+Not built: sharing conv1 .. layer1 between the passes, DataParallel (threads in one process), fp16 storage, an image gradient,
+capture of a whole step in a graph, `iter` as a tensor.  fp32 CUDA input, one device per process.
 """
 import torch
 from torch import nn
@@ -43,6 +47,7 @@ def _point_mlp(cin):
 
 class spherical_fusion(trainable.spherical_fusion):
     _DOWN = "down1"
+    SYNCBN_REPLICATED = ("mlp_points1",)                                       # fed the unit rays alone; mlp_points2 sees rays . depth: synchronised
 
     def __init__(self, nrows=4, npatches=18, patch_size=(256, 256), fov=(80, 80), *, precision="f16x3"):
         super().__init__(nrows, npatches, patch_size, fov, precision=precision)

@@ -31,7 +31,20 @@ y = act(batch_norm(x) + res) (csrc/omni_batchnorm.hip) on x [M,C
 `training=False` (the usual way to fine-tune).  Gradients w.r.t. x, weight, bias and res; the same rules: fixed summation order (in
 double), no atomics, no host synchronisation, only what autograd asks for, channels-last tensors without a copy.  The per-channel
 statistics of a BatchNorm3d over [B,C,P,P,N] are those of this operator over [M = B.N, C, P, P].  Not covered: momentum=None (the
-cumulative average reads a counter on the host), statistics across GPUs, fp16 storage, double backward.
+cumulative average reads a counter on the host), fp16 storage, double backward.
+
+Statistics across the ranks of a process group (csrc/omni_batchnorm.hip omni_syncbn_*) — data-parallel training, one
+process per GPU:
+
+    y = sync_batch_norm(x, weight=None, bias=None, running_mean=None, running_var=None, *, res=None, training=True, momentum=0.1,
+                        eps=1e-5, act="none" | "relu", group=None)
+    layer = SyncBatchNorm2d(64, act="relu", process_group=None)           # an ops.BatchNorm2d: same parameters, buffers, state dict
+    model, names = convert_sync_batchnorm(model, process_group=None, skip=())   # swaps every ops.BatchNorm2d in place
+
+batch_norm over the rows of ALL ranks: each rank sums its own rows in double, one dist.all_gather_records moves the records (2 C + 1
+doubles per rank), every rank adds them in rank order — the same bits everywhere — and applies; the backward exchanges its two sums the
+same way.  weight and bias receive THIS rank's gradient (dist.sync_gradients adds the ranks').  All ranks must call the operator in the
+same order and ask for the same gradients.  Eval mode, world 1 or no process group: batch_norm itself.
 
 The transformer between layer4 and the decoder (csrc/omni_transformer_bwd.hip), under the reference's state-dict names:
 
@@ -276,8 +289,9 @@ class Conv2d(torch.nn.Conv2d):
 
 
 # ------------------------------------------------------------------------------------------------ batch normalisation
-def _check_bn_args(x, weight, bias, running_mean, running_var, res, training, momentum, eps, act):
-    """Every rejection of batch_norm, raised before anything is launched."""
+def _check_bn_args(x, weight, bias, running_mean, running_var, res, training, momentum, eps, act, single_ok=False):
+    """Every rejection of batch_norm, raised before anything is launched.  single_ok: one value per channel is legal in training mode
+    (sync_batch_norm: the other ranks hold more)."""
     _check_f32_dev((("x", x), ("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var), ("res", res)),
                    optional=("weight", "bias", "running_mean", "running_var", "res"))
     if act not in ACTS:
@@ -306,7 +320,7 @@ def _check_bn_args(x, weight, bias, running_mean, running_var, res, training, mo
         raise ValueError(f"momentum must be a number in [0, 1] (got {momentum!r})")
     if not isinstance(eps, (int, float)) or not 0.0 < eps < float("inf"):
         raise ValueError(f"eps must be a positive finite number (got {eps!r})")
-    if training and M * H * W == 1:
+    if training and M * H * W == 1 and not single_ok:
         raise ValueError(f"Expected more than 1 value per channel when training (got x of shape {tuple(x.shape)})")
     if not training and running_mean is None:
         raise ValueError("training=False needs running_mean and running_var")
@@ -390,6 +404,124 @@ class BatchNorm2d(torch.nn.BatchNorm2d):
             self.num_batches_tracked.add_(1)                                   # on the device; nothing reads it here
         return batch_norm(x, self.weight, self.bias, self.running_mean, self.running_var, res=res, training=batch_stats,
                           momentum=self.momentum, eps=self.eps, act=self.act)
+
+
+# ------------------------------------------------------------------------------------------------ statistics across ranks
+SYNCBN_MAX_WORLD = 64
+
+
+def _syncbn_world(group):
+    """ranks that share the statistics: those of `group` (None: the default group), 1 without an initialised process group"""
+    from . import dist as _dist
+    return _dist._group_world(group)
+
+
+def _check_syncbn_records(who, table, world, C, dev):
+    if tuple(table.shape) != (world, 2 * C + 1) or table.dtype != torch.float64 or table.device != dev or not table.is_contiguous():
+        raise ValueError(f"{who}: the gathered records must be a contiguous float64 [{world}, {2 * C + 1}] tensor on {dev} "
+                         f"(got {table.dtype} {tuple(table.shape)} on {table.device})")
+
+
+class _SyncBatchNorm(torch.autograd.Function):
+    """Training mode, world > 1.  forward: stats -> gather -> apply; backward: reduce -> gather -> apply."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, res, momentum, eps, act, group, world):
+        from . import dist as _dist
+        lib = _lib.load()
+        xn, resn = _nhwc(x), _nhwc(res)
+        w = weight.contiguous() if weight is not None else None
+        b = bias.contiguous() if bias is not None else None
+        M, H, W, C = xn.shape
+        rows, dev = M * H * W, xn.device
+        y = _empty((M, H, W, C), dtype=torch.float32, device=dev)
+        saved = _empty((2, C), dtype=torch.float32, device=dev)
+        rec = _empty((2 * C + 1,), dtype=torch.float64, device=dev)
+        ws, nbytes = _bn_workspace(lib, rows, C, dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.omni_syncbn_stats_f32(_p(xn), _p(rec), rows, C, _p(ws), nbytes, _lib.stream_of(xn)), "sync_batch_norm_stats")
+            table = _dist.all_gather_records(rec, group)
+            _check_syncbn_records("sync_batch_norm", table, world, C, dev)
+            _lib.check(lib.omni_syncbn_fwd_apply_f32(_p(xn), _p(resn), _p(w), _p(b), _p(table), world, _p(running_mean), _p(running_var), _p(y),
+                                                     _p(saved), rows, C, float(momentum), float(eps), ACTS[act], _lib.stream_of(xn)),
+                       "sync_batch_norm_apply")
+        ctx.conf = (act, group, world)
+        ctx.save_for_backward(xn, w, saved, y if act == "relu" else None)
+        return _nchw(y)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        from . import dist as _dist
+        lib = _lib.load()
+        xn, w, saved, y = ctx.saved_tensors
+        act, group, world = ctx.conf
+        need_x, need_w, need_b, _, _, need_res = ctx.needs_input_grad[:6]
+        relu = act == "relu"
+        g = _nhwc(grad_out.to(torch.float32))
+        M, H, W, C = xn.shape
+        rows, dev = M * H * W, xn.device
+        dx = _new((M, H, W, C), dev) if need_x else None
+        dres = _new((M, H, W, C), dev) if need_res and relu else None
+        dgamma, dbeta = _new((C,), dev) if need_w else None, _new((C,), dev) if need_b else None
+        with torch.cuda.device(dev):
+            stream = _lib.stream_of(xn)
+            dz_written = False
+            table = None
+            if need_x or need_w or need_b:
+                rec = _empty((2 * C + 1,), dtype=torch.float64, device=dev)
+                ws, nbytes = _bn_workspace(lib, rows, C, dev)
+                dz_written = dres is not None                                  # DESIGN §20: the reduce pass writes dZ only where the residual wants it
+                _lib.check(lib.omni_syncbn_bwd_reduce_f32(_p(g), _p(xn), _p(y), _p(saved), _p(dres), _p(rec), _p(dgamma), _p(dbeta), rows, C,
+                                                          ACTS[act], _p(ws), nbytes, stream), "sync_batch_norm_bwd_reduce")
+                if need_x:                                                     # the one collective of the backward: exactly when x needs a gradient
+                    table = _dist.all_gather_records(rec, group)
+                    _check_syncbn_records("sync_batch_norm (backward)", table, world, C, dev)
+            if dx is not None or (dres is not None and not dz_written):
+                _lib.check(lib.omni_syncbn_bwd_apply_f32(_p(dres if dz_written else g), _p(None if dz_written else y), _p(xn), _p(w), _p(saved),
+                                                         _p(table), world, _p(dx), _p(None if dz_written else dres), rows, C, ACTS[act], stream),
+                           "sync_batch_norm_bwd_apply")
+        if need_res and not relu:
+            dres = g                                                           # the residual's gradient is grad_out itself: no copy
+        return (_nchw(dx), dgamma, dbeta, None, None, _nchw(dres), None, None, None, None, None)
+
+
+def sync_batch_norm(x, weight=None, bias=None, running_mean=None, running_var=None, *, res=None, training=True, momentum=0.1, eps=1e-5,
+                    act="none", group=None):
+    """batch_norm whose training-mode statistics run over the rows of ALL ranks of `group` (None: the default process group): W ranks of b
+    items compute what one device computes on W.b items (invstd = 1 / sqrt(var + eps)).  Forward: this rank's sums of x and
+    x^2 in double -> one dist.all_gather_records -> every rank adds the records in rank order and applies; `saved` and the running
+    buffers have the same bits on all ranks.  Backward: this rank's sums of dZ and dZ.xhat -> one gather -> dx.  The gradients of weight
+    and bias are THIS rank's sums: like every other parameter's they are added by dist.sync_gradients.  The backward's collective runs
+    exactly when x needs a gradient, so ALL ranks must ask for the same gradients (and call the operator in the same order), or the
+    group hangs.  A rank may hold a single value per channel; the group's total must be more than one (not checked: the count stays on
+    the device).  Eval mode, world 1 or no initialised process group: ops.batch_norm itself, the same bits, no collective."""
+    world = _syncbn_world(group)
+    if not training or world == 1:
+        return batch_norm(x, weight, bias, running_mean, running_var, res=res, training=training, momentum=momentum, eps=eps, act=act)
+    if world > SYNCBN_MAX_WORLD:
+        raise ValueError(f"sync_batch_norm: at most {SYNCBN_MAX_WORLD} ranks share their statistics (the group has {world})")
+    _check_bn_args(x, weight, bias, running_mean, running_var, res, True, momentum, eps, act, single_ok=True)
+    return _SyncBatchNorm.apply(x, weight, bias, running_mean, running_var, res, momentum, eps, act, group, world)
+
+
+class SyncBatchNorm2d(BatchNorm2d):
+    """ops.BatchNorm2d with ops.sync_batch_norm under it: the same parameters, buffers, state dict, `act=` and forward(x, res=None).
+    `process_group=None` is the default group.  In eval mode, at world 1 and without a process group it IS ops.BatchNorm2d."""
+
+    def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True, act="none", process_group=None, **kw):
+        super().__init__(num_features, eps=eps, momentum=momentum, affine=affine, track_running_stats=track_running_stats, act=act, **kw)
+        self.process_group = process_group
+
+    def forward(self, x, res=None):
+        batch_stats = self.training or not self.track_running_stats
+        if self.training and self.track_running_stats:
+            self.num_batches_tracked.add_(1)
+        return sync_batch_norm(x, self.weight, self.bias, self.running_mean, self.running_var, res=res, training=batch_stats,
+                               momentum=self.momentum, eps=self.eps, act=self.act, group=self.process_group)
+
+    def extra_repr(self):
+        return f"{super().extra_repr()}, process_group={self.process_group}"
 
 
 # ------------------------------------------------------------------------------------------------ the transformer (DESIGN.md §21)
@@ -1116,4 +1248,45 @@ def convert(module, spatial=False, precision=None):
             if new is not None:
                 setattr(parent, cname, new)
                 names.append(f"{pname}.{cname}" if pname else cname)
+    return module, names
+
+
+def convert_sync_batchnorm(module, process_group=None, skip=()):
+    """Replaces, in place, every ops.BatchNorm2d by an ops.SyncBatchNorm2d of `process_group` (None: the default group); an
+    nn.BatchNorm2d in convert's scope goes through convert first (the module's convolutions are NOT touched here).  The new layer holds the
+    SAME Parameter and buffer objects, hooks, mode and `act`: the state dict keeps its keys, order and tensors.  `skip`: name prefixes
+    ("mlp_points" covers "mlp_points" and "mlp_points.1", not "mlp_points1") whose layers stay unsynchronised — those whose input is
+    identical on every rank.  Layers that are SyncBatchNorm2d already are left alone: a second call replaces nothing.  Returns
+    (module, [the names replaced])."""
+    if isinstance(skip, str):
+        raise ValueError(f"convert_sync_batchnorm: skip is a sequence of name prefixes, not a string (got {skip!r})")
+    skip = tuple(skip)
+    if not all(isinstance(s, str) and s for s in skip):
+        raise ValueError(f"convert_sync_batchnorm: skip holds non-empty name prefixes (got {skip!r})")
+    if not isinstance(module, torch.nn.Module):
+        raise ValueError(f"convert_sync_batchnorm: an nn.Module is expected (got {type(module).__name__})")
+
+    def skipped(name):
+        return any(name == s or name.startswith(s + ".") for s in skip)
+
+    def swapped(m):
+        if type(m) is torch.nn.BatchNorm2d and m.momentum is not None and m.num_features % 4 == 0:
+            m = _swap_class(m, BatchNorm2d)
+        if type(m) is BatchNorm2d:
+            new = _swap_class(m, SyncBatchNorm2d)
+            new.process_group = process_group
+            return new
+        return None
+
+    root = None if skipped("") else swapped(module)
+    if root is not None:
+        return root, [""]
+    names = []
+    for pname, parent in list(module.named_modules()):
+        for cname, child in list(parent.named_children()):
+            name = f"{pname}.{cname}" if pname else cname
+            new = None if skipped(name) else swapped(child)
+            if new is not None:
+                setattr(parent, cname, new)
+                names.append(name)
     return module, names
