@@ -831,6 +831,32 @@ int omni_depth_heads_bwd_f32(const float* grad_a, const float* grad_c, const flo
                              omni_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * AdamW with the gradient norm and the clip of clip_grad_norm_ over one flat arena (csrc/omni_optim.hip).  Parameters,
+ * exp_avg and exp_avg_sq are three fp32 arenas of one layout: a segment per tensor, each at a multiple of 64 floats, the padding zero and
+ * never read or written.  A chunk is 4096 elements of one segment (the last chunk of a segment is short).  Two DEVICE tables describe the
+ * work: `segments`, long long [nseg][4] = arena offset in floats, element count, address of the gradient (0: none; any 4-byte alignment,
+ * contiguous in the parameter's storage order), parameter group; `chunks`, int [nchunk][2] = segment, offset of the chunk within it.  Both
+ * 8-byte aligned; an entry that points outside [0, nseg) or past its segment's count is skipped, an arena shorter than the table says is
+ * the caller's error.  Nothing is allocated, nothing synchronises, nothing is read back; no atomics, every sum in a fixed order: the same
+ * bits on every run, whatever the gradients' alignment.  The three calls can be captured; what changes between steps is in device memory.
+ * omni_adamw_grad_sqnorm_f32: partials[c] = the sum of g . g over chunk c in double, 0 for a segment without a gradient.
+ * omni_adamw_prepare_f32 (one block): adds the partials in the order of omni_partials.h, rounds once to fp32 and takes the square root;
+ * writes `record`, float [4 + 8 . ngroups]: [0] that norm, [1] clip = min(1, max_norm / (norm + 1e-6)) in fp32 (1 where max_norm < 0: no
+ * clipping), [2] 1 where the norm is inf or NaN, [3] 1 where this step is skipped (skip_nonfinite and [2]); then per group, from
+ * `groups` = double [ngroups][5] (lr, beta1, beta2, eps, weight_decay) in DEVICE memory: 1 - lr . wd, lr / (1 - beta1^t), sqrt(1 - beta2^t),
+ * eps, beta2, 1 - beta1, 1 - beta2, 0, each computed in double and rounded once.  `counters`, long long [2]: a skipped step adds 1 to
+ * counters[1]; any other adds 1 to the step count t = counters[0] first.  1 <= ngroups <= 256.
+ * omni_adamw_apply_f32: per element of every segment that has a gradient, unless record[3] is set, in fp32:
+ *     g' = g . clip;  p = p . (1 - lr . wd);  m = fma(g' - m, 1 - beta1, m);  v = fma((1 - beta2) . g', g', v . beta2);
+ *     p = fma(-lr / bc1, m / (sqrt(v) / sqrt(bc2) + eps), p)
+ * A skipped step or a segment without a gradient leaves p, m, v untouched; the gradient is never written.  Arenas 16-byte aligned. */
+int omni_adamw_grad_sqnorm_f32(const void* segments, int nseg, const int* chunks, int nchunk, double* partials, omni_stream_t stream);
+int omni_adamw_prepare_f32(const double* partials, int nchunk, const double* groups, int ngroups, double max_norm, int skip_nonfinite,
+                           float* record, long long* counters, omni_stream_t stream);
+int omni_adamw_apply_f32(float* params, float* exp_avg, float* exp_avg_sq, const void* segments, int nseg, const int* chunks, int nchunk,
+                         const float* record, int ngroups, omni_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * The 1x1 convolutions of the point-feature MLPs in training mode (csrc/omni_point_conv.hip): mlp_points1 / mlp_points2 of
  * model/spherical_model_iterative.py:290-305, 387-393 and mlp_points of model/spherical_model.py:228-235.  fp32 FMAs, no bias:
  *     y[m,hw,o] = sum_c w[o][c] . (x[m mod Mx, c, hw] . (scale ? scale[m,hw] : 1)),  c ascending, the product x . scale rounded first.

@@ -191,6 +191,9 @@ omni_upsample_bilinear2x_bwd_f32 i ppi4p
 omni_depth_heads_fwd_f32 i p7i4p
 omni_depth_heads_bwd_workspace_bytes z i3
 omni_depth_heads_bwd_f32 i p9i4pzp
+omni_adamw_grad_sqnorm_f32 i pipipp
+omni_adamw_prepare_f32 i pipidip3
+omni_adamw_apply_f32 i p4ipipip
 omni_point_conv_fwd_f32 i p4i5p
 omni_point_conv_bwd_workspace_bytes z i4
 omni_point_conv_bwd_f32 i p7i5pzp

@@ -34,8 +34,8 @@ those of `SYNCBN_REPLICATED` then takes its statistics over the batches of all r
 before the optimiser's step.
 
 The iterative model is model/trainable_iterative.py, a subclass.  Not built: DataParallel (threads in one
-process), fp16 storage of activations or weights, an image gradient, a hand-written optimiser (torch.optim.AdamW steps the parameters),
-capture of a whole step in a graph.  fp32 CUDA input, one device per process.
+process), fp16 storage of activations or weights, an image gradient, capture of a whole step (forward, backward, optimiser) in one
+graph.  The optimiser is omnifusion_amd.optim.AdamW (torch.optim.AdamW works as well).  fp32 CUDA input, one device per process.
 """
 import ctypes
 
