@@ -41,6 +41,8 @@ const OptName kOpts[] = {
     {"conv_epi_lds", "OMNI_CONV_EPI_LDS", &OmniOptions::conv_epi_lds, 1},
     {"conv_up2_persist", "OMNI_CONV_UP2_PERSIST", &OmniOptions::conv_up2_persist, 1},
     {"conv_up2_heads_taps", "OMNI_CONV_UP2_HEADS_TAPS", &OmniOptions::conv_up2_heads_taps, 1},
+    {"conv_up2_taps_walk", "OMNI_CONV_UP2_TAPS_WALK", &OmniOptions::conv_up2_taps_walk, 1},
+    {"conv_up2_taps_walk_grid", "OMNI_CONV_UP2_TAPS_WALK_GRID", &OmniOptions::conv_up2_taps_walk_grid, 0},
     {"splitk_max", "OMNI_SPLITK_MAX", &OmniOptions::splitk_max, 0},
     {"e2p_gather", "OMNI_E2P_GATHER", &OmniOptions::e2p_gather, 0},
     {"e2p_notab", "OMNI_E2P_NOTAB", &OmniOptions::e2p_notab, 0},

@@ -44,6 +44,8 @@ struct OmniOptions {
     int conv_epi_lds;     // OMNI_CONV_EPI_LDS   1 (default): split-half outputs of the convolution kernels leave through an LDS transposition, 16 bytes per lane | 0: 8 bytes per lane straight from the accumulators
     int conv_up2_persist; // OMNI_CONV_UP2_PERSIST 1 (default): conv3x3(up2(x)) with 32 -> 32 channels (de_conv4_0) on the persistent kernel with resident weights | 0: the halo kernel
     int conv_up2_heads_taps; // OMNI_CONV_UP2_HEADS_TAPS 1 (default; profiles/EXPERIMENTS.md, r29a): de_conv4_0 + heads (omni_conv3x3_up2_heads_sh_f16x3) at patches of 128 x 128 on up2_heads_taps_kernel (omni_conv_up2_heads_taps.hip: tap products on the low-resolution map; another fp32 summation order than the g1 kernel's, results agree to ~1e-6) | 0: conv3x3_up2_g1_kernel<HEADS>, which f16x1 and every other patch size keep whatever this says
+    int conv_up2_taps_walk; // OMNI_CONV_UP2_TAPS_WALK 1 (default; profiles/EXPERIMENTS.md, r31a): omni_conv3x3_up2_taps_sh_f16x3 (de_conv3_0, de_conv2_0) on up2_taps_walk_kernel (omni_conv_up2_taps.hip: eight waves, persistent blocks that walk bands with resident weights, no repeated fragment products; same bits) for the forms that were faster with three forwards in flight | 0: up2_taps_fused_kernel for both forms | 2: the new kernel for both forms | 3 / 4: for the band form (32-wide maps) / the whole-image form (16 x 16 maps) only
+    int conv_up2_taps_walk_grid; // OMNI_CONV_UP2_TAPS_WALK_GRID 0 (default): one block of up2_taps_walk_kernel per CU (a multiple of 8) or per unit | n > 0: at most n blocks, rounded down to a multiple of 8 and at least 8 (tests: one block walks many units at tiny shapes; same bits)
     int splitk_max;       // OMNI_SPLITK_MAX     cap of the split-K plan (0 = none)
     int e2p_gather;       // OMNI_E2P_GATHER     1: equi2pers always takes the direct-gather kernel (no LDS staging)
     int e2p_notab;        // OMNI_E2P_NOTAB      1: no per-geometry sampling-coordinate table

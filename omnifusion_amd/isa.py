@@ -12,7 +12,7 @@ found by measurement on MI355X:
     prevents it is a compiler flag in build.py — one object built without it, or a toolchain
     that ignores it, would re-open the hazard silently.  So the DISASSEMBLY is checked.
  2. the kernels that count their own `s_waitcnt vmcnt(N)` by hand (`e2p_box_kernel`,
-    `p2e_lds_kernel`, `p2e_walk_kernel`, `up2_taps_fused_kernel`, `up2_heads_taps_kernel`) must not spill: a scratch store/load in the middle of
+    `p2e_lds_kernel`, `p2e_walk_kernel`, `up2_taps_fused_kernel`, `up2_heads_taps_kernel`, `up2_taps_walk_kernel`) must not spill: a scratch store/load in the middle of
     the LDS-DMA pipeline shifts every hand-counted wait.  So `.private_segment_fixed_size` and
     the spill counts of those kernels are checked to be 0.
 
@@ -28,7 +28,7 @@ LLVM = os.environ.get("OMNI_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 FORBIDDEN = re.compile(r"\bv_pk_(mul|add|fma)_f32\b")
 # kernels whose correctness depends on hand-counted vmcnt: no scratch, no spills
-COUNTED = ("e2p_box_kernel", "p2e_lds_kernel", "p2e_walk_kernel", "e2p_ref_kernel", "up2_taps_fused_kernel", "up2_heads_taps_kernel")
+COUNTED = ("e2p_box_kernel", "p2e_lds_kernel", "p2e_walk_kernel", "e2p_ref_kernel", "up2_taps_fused_kernel", "up2_heads_taps_kernel", "up2_taps_walk_kernel")
 # kernels that hold >= 1 % of the bench's GPU time (profiles/r04e_bench_kernel_stats.txt): a spill there is a performance bug —
 # scratch 0 is required of every instantiation (conv_sh_kernel<128,128,4,2,3,4> carried 236 B of it)
 HOT = ("conv_sh_kernel", "conv3x3_halo_sh_kernel", "conv3x3_up2_g1_kernel", "stem_f16x3_pc_kernel", "heads_kernel", "maxpool_kernel",

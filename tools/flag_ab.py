@@ -40,3 +40,6 @@ for rnd in range(4):
 med = lambda x: sorted(x)[len(x) // 2]
 for v in VALS:
     print("B=%d %s=%d: pipelined %.0f pano/s   plain %.0f pano/s   one panorama %.3f ms" % (B, FLAG, v, med(acc[v][0]), med(acc[v][1]), med(acc[v][2])), flush=True)
+for v in VALS:                                                      # every round's figure: a difference counts where the ranges do not overlap
+    print("B=%d %s=%d rounds: pipelined %s   plain %s   one panorama %s" % (B, FLAG, v, " ".join("%.0f" % x for x in acc[v][0]), " ".join("%.0f" % x for x in acc[v][1]),
+                                                                              " ".join("%.3f" % x for x in acc[v][2])), flush=True)
