@@ -263,6 +263,9 @@ int omni_sh_to_f32(const void* src, float* dst, size_t n, omni_stream_t stream);
  * (reset != 0 clears it).  Synchronises the device: diagnostic only.  The fp32 reference has no such limit
  * (model/spherical_model.py runs fp32 end to end): a checkpoint that trips the flag needs OMNI_NET_PRECISION=fp32. */
 int omni_sh_overflow(int* flag, int reset);
+/* The non-GEMM operators of the network, from here to omni_mlp_points_f32 (csrc/omni_net.hip).  All of them return OMNI_ERR_INVALID before any
+ * launch for a null tensor (the two optional ones are named) or a dimension below 1; omni_maxpool3x3s2_f32 / omni_upsample_bilinear_f32 for C % 4 != 0
+ * (four channels per thread); the SH forms for C % 32 != 0; omni_add_period_* for period == 0 (the SH form also unless total and period are multiples of 32). */
 /* conv1 7x7 s2 p3 (3->64) + bn1 + ReLU, model/spherical_model.py:254.  src planar [M,3,P,P]
  * (OMNI_LAYOUT_BNCHW patches), wt [147][64] (k = (ky*7+kx)*3+c), dst NHWC [M,P/2,P/2,64]. */
 int omni_stem_f32(const float* src, const float* wt, const float* bias, float* dst, int M, int P, omni_stream_t stream);

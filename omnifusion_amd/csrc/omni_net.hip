@@ -460,6 +460,7 @@ extern "C" {
 
 int omni_stem_f32(const float* src, const float* wt, const float* bias, float* dst, int M, int P, omni_stream_t stream)
 {
+    if (!src || !wt || !bias || !dst || M < 1 || P < 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_stem_f32: null tensor or empty shape");
     if (P % 16) OMNI_FAIL(OMNI_ERR_INVALID, "omni_stem: patch size must be a multiple of 16");
     const int Po = P / 2;
     hipLaunchKernelGGL(stem_kernel<false>, dim3(M * (Po / 8) * (Po / 8)), dim3(256), 0, S_, src, wt, bias, (void*)dst, M, P, Po);
@@ -467,30 +468,37 @@ int omni_stem_f32(const float* src, const float* wt, const float* bias, float* d
 }
 int omni_maxpool3x3s2_f32(const float* src, float* dst, int M, int H, int W, int C, omni_stream_t stream)
 {
+    if (!src || !dst || M < 1 || H < 1 || W < 1 || C < 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_maxpool3x3s2_f32: null tensor or empty shape");
+    if (C % 4) OMNI_FAIL(OMNI_ERR_INVALID, "omni_maxpool3x3s2_f32: C must be a multiple of 4");
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     hipLaunchKernelGGL(maxpool_kernel<false>, dim3(nblk((size_t)M * Ho * Wo * C / 4)), dim3(256), 0, S_, (const void*)src, (void*)dst, M, H, W, C, Ho, Wo);
     OMNI_HIP(hipGetLastError()); return OMNI_OK;
 }
 int omni_upsample_bilinear_f32(const float* src, float* dst, int M, int H, int W, int C, int Ho, int Wo, omni_stream_t stream)
 {
+    if (!src || !dst || M < 1 || H < 1 || W < 1 || C < 1 || Ho < 1 || Wo < 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_upsample_bilinear_f32: null tensor or empty shape");
+    if (C % 4) OMNI_FAIL(OMNI_ERR_INVALID, "omni_upsample_bilinear_f32: C must be a multiple of 4");
     hipLaunchKernelGGL(upsample_kernel<false>, dim3(nblk((size_t)M * Ho * Wo * C / 4)), dim3(256), 0, S_, (const void*)src, (void*)dst, M, H, W, C, Ho, Wo,
                        (float)H / (float)Ho, (float)W / (float)Wo);
     OMNI_HIP(hipGetLastError()); return OMNI_OK;
 }
 int omni_add_hw_f32(float* x, const float* y, int M, int HW, int C, omni_stream_t stream)
 {
+    if (!x || !y || M < 1 || HW < 1 || C < 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_add_hw_f32: null tensor or empty shape");
     const size_t total = (size_t)M * HW * C;
     hipLaunchKernelGGL(add_hw_kernel, dim3(nblk(total)), dim3(256), 0, S_, x, y, total, HW, C);
     OMNI_HIP(hipGetLastError()); return OMNI_OK;
 }
 int omni_add_period_f32(float* x, const float* y, size_t total, size_t period, omni_stream_t stream)
 {
+    if (!x || !y || total < 1 || period < 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_add_period_f32: null tensor, empty tensor or period 0");
     hipLaunchKernelGGL(add_period_kernel, dim3(nblk(total)), dim3(256), 0, S_, x, y, total, period);
     OMNI_HIP(hipGetLastError()); return OMNI_OK;
 }
 // ---- the same operators on split-half (SH) activations (omni_sh.h); C % 32 == 0
 int omni_stem_sh(const float* src, const float* wt, const float* bias, void* dst, int M, int P, omni_stream_t stream)
 {
+    if (!src || !wt || !bias || !dst || M < 1 || P < 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_stem_sh: null tensor or empty shape");
     if (P % 16) OMNI_FAIL(OMNI_ERR_INVALID, "omni_stem: patch size must be a multiple of 16");
     const int Po = P / 2;
     hipLaunchKernelGGL(stem_kernel<true>, dim3(M * (Po / 8) * (Po / 8)), dim3(256), 0, S_, src, wt, bias, dst, M, P, Po);
@@ -498,6 +506,7 @@ int omni_stem_sh(const float* src, const float* wt, const float* bias, void* dst
 }
 int omni_maxpool3x3s2_sh(const void* src, void* dst, int M, int H, int W, int C, omni_stream_t stream)
 {
+    if (!src || !dst || M < 1 || H < 1 || W < 1 || C < 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_maxpool3x3s2_sh: null tensor or empty shape");
     if (C % 32) OMNI_FAIL(OMNI_ERR_INVALID, "SH tensors need C % 32 == 0");
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     hipLaunchKernelGGL(maxpool_kernel<true>, dim3(nblk((size_t)M * Ho * Wo * C / 4)), dim3(256), 0, S_, src, dst, M, H, W, C, Ho, Wo);
@@ -505,6 +514,7 @@ int omni_maxpool3x3s2_sh(const void* src, void* dst, int M, int H, int W, int C,
 }
 int omni_upsample_bilinear_sh(const void* src, void* dst, int M, int H, int W, int C, int Ho, int Wo, omni_stream_t stream)
 {
+    if (!src || !dst || M < 1 || H < 1 || W < 1 || C < 1 || Ho < 1 || Wo < 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_upsample_bilinear_sh: null tensor or empty shape");
     if (C % 32) OMNI_FAIL(OMNI_ERR_INVALID, "SH tensors need C % 32 == 0");
     hipLaunchKernelGGL(upsample_sh8_kernel, dim3(nblk((size_t)M * Ho * Wo * C / 8)), dim3(256), 0, S_, (const unsigned char*)src,
                        (unsigned char*)dst, M, H, W, C, Ho, Wo, (float)H / (float)Ho, (float)W / (float)Wo);
@@ -533,6 +543,7 @@ int omni_up2_tapsum_sh(const float* y, const float* bias, void* dst, int M, int 
 }
 int omni_add_hw_sh(void* x, const float* y, int M, int HW, int C, omni_stream_t stream)
 {
+    if (!x || !y || M < 1 || HW < 1 || C < 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_add_hw_sh: null tensor or empty shape");
     if (C % 32) OMNI_FAIL(OMNI_ERR_INVALID, "SH tensors need C % 32 == 0");
     const size_t total4 = (size_t)M * HW * C / 4;
     hipLaunchKernelGGL(add_hw_sh_kernel, dim3(nblk(total4)), dim3(256), 0, S_, x, y, total4, HW, C);
@@ -540,33 +551,39 @@ int omni_add_hw_sh(void* x, const float* y, int M, int HW, int C, omni_stream_t 
 }
 int omni_add_period_sh(void* x, const float* y, size_t total, size_t period, omni_stream_t stream)
 {
-    if (total % 32 || period % 32) OMNI_FAIL(OMNI_ERR_INVALID, "SH tensors need C % 32 == 0");
+    if (!x || !y || total < 1 || period < 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_add_period_sh: null tensor, empty tensor or period 0");
+    if (total % 32 || period % 32) OMNI_FAIL(OMNI_ERR_INVALID, "omni_add_period_sh: total and period must be multiples of 32");
     hipLaunchKernelGGL(add_period_sh_kernel, dim3(nblk(total / 4)), dim3(256), 0, S_, x, y, total / 4, period);
     OMNI_HIP(hipGetLastError()); return OMNI_OK;
 }
 int omni_layernorm512_sh(const float* x, const float* g, const float* b, void* y, int rows, float eps, omni_stream_t stream)
 {
+    if (!x || !g || !b || !y || rows < 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_layernorm512_sh: null tensor or no rows");
     hipLaunchKernelGGL(layernorm512_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, S_, x, g, b, y, rows, eps);
     OMNI_HIP(hipGetLastError()); return OMNI_OK;
 }
 int omni_attention_qkv_sh(const float* qkv, void* out, int B, int N, omni_stream_t stream)
 {
+    if (!qkv || !out || B < 1 || N < 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_attention_qkv_sh: null tensor or empty shape");
     if (N > 64) OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_attention: at most 64 tokens");
     hipLaunchKernelGGL(attention_kernel<true>, dim3(B * 4, (N + 3) / 4), dim3(256), 0, S_, qkv, qkv + 512, out, N, 0.08838834764831845f, 1536, 1536, 512);
     OMNI_HIP(hipGetLastError()); return OMNI_OK;
 }
 int omni_token_pack_f32(const float* d, const float* pos, float* tok, int M, int N, int HW, int C, omni_stream_t stream)
 {
+    if (!d || !pos || !tok || M < 1 || N < 1 || HW < 1 || C < 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_token_pack_f32: null tensor or empty shape");
     hipLaunchKernelGGL(token_pack_kernel, dim3(nblk((size_t)M * HW * C)), dim3(256), 0, S_, d, pos, tok, M, N, HW, C);
     OMNI_HIP(hipGetLastError()); return OMNI_OK;
 }
 int omni_layernorm512_f32(const float* x, const float* g, const float* b, float* y, int rows, float eps, omni_stream_t stream)
 {
+    if (!x || !g || !b || !y || rows < 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_layernorm512_f32: null tensor or no rows");
     hipLaunchKernelGGL(layernorm512_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, S_, x, g, b, (void*)y, rows, eps);
     OMNI_HIP(hipGetLastError()); return OMNI_OK;
 }
 int omni_attention_f32(const float* q, const float* kv, float* out, int B, int N, omni_stream_t stream)
 {
+    if (!q || !kv || !out || B < 1 || N < 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_attention_f32: null tensor or empty shape");
     if (N > 64) OMNI_FAIL(OMNI_ERR_UNSUPPORTED, "omni_attention: at most 64 tokens");
     hipLaunchKernelGGL(attention_kernel<false>, dim3(B * 4, (N + 3) / 4), dim3(256), 0, S_, q, kv, (void*)out, N, 0.08838834764831845f /* 128^-1/2 */, 512, 1024, 512);
     OMNI_HIP(hipGetLastError()); return OMNI_OK;
@@ -574,6 +591,7 @@ int omni_attention_f32(const float* q, const float* kv, float* out, int B, int N
 int omni_heads_f32(const float* x, const float* w, float bias_pred, float bias_weight, float* out_a, float* out_c,
                    int M, int P, int confidence, omni_stream_t stream)
 {
+    if (!x || !w || !out_a || M < 1 || P < 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_heads_f32: null tensor or empty shape");       // (out_c may be null)
     const int ht = (P + HT - 1) / HT;
     const int ntiles = M * ht * ht;
     hipLaunchKernelGGL(heads_kernel, dim3(ntiles < 768 ? ntiles : 768), dim3(256), 0, S_, x, w, bias_pred, bias_weight, out_a, out_c, M, P, confidence, ntiles);
@@ -582,6 +600,7 @@ int omni_heads_f32(const float* x, const float* w, float bias_pred, float bias_w
 int omni_mlp_points_f32(const float* xyz, const float* depth, const float* w1, const float* b1, const float* w2,
                         const float* b2, float* out, int Mo, int N, int HW, omni_stream_t stream)
 {
+    if (!xyz || !w1 || !b1 || !w2 || !b2 || !out || Mo < 1 || N < 1 || HW < 1) OMNI_FAIL(OMNI_ERR_INVALID, "omni_mlp_points_f32: null tensor or empty shape");   // (depth may be null)
     hipLaunchKernelGGL(mlp_points_kernel, dim3(nblk((size_t)Mo * HW)), dim3(256), 0, S_, xyz, depth, w1, b1, w2, b2, out, Mo, N, HW);
     OMNI_HIP(hipGetLastError()); return OMNI_OK;
 }

@@ -14,6 +14,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _glue_cases import f16x1_check, stem_f16x1_refs
 from _util import golden, smooth_erp
 
 pytestmark = pytest.mark.gpu
@@ -89,12 +90,9 @@ class _Options:
 
 
 def _check(out, ref_hi, ref_exact, scale, what):
-    """out within REL * scale of the hi-only reference; the hi-only and exact references at least 3x further apart somewhere"""
-    err = ((out.double().cpu() - ref_hi).abs() / scale).max().item()
-    gap = ((ref_exact - ref_hi).abs() / scale).max().item()
-    assert gap > 3 * REL, (what, "the gate would not tell f16x1 from f16x3 here", gap)
-    assert err <= REL, (what, err, gap)
-    return err
+    """out within REL * scale of the hi-only reference; the hi-only and exact references at least 3x further apart somewhere (tests/_glue_cases.py
+    holds the check: tests/test_glue_float64_gpu.py applies the same one to the stem's other launch forms)"""
+    return f16x1_check(out, ref_hi, ref_exact, scale, what, REL)
 
 
 # the shapes of test_conv2d_vs_torch: M, H, W, C1, C2, Cout, k, stride, pad, act, res
@@ -308,13 +306,7 @@ def test_stem_f16x1(opts, M):
     wk = torch.zeros(64, 3, 7, 8); wk[..., :7] = w
     W16 = split_weights_f16x3(torch.cat([wk.reshape(64, 168), torch.zeros(64, 24)], 1)).to(DEV)
     X, B = x.to(DEV), b.to(DEV)
-    xh = torch.where(x.abs() < 6.103515625e-05, torch.zeros_like(x), x).half().double()
-    wf = W16.double().cpu()
-    wh = wf[:, :, 0, :].reshape(64, 192)[:, :168].reshape(64, 3, 7, 8)[..., :7]
-    we = (wf[:, :, 0, :] + wf[:, :, 1, :] * 2.0 ** -11).reshape(64, 192)[:, :168].reshape(64, 3, 7, 8)[..., :7]
-    conv = lambda x_, w_: F.conv2d(x_, w_, stride=2, padding=3).permute(0, 2, 3, 1)
-    ref_hi, ref_ex = F.relu(conv(xh, wh) + b.double()), F.relu(conv(x.double(), we) + b.double())
-    scale = conv(xh.abs(), wh.abs()) + b.double().abs()
+    ref_hi, ref_ex, scale = stem_f16x1_refs(x, b, W16)
     with _Options(L, **opts):
         out = torch.full((M, P // 2, P // 2, 64), float("nan"), device=DEV)
         assert lib.omni_stem_sh_f16x1(_p(X), _p(W16), _p(B), _p(out), M, P, _stream()) == 0, lib.omni_last_error()
